@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X backend on BASELINE.json's metric: Goldilocks NTT field-elements/s (+ FRI.prove ms).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: torch.distributed.run, one rank per GPU)
+
+A plain run measures the headline and nothing else: set-up, bfs_ntt_tune, clock spin-up, W warmup steps, K timed steps, the outputs
+of the last step written under --dump-outputs, the JSON line (the headline keys, `config`, and `roofline`, which is priced from this
+run's HIP events and the tracked static files).  Everything else -- the CPU baseline and the sustained leg, the post-run guard and the
+all-gather of the roots, the direct-route timing, the other shapes, FRI, Merkle and prover legs, throughput modes and the
+cooperative proof -- runs only with --full; the --no-* switches then drop single legs of it.
+--dump-outputs DIR: after the timed steps, a fixed sample of the last step's output columns (per column, one seeded random position in
+each of k equal strides, k * columns = 2^20 in all) as DIR/ntt_output.npy (float64: the field elements, rounded), DIR/ntt_output_limbs16.npy
+(float32 [..., 4]: the same elements as exact little-endian 16-bit limbs, so one flipped bit shows as a difference >= 1) and
+DIR/ntt_output_index.npy (float64: the sampled positions within each column); arrays are [columns, k], 32 MiB in all.
 
 Workload (config 5 of BASELINE.json): `--total-columns` (default 8) independent trace columns of 2^24 base-field elements,
 sharded over the ranks by stark_brainfuck_amd.shard (column c lives on rank c mod N: 8 / 4 / 2 / 1 columns per GPU at N = 1 / 2 /
@@ -10,7 +20,8 @@ a rank (one bfs_gl_ntt call, batch = its columns).  `--scaling weak` gives every
 value = total field elements transformed per second over all ranks, timed over exactly K steps between barrier + device
 synchronisation on both sides, max over ranks.  After the timed region every rank commits to its output columns and the 64-byte
 roots are all-gathered (shard.gather_roots over RCCL: the only collective of the design, never inside the timed region).
-Extra keys on the same JSON line (kept under ~6 KB so that the driver's record carries every headline; per-kernel tables live in profiles/):
+Extra keys on the same JSON line (kept under ~6 KB so that the driver's record carries every headline; per-kernel tables live in profiles/;
+all but `roofline` come from --full):
     roofline      dominant kernel (the NTT tile kernel) vs the 8 TB/s HBM roofline, launch time from HIP events on the kernel's stream.
                   roofline.valu / hbm_physical / bound_actual: the integer-VALU issue fraction (static PMC instruction count over THIS run's
                   step time, at the nominal clock and at the clock sampled in the sustained leg) and the bytes really moved against the tile
@@ -116,7 +127,17 @@ def main():
     ap.add_argument("--stark-worker", type=float, default=0.0, help=argparse.SUPPRESS)   # internal: one prover PROCESS of bench_stark_concurrent
     ap.add_argument("--no-tune", action="store_true", help="do not call bfs_ntt_tune on the step's buffer pair (every step takes the direct route)")
     ap.add_argument("--no-check", action="store_true", help="skip the post-run round-trip check and root gather (PMC collection runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (CPU baseline, guard + roots, other shapes, FRI / Merkle / prover, "
+                         "throughput, cooperative proof); a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's output columns to DIR/*.npy (module docstring)")
     args = ap.parse_args()
+    if args.cooperative and not args.full:
+        ap.error("--cooperative times a --full leg: add --full")
+    if not args.full:
+        # a plain run is the headline only: every leg with a --no-* switch is off, and so is the direct-route timing (args.full below)
+        args.no_cpu = args.no_check = args.no_single = args.no_fri = args.no_stark = args.no_concurrent = args.no_cooperative = True
 
     if args.stark_worker > 0:
         raise SystemExit(stark_worker(args.stark_worker))
@@ -296,11 +317,14 @@ def main():
         elapsed, kern = float(t[0]), float(t[1])
     else:
         kern = kern_ms.value
+    # what the last timed step left in d_out, before any later leg writes it again
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, my_cols, n, total_cols, dist, rank)
 
     # ---- the same K steps on the direct route (what a caller who never calls bfs_ntt_tune gets): remembered pairs forgotten, W warm-up
     # steps, K timed ones between HIP events
     direct_ms = None
-    if tuned_route is not None:
+    if args.full and tuned_route is not None:
         _lib.check(lib.bfs_ntt_route_forget(None, None))
         for _ in range(max(args.warmup, 1)):
             step()
@@ -515,6 +539,34 @@ def main():
             del d_in, d_out
             line["stark_prove_cooperative"] = guarded_cooperative(world)
         print(json.dumps(slim(line, world), separators=(",", ":")), flush=True)
+
+
+DUMP_SAMPLES = 1 << 20          # sampled output elements over all columns (--dump-outputs: 32 bytes each on disk, 32 MiB in all)
+
+
+def dump_outputs(out_dir, d_out, my_cols, n, total_cols, dist, rank, stream=0):
+    """--dump-outputs: k = 2^20 / columns positions per column (one in each of k equal strides, offset drawn from a generator seeded with
+    (SEED, column)), read from the output columns after the timed steps; rank 0 writes every column's sample (module docstring)"""
+    k = max(1, min(n, DUMP_SAMPLES // total_cols))
+    stride = n // k
+    mine = {}
+    for j, c in enumerate(my_cols):
+        idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng([SEED, c]).integers(0, stride, k)
+        mine[c] = (idx, d_out.to_numpy(n, offset=j * n, stream=stream)[idx])
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        for p in parts:
+            mine.update(p)
+    if rank != 0:
+        return
+    idx = np.stack([mine[c][0] for c in range(total_cols)])
+    vals = np.stack([mine[c][1] for c in range(total_cols)])
+    limbs = np.stack([(vals >> np.uint64(16 * i)) & np.uint64(0xFFFF) for i in range(4)], axis=-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ntt_output.npy"), vals.astype(np.float64))
+    np.save(os.path.join(out_dir, "ntt_output_limbs16.npy"), limbs.astype(np.float32))
+    np.save(os.path.join(out_dir, "ntt_output_index.npy"), idx.astype(np.float64))
 
 
 def route_probe_info(lib):

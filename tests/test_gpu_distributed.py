@@ -79,7 +79,7 @@ def test_bench_under_torchrun_single_rank(scaling):
     box has: sharding through shard.assign_columns, the all-gather of the roots, one JSON line with the contract's keys"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--scaling", scaling, "--total-columns", "4", "--columns", "2", "--log-n", "20", "--no-fri", "--no-cpu", "--spinup-ms", "0"]
+           "--scaling", scaling, "--total-columns", "4", "--columns", "2", "--log-n", "20", "--full", "--no-fri", "--no-cpu", "--spinup-ms", "0"]
     res = subprocess.run(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -91,6 +91,37 @@ def test_bench_under_torchrun_single_rank(scaling):
     assert line["config"]["total_columns"] == (4 if scaling == "strong" else 2)
     assert line["roots_sha256"] and len(line["roots_sha256"]) == 64
     assert line["value"] > 1e9
+
+
+def test_plain_bench_times_the_headline_and_dumps_the_last_step(oracle, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, no --full: the line carries the headline keys and none of the other
+    legs, and the dumped sample (here every element: two 2^12 columns are under the 2^20 budget) is the oracle's forward transform of
+    the bench's inputs -- the limbs exactly, the rounded float64 to the last place"""
+    n, cols = 1 << 12, 2
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--log-n", "12",
+           "--total-columns", str(cols), "--spinup-ms", "0", "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 4 and line["ms_per_step"] > 0
+    for key in ("cpu_baseline", "sustained", "fri_prove", "stark_prove", "single_column_2p24", "merkle_tree_2p24"):
+        assert key not in line, key
+    assert line["guard"] is None and line["roots_sha256"] is None and line["ms_per_step_direct_route"] is None
+    import bench                    # (ROOT is on sys.path: conftest)
+    w = oracle.primitive_nth_root(n)
+    want = np.stack([oracle.ntt(w, bench.felt_array(bench.SEED + (c << 32), 0, n)) for c in range(cols)])
+    idx = np.load(tmp_path / "ntt_output_index.npy")
+    limbs = np.load(tmp_path / "ntt_output_limbs16.npy")
+    vals = np.load(tmp_path / "ntt_output.npy")
+    assert idx.shape == (cols, n) and (idx == np.arange(n)).all()
+    assert limbs.dtype == np.float32 and vals.dtype == np.float64 and limbs.shape == (cols, n, 4)
+    got = sum(limbs[..., i].astype(np.uint64) << np.uint64(16 * i) for i in range(4))
+    assert (got == want).all()
+    assert (vals == want.astype(np.float64)).all()
 
 
 def test_concurrent_provers_in_one_process(oracle):
@@ -275,7 +306,7 @@ def test_bench_with_two_ranks_on_one_gpu():
     the roots, and the cooperative proof -- with two ranks that share this GPU and exchange over gloo (BFS_BENCH_BACKEND / _DEVICE)"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--total-columns", "4", "--log-n", "20", "--no-cpu", "--spinup-ms", "0", "--cooperative"]
+           "--total-columns", "4", "--log-n", "20", "--full", "--no-cpu", "--spinup-ms", "0", "--cooperative"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BFS_BENCH_BACKEND="gloo", BFS_BENCH_DEVICE="0")
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -296,7 +327,7 @@ def test_bench_with_eight_ranks_on_one_gpu():
     equal to what verify() accepts.  No scaling number comes out of this -- it exercises the code path at the driver's world size."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--total-columns", "8", "--log-n", "20", "--no-cpu", "--spinup-ms", "0", "--cooperative", "--no-single", "--no-concurrent"]
+           "--total-columns", "8", "--log-n", "20", "--full", "--no-cpu", "--spinup-ms", "0", "--cooperative", "--no-single", "--no-concurrent"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BFS_BENCH_BACKEND="gloo", BFS_BENCH_DEVICE="0")
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=2400, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -336,7 +367,7 @@ def test_plain_bench_command_launches_its_own_ranks():
     bench.guarded_cooperative's separate job.  Two ranks share this
     box's one GPU and exchange over gloo (test hooks BFS_BENCH_BACKEND / BFS_BENCH_DEVICE)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--total-columns", "4",
-           "--log-n", "20", "--no-cpu", "--spinup-ms", "0"]
+           "--log-n", "20", "--full", "--no-cpu", "--spinup-ms", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BFS_BENCH_BACKEND="gloo", BFS_BENCH_DEVICE="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)

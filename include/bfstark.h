@@ -145,6 +145,36 @@ int bfs_xfe_mul_pointwise(const uint64_t* d_a, uint64_t a_stride, const uint64_t
                           uint64_t n, void* stream);
 int bfs_xfe_batch_inverse(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint64_t n, void* stream);
 
+/* ---- subproduct tree over an arbitrary set of base-field points ------------------------------------------------ */
+/*
+ * A handle on the subproduct tree of n >= 1 points x_0 .. x_{n-1} of F_p (leaves X - x_i, padded to a power of two with the constant
+ * 1): the node products, their transforms and the inverses of the reversed nodes that the remainder tree needs, all in HBM from the
+ * library's pool.  Several columns and calls reuse one tree, as Table.interpolate_columns interpolates every column over one domain
+ * (table.py:112-136).  Values and coefficients are base-field words; an extension-field column is its three limb planes, three columns.
+ *     bfs_ptree_build        the tree of d_points[0 .. n)                                   (ntt.py:82-97 for every node at once)
+ *     bfs_ptree_zerofier     d_out[0 .. n] = coefficients of prod (X - x_i), monic          fast_zerofier             ntt.py:82-97
+ *     bfs_ptree_evaluate     d_out[b][i] = P_b(x_i), P_b = n_coeffs coefficients at d_coeffs + b*in_stride (any n_coeffs; a
+ *                            polynomial with more than n coefficients is first reduced modulo the root)
+ *                                                                                           fast_evaluate             ntt.py:100-120
+ *     bfs_ptree_interpolate  d_out[b][0 .. n) = the coefficients of the polynomial of degree < n that takes the values
+ *                            d_values[b*in_stride + i] at x_i                               fast_interpolate          ntt.py:123-161
+ *     bfs_ptree_size         n
+ *     bfs_ptree_free         hands the tree's memory back to the pool, stream-ordered on `stream` (work on other streams that uses
+ *                            the tree must be finished or ordered before it)
+ * Stream-ordered: every call enqueues its kernels on `stream` and takes its temporaries from the pool; the tree is ready for work
+ * ordered after bfs_ptree_build on its stream.  bfs_ptree_interpolate synchronises the stream once (the batch inverse of Z'(x_i),
+ * as bfs_gl_batch_inverse): two equal points give BFS_ERR_ZERO_IN_BATCH_INVERSE and leave d_out unwritten.
+ */
+typedef struct bfs_ptree bfs_ptree;
+int bfs_ptree_build(const uint64_t* d_points, uint64_t n, void* stream, bfs_ptree** out);
+uint64_t bfs_ptree_size(const bfs_ptree* tree);
+int bfs_ptree_zerofier(const bfs_ptree* tree, uint64_t* d_out, void* stream);
+int bfs_ptree_evaluate(const bfs_ptree* tree, const uint64_t* d_coeffs, uint64_t n_coeffs, uint64_t in_stride, uint32_t batch,
+                       uint64_t* d_out, uint64_t out_stride, void* stream);
+int bfs_ptree_interpolate(const bfs_ptree* tree, const uint64_t* d_values, uint64_t in_stride, uint32_t batch, uint64_t* d_out,
+                          uint64_t out_stride, void* stream);
+int bfs_ptree_free(bfs_ptree* tree, void* stream);
+
 /* ---- proof stream / Fiat-Shamir (host) -------------------------------------------------------------------- */
 /*
  * ProofStream of the reference (ip.py:4-30): a list of Python objects, serialised with pickle.dumps and hashed

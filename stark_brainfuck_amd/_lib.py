@@ -56,6 +56,12 @@ _SIGNATURES = {
     "bfs_gl_batch_inverse": (ci, [vp, vp, u64, vp]),
     "bfs_xfe_mul_pointwise": (ci, [vp, u64, vp, u64, vp, u64, u64, vp]),
     "bfs_xfe_batch_inverse": (ci, [vp, u64, vp, u64, u64, vp]),
+    "bfs_ptree_build": (ci, [vp, u64, vp, ctypes.POINTER(vp)]),
+    "bfs_ptree_size": (u64, [vp]),
+    "bfs_ptree_zerofier": (ci, [vp, vp, vp]),
+    "bfs_ptree_evaluate": (ci, [vp, vp, u64, u64, u32, vp, u64, vp]),
+    "bfs_ptree_interpolate": (ci, [vp, vp, u64, u32, vp, u64, vp]),
+    "bfs_ptree_free": (ci, [vp, vp]),
     "bfs_ps_new": (vp, []),
     "bfs_ps_loads": (vp, [ctypes.c_char_p, sz]),
     "bfs_ps_free": (None, [vp]),

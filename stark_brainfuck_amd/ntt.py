@@ -6,17 +6,21 @@ Same functions, argument order, results and AssertionErrors:
     fast_multiply(lhs, rhs, root, order)   ntt.py:45-79     fast_coset_evaluate(poly, offset, g, n) ntt.py:164-168
     fast_coset_interpolate(offset, g, v)   ntt.py:171-174   batch_inverse(array)                    ntt.py:177-188
     fast_coset_divide(l, r, offset, g, n)  ntt.py:191-235
+    fast_zerofier(domain, root, order)     ntt.py:82-97     fast_evaluate(poly, domain, root, order)  ntt.py:100-120
+    fast_interpolate(domain, v, root, o)   ntt.py:123-161   (SubproductTree: the GPU subproduct tree behind these three)
 
 `values` may be a Python list of BaseFieldElement / ExtensionFieldElement objects (a new list of new objects comes
 back, as in the reference) or a BaseArray / XArray living in HBM (an array of the same kind comes back, nothing is
 copied to the host).  Every transform runs in the HIP kernels behind bfs_gl_ntt; there is no CPU fallback.
 """
+import ctypes
+
 import numpy as np
 
 from . import _lib
 from .algebra import BaseFieldElement
 from .arrays import BaseArray, XArray, raw_ntt
-from .device import current_stream
+from .device import current_stream, synchronize
 from .extension_field import ExtensionFieldElement
 from .univariate import Polynomial
 
@@ -279,33 +283,45 @@ def fast_coset_divide(lhs, rhs, offset, primitive_root, root_order):
     return Polynomial(quo.to_elements()[:lhs.degree() - rhs.degree() + 1])
 
 
+
+
 # ---- subproduct-tree routines (ntt.py:82-161): zerofier, multi-point evaluation, interpolation over an arbitrary domain.
-# Same divide-and-conquer as the reference; every product of degree >= 8 goes through fast_multiply (GPU transforms).
-def fast_zerofier(domain, primitive_root, root_order):
+#
+# The reference's recursion stays below under private names, exactly as it was (every product of degree >= 8 goes through fast_multiply,
+# every remainder through host long division).  A domain of base-valued points -- BaseFieldElements or lifted ExtensionFieldElements, what
+# Table.interpolate_columns builds (table.py:120-125) -- goes instead through the subproduct tree on the GPU (csrc/subproduct.hip), which
+# gives the same polynomials: the zerofier, the remainders and the interpolant are unique, and the recursion computes them exactly as long
+# as no product it forms wraps around in fast_multiply's cyclic transform.  fast_multiply transforms at order root_order at most, and the
+# largest product the recursion forms has degree len(domain) (the root of the zerofier), so len(domain) < root_order keeps every one exact.
+# Below TREE_MIN_POINTS the recursion is cheap and the list call keeps it.
+TREE_MIN_POINTS = 64
+
+
+def _fast_zerofier_recursive(domain, primitive_root, root_order):
     _check_root(primitive_root, root_order)
     if len(domain) == 0:
         return Polynomial([])
     if len(domain) == 1:
         return Polynomial([-domain[0], primitive_root.field.one()])
     half = len(domain) // 2
-    return fast_multiply(fast_zerofier(domain[:half], primitive_root, root_order),
-                         fast_zerofier(domain[half:], primitive_root, root_order), primitive_root, root_order)
+    return fast_multiply(_fast_zerofier_recursive(domain[:half], primitive_root, root_order),
+                         _fast_zerofier_recursive(domain[half:], primitive_root, root_order), primitive_root, root_order)
 
 
-def fast_evaluate(polynomial, domain, primitive_root, root_order):
+def _fast_evaluate_recursive(polynomial, domain, primitive_root, root_order):
     _check_root(primitive_root, root_order)
     if len(domain) == 0:
         return []
     if len(domain) == 1:
         return [polynomial.evaluate(domain[0])]
     half = len(domain) // 2
-    lz = fast_zerofier(domain[:half], primitive_root, root_order)
-    rz = fast_zerofier(domain[half:], primitive_root, root_order)
-    return (fast_evaluate(polynomial % lz, domain[:half], primitive_root, root_order) +
-            fast_evaluate(polynomial % rz, domain[half:], primitive_root, root_order))
+    lz = _fast_zerofier_recursive(domain[:half], primitive_root, root_order)
+    rz = _fast_zerofier_recursive(domain[half:], primitive_root, root_order)
+    return (_fast_evaluate_recursive(polynomial % lz, domain[:half], primitive_root, root_order) +
+            _fast_evaluate_recursive(polynomial % rz, domain[half:], primitive_root, root_order))
 
 
-def fast_interpolate(domain, values, primitive_root, root_order):
+def _fast_interpolate_recursive(domain, values, primitive_root, root_order):
     _check_root(primitive_root, root_order)
     assert len(domain) == len(values), "cannot interpolate over domain of different length than values list"
     if len(domain) == 0:
@@ -313,12 +329,186 @@ def fast_interpolate(domain, values, primitive_root, root_order):
     if len(domain) == 1:
         return Polynomial([values[0]])
     half = len(domain) // 2
-    lz = fast_zerofier(domain[:half], primitive_root, root_order)
-    rz = fast_zerofier(domain[half:], primitive_root, root_order)
-    left_offset = fast_evaluate(rz, domain[:half], primitive_root, root_order)
-    right_offset = fast_evaluate(lz, domain[half:], primitive_root, root_order)
+    lz = _fast_zerofier_recursive(domain[:half], primitive_root, root_order)
+    rz = _fast_zerofier_recursive(domain[half:], primitive_root, root_order)
+    left_offset = _fast_evaluate_recursive(rz, domain[:half], primitive_root, root_order)
+    right_offset = _fast_evaluate_recursive(lz, domain[half:], primitive_root, root_order)
     left_targets = [v / d for v, d in zip(values[:half], left_offset)]
     right_targets = [v / d for v, d in zip(values[half:], right_offset)]
-    li = fast_interpolate(domain[:half], left_targets, primitive_root, root_order)
-    ri = fast_interpolate(domain[half:], right_targets, primitive_root, root_order)
+    li = _fast_interpolate_recursive(domain[:half], left_targets, primitive_root, root_order)
+    ri = _fast_interpolate_recursive(domain[half:], right_targets, primitive_root, root_order)
     return li * rz + ri * lz
+
+
+class SubproductTree:
+    """The subproduct tree of a set of base-field points, built once on the GPU and reused for any number of columns
+    (bfs_ptree_*, include/bfstark.h).  `domain` is a BaseArray or a list of BaseFieldElements / lifted ExtensionFieldElements.
+
+        zerofier()          BaseArray of the n + 1 coefficients of prod (X - x_i), low degree first (fast_zerofier, ntt.py:82-97)
+        evaluate(coeffs)    coefficients -> values at the n points: a BaseArray of `batch` columns gives a BaseArray of `batch`
+                            columns of n values, an XArray an XArray (fast_evaluate, ntt.py:100-120)
+        interpolate(values) values at the n points -> the n coefficients of the interpolant, same kinds (fast_interpolate, ntt.py:123-161)
+
+    Nothing is copied to the host; interpolate() synchronises once (the batch inverse of Z'(x_i)) and raises the reference's
+    AssertionError of batch_inverse when two points are equal."""
+
+    def __init__(self, domain):
+        self._h = None
+        if isinstance(domain, BaseArray):
+            if domain.batch != 1:
+                raise ValueError("a domain is one column of points")
+            pts = domain
+        else:
+            values = _base_points(domain)
+            if values is None:
+                raise ValueError("SubproductTree needs points of the base field (genuine extension elements are not)")
+            pts = BaseArray.from_numpy(np.array(values, dtype=np.uint64))
+        self.n, self.field = len(pts), pts.field
+        if self.n == 0:
+            raise ValueError("SubproductTree needs at least one point")
+        self._stream = current_stream()
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().bfs_ptree_build(pts.ptr, self.n, self._stream, ctypes.byref(h)))
+        self._h = h.value
+
+    def __len__(self):
+        return self.n
+
+    def zerofier(self):
+        out = BaseArray.empty(self.n + 1, self.field)
+        _lib.check(_lib.load().bfs_ptree_zerofier(self._h, out.ptr, current_stream()))
+        return out
+
+    def evaluate(self, coeffs):
+        lib, st = _lib.load(), current_stream()
+        if isinstance(coeffs, XArray):
+            out = XArray.empty(self.n, coeffs.field)
+            _lib.check(lib.bfs_ptree_evaluate(self._h, coeffs.ptr, coeffs.n, coeffs.stride, 3, out.ptr, out.stride, st))
+            return out
+        if isinstance(coeffs, BaseArray):
+            out = BaseArray.empty(self.n, coeffs.field, coeffs.batch)
+            _lib.check(lib.bfs_ptree_evaluate(self._h, coeffs.ptr, coeffs.n, coeffs.n, coeffs.batch, out.ptr, self.n, st))
+            return out
+        raise TypeError("evaluate() takes a BaseArray or an XArray of coefficients")
+
+    def interpolate(self, values):
+        assert len(values) == self.n, "cannot interpolate over domain of different length than values list"
+        lib, st = _lib.load(), current_stream()
+        if isinstance(values, XArray):
+            out = XArray.empty(self.n, values.field)
+            _lib.check(lib.bfs_ptree_interpolate(self._h, values.ptr, values.stride, 3, out.ptr, out.stride, st))
+            return out
+        if isinstance(values, BaseArray):
+            out = BaseArray.empty(self.n, values.field, values.batch)
+            _lib.check(lib.bfs_ptree_interpolate(self._h, values.ptr, values.n, values.batch, out.ptr, self.n, st))
+            return out
+        raise TypeError("interpolate() takes a BaseArray or an XArray of values")
+
+    def free(self):
+        """hand the tree's memory back to the library's pool (stream-ordered, like DeviceBuffer.free)"""
+        if self._h:
+            stream = current_stream()
+            if stream != self._stream:
+                synchronize(stream)
+            _lib.load().bfs_ptree_free(self._h, self._stream)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _base_points(domain):
+    """int values of a list of BaseFieldElements / lifted ExtensionFieldElements; None if any point is a genuine extension element"""
+    out = []
+    for x in domain:
+        if isinstance(x, BaseFieldElement):
+            out.append(x.value)
+        elif isinstance(x, ExtensionFieldElement) and not _is_genuine_extension(x):
+            c = x.polynomial.coefficients
+            out.append(c[0].value if c else 0)
+        else:
+            return None
+    return out
+
+
+def _tree_points(domain, primitive_root, root_order, items=()):
+    """the domain's int values when a list call goes to the subproduct tree, else None.  Besides the size rule above, the domain, the
+    root and the values / coefficients must all be of one element type: either all BaseFieldElements or all ExtensionFieldElements
+    (the domain then lifted base elements).  Those are the two mixes the recursion computes at all -- it multiplies a BaseFieldElement
+    by an ExtensionFieldElement at its leaves otherwise, which raises (algebra.py BaseField.multiply reads `.value`,
+    ExtensionField.multiply `.polynomial`) -- and its results are then of that same type throughout: fast_multiply returns lifted
+    elements exactly when its operands are extension elements (ntt.py:59-79)."""
+    if not TREE_MIN_POINTS <= len(domain) < root_order:
+        return None
+    kind = type(primitive_root)
+    if kind not in (BaseFieldElement, ExtensionFieldElement):
+        return None
+    if any(type(x) is not kind for x in domain) or any(type(v) is not kind for v in items):
+        return None
+    return _base_points(domain)
+
+
+def _tree_of(values):
+    return SubproductTree(BaseArray.from_numpy(np.array(values, dtype=np.uint64)))
+
+
+def _elements(arr, kind):
+    """the element objects of a base-field BaseArray: BaseFieldElements, or lifted ExtensionFieldElements as an XArray gives them"""
+    if kind is BaseFieldElement:
+        return arr.to_elements()
+    soa = np.zeros((3, arr.n), dtype=np.uint64)
+    soa[0] = arr.to_numpy()
+    return XArray.from_numpy(soa).to_elements()
+
+
+def _column(items, kind):
+    """device array of list values / coefficients of element type `kind`"""
+    return XArray.from_elements(items) if kind is ExtensionFieldElement else BaseArray.from_elements(items)
+
+
+def _from_column(arr, kind):
+    return arr.to_elements() if isinstance(arr, XArray) else _elements(arr, kind)
+
+
+def fast_zerofier(domain, primitive_root, root_order):
+    _check_root(primitive_root, root_order)
+    if isinstance(domain, BaseArray):
+        return SubproductTree(domain).zerofier() if len(domain) else BaseArray.empty(0, domain.field)
+    pts = _tree_points(domain, primitive_root, root_order)
+    if pts is None:
+        return _fast_zerofier_recursive(domain, primitive_root, root_order)
+    return Polynomial(_elements(_tree_of(pts).zerofier(), type(primitive_root)))
+
+
+def fast_evaluate(polynomial, domain, primitive_root, root_order):
+    _check_root(primitive_root, root_order)
+    if isinstance(domain, BaseArray):
+        coeffs = polynomial if isinstance(polynomial, (BaseArray, XArray)) else _coeff_array(polynomial.coefficients)
+        return SubproductTree(domain).evaluate(coeffs)
+    pts = _tree_points(domain, primitive_root, root_order, polynomial.coefficients)
+    if pts is None:
+        return _fast_evaluate_recursive(polynomial, domain, primitive_root, root_order)
+    kind = type(primitive_root)
+    return _from_column(_tree_of(pts).evaluate(_column(polynomial.coefficients, kind)), kind)
+
+
+def fast_interpolate(domain, values, primitive_root, root_order):
+    _check_root(primitive_root, root_order)
+    assert len(domain) == len(values), "cannot interpolate over domain of different length than values list"
+    if isinstance(domain, BaseArray):
+        if not len(domain):
+            return values
+        return SubproductTree(domain).interpolate(values if isinstance(values, (BaseArray, XArray)) else _coeff_array(values))
+    pts = _tree_points(domain, primitive_root, root_order, values)
+    if pts is None:
+        return _fast_interpolate_recursive(domain, values, primitive_root, root_order)
+    kind = type(primitive_root)
+    try:
+        coeffs = _tree_of(pts).interpolate(_column(values, kind))
+    except AssertionError:
+        # two equal points (Z'(x_i) = 0): the recursion runs into them its own way and reports that
+        return _fast_interpolate_recursive(domain, values, primitive_root, root_order)
+    return Polynomial(_from_column(coeffs, kind))

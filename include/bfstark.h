@@ -506,6 +506,26 @@ int bfs_air_counts(int table, int counts[3]);
  * terminal order (NOT divided by the zerofiers).  Challenges / terminals / params as for bfs_air_quotients. */
 int bfs_air_evaluate(int table, const uint64_t* base_row, const uint64_t* base_next, const uint64_t* ext_row, const uint64_t* ext_next,
                      const uint64_t* h_challenges, const uint64_t* h_terminals, const uint64_t* h_params, uint64_t* out);
+/*
+ * Trace checking: Table.test / Table.xtest (table.py:48-110) on the GPU, answering which constraint fails, on which row first, on
+ * how many rows.  Base column c of the trace at d_base + c*ld, limb l of extension column k at d_ext + (3k+l)*ld; ld >= rows, any
+ * row count (0: nothing is evaluated).  Boundary constraints run on row 0, transition constraints on the pairs (r, r+1) for
+ * r < rows - 1 (no cyclic wrap), terminal constraints on row rows - 1.  Operands are reduced mod p on load.
+ *   extended == 0: the base AIR (stark_brainfuck_amd/air.py TableAir.base: processor_table.py:123-201, instruction_table.py:27-56,
+ *                  memory_table.py:46-112), counts[0] + counts[1] entries of h_out; d_ext, challenges, terminals and params may be NULL.
+ *   extended == 1: the full AIR, bfs_air_num_quotients(table) entries (boundary, transition, terminal order); challenges / terminals /
+ *                  params as for bfs_air_quotients (params NULL = 1).
+ * h_out[q].first_row = the lowest failing row (of a transition pair: its current row), UINT64_MAX if none; h_out[q].count = the number
+ * of failing rows.  Failing rows are data, not errors (BFS_OK).  Synchronises the stream.
+ */
+typedef struct bfs_air_violation {
+    uint64_t first_row;
+    uint64_t count;
+} bfs_air_violation;
+/* counts[0] = base boundary, counts[1] = base transition constraints of `table` */
+int bfs_air_base_counts(int table, int counts[2]);
+int bfs_air_check(int table, int extended, const uint64_t* d_base, const uint64_t* d_ext, uint64_t rows, uint64_t ld,
+                  const uint64_t* h_challenges, const uint64_t* h_terminals, const uint64_t* h_params, bfs_air_violation* h_out, void* stream);
 int bfs_air_quotients(int table, const uint64_t* d_base, const uint64_t* d_ext, uint64_t* d_out, uint32_t log_n, uint64_t unit_distance,
                       uint64_t height, uint64_t omicron_inv, uint64_t offset, uint64_t omega, const uint64_t* h_challenges,
                       const uint64_t* h_terminals, const uint64_t* h_params, void* stream);

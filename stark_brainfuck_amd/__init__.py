@@ -22,8 +22,9 @@ from .salted_merkle import SaltedMerkle
 from .ip import ProofStream, reference_pickle
 from .fri import Fri
 from ._lib import BackendUnavailable
+from .table import AirViolation, AirViolationError
 
 __all__ = ["BaseField", "BaseFieldElement", "xgcd", "Polynomial", "colinear", "ExtensionField",
            "ExtensionFieldElement", "BaseArray", "XArray", "ntt", "intt", "fast_multiply", "fast_coset_evaluate",
            "fast_coset_interpolate", "batch_inverse", "fast_coset_divide", "SubproductTree", "Merkle", "SaltedMerkle", "ProofStream",
-           "reference_pickle", "Fri", "BackendUnavailable"]
+           "reference_pickle", "Fri", "BackendUnavailable", "AirViolation", "AirViolationError"]

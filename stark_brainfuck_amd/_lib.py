@@ -143,6 +143,8 @@ _SIGNATURES = {
     "bfs_difference_combine_rows": (ci, [vp, vp, u32, u64, u64, vp, vp, vp, u64, u64, vp]),
     "bfs_zerofier_inverses_rows": (ci, [u32, u64, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u64), vp, u64, u64, vp]),
     "bfs_air_counts": (ci, [ci, ctypes.POINTER(ci)]),
+    "bfs_air_base_counts": (ci, [ci, ctypes.POINTER(ci)]),
+    "bfs_air_check": (ci, [ci, ci, vp, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp]),
     "bfs_stark_verify_begin": (ci, [vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci)]),
     "bfs_stark_verify_finish": (ci, [vp, vp, ctypes.POINTER(u64), u32, ctypes.POINTER(ci)]),
     "bfs_stark_session_new": (vp, []),
@@ -156,6 +158,11 @@ _SIGNATURES = {
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
     _fields_ = [("d_base", vp), ("nwords", u32), ("stride", u32), ("out_offset", u64)]
+
+
+class AirViolation(ctypes.Structure):
+    """bfs_air_violation (include/bfstark.h)"""
+    _fields_ = [("first_row", u64), ("count", u64)]
 
 
 class RowColumn(ctypes.Structure):

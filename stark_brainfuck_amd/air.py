@@ -127,11 +127,22 @@ class TableAir:
     def transition(self): raise NotImplementedError
     def terminal(self): raise NotImplementedError
 
+    # the BASE AIR: what the reference's Table.test() checks on the base trace (table.py:48-70), restated from its
+    # base_boundary_constraints / base_transition_constraints in their order.  Variables are base columns only.
+    def base_boundary(self): return []
+    def base_transition(self): return []
+
     def all(self):
         """the three constraint lists; built once (the graphs are symbolic in challenges, terminals and parameters)"""
         if getattr(self, "_all", None) is None:
             self._all = [("boundary", self.boundary()), ("transition", self.transition()), ("terminal", self.terminal())]
         return self._all
+
+    def base(self):
+        """the base constraint lists: [("boundary", ...), ("transition", ...)], built once"""
+        if getattr(self, "_base", None) is None:
+            self._base = [("boundary", self.base_boundary()), ("transition", self.base_transition())]
+        return self._base
 
 
 class ProcessorAir(TableAir):
@@ -192,6 +203,27 @@ class ProcessorAir(TableAir):
     def boundary(self):
         return [var(i) for i in (self.CLK, self.IP, self.MP, self.MV, self.MVI, self.IEV, self.OEV)]
 
+    def base_boundary(self):
+        """processor_table.py:185-201"""
+        return [var(i) for i in (self.CLK, self.IP, self.MP, self.MV, self.MVI)]
+
+    def base_transition(self):
+        """processor_table.py:123-183: the instruction polynomials carry the factor ci themselves (:114-117), so they vanish on
+        padding rows as the extended ones do; then the clock and the memory-value-inverse rules"""
+        cur = [var(i) for i in range(self.base_width)]
+        nxt = [var(i, True) for i in range(self.base_width)]
+        ci, mv, mvi = cur[self.CI], cur[self.MV], cur[self.MVI]
+        polys = [None, None, None]
+        for c in "[]<>+-,.":
+            instr = self._instruction_polynomials(c, cur, nxt)
+            des = deselector(c, ci)
+            for i in range(3):
+                if instr[i] is not None:
+                    t = des * (instr[i] * ci)
+                    polys[i] = t if polys[i] is None else polys[i] + t
+        mv_is_zero = mv * mvi - 1
+        return polys + [nxt[self.CLK] - cur[self.CLK] - 1, mv * mv_is_zero, mvi * mv_is_zero]
+
     def terminal(self):
         x = [var(i) for i in range(11)]
         d, e, f = chal(D), chal(EE), chal(F)
@@ -226,6 +258,19 @@ class InstructionAir(TableAir):
         x = [var(i) for i in range(5)]
         return [x[self.ADDR], x[self.EVAL] - chal(A) * x[self.ADDR] - chal(B) * x[self.CI] - chal(C) * x[self.NI]]
 
+    def base_boundary(self):
+        """instruction_table.py:52-56"""
+        return [var(self.ADDR)]
+
+    def base_transition(self):
+        """instruction_table.py:27-50"""
+        addr, ci, ni = (var(i) for i in range(3))
+        addr_n, ci_n, ni_n = (var(i, True) for i in range(3))
+        return [(addr_n - addr - 1) * (addr_n - addr),
+                (addr_n - addr) * (ni - ci_n),
+                (addr_n - addr - 1) * (ci_n - ci),
+                (addr_n - addr - 1) * (ni_n - ni)]
+
     def terminal(self):
         return [var(self.PERM) - term(0), var(self.EVAL) - term(4)]
 
@@ -249,6 +294,21 @@ class MemoryAir(TableAir):
 
     def boundary(self):
         return [var(self.CLK), var(self.MP), var(self.MV)]
+
+    def base_boundary(self):
+        """memory_table.py:103-112"""
+        return [var(self.CLK), var(self.MP), var(self.MV)]
+
+    def base_transition(self):
+        """memory_table.py:46-101"""
+        clk, mp, mv, dm = (var(i) for i in range(4))
+        clk_n, mp_n, mv_n, dm_n = (var(i, True) for i in range(4))
+        return [(mp_n - mp - 1) * (mp_n - mp),
+                (mp_n - mp) * mv_n,
+                (dm_n - 1) * dm_n,
+                dm * (mp_n - mp),
+                dm * (mv_n - mv),
+                (mp_n - 1 - mp) * (clk_n - 1 - clk)]
 
     def terminal(self):
         clk, mp, mv, dm, perm = (var(i) for i in range(5))

@@ -37,7 +37,8 @@ from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
 from .algebra import P_GOLDILOCKS
-from .table import extend_tables_device, lde_tables, prepare_extension, sample_ext, sample_ext_many, zerofier_inverses
+from .table import (AirViolation, AirViolationError, extend_tables_device, lde_tables, prepare_extension, sample_ext, sample_ext_many,
+                    zerofier_inverses)
 from .univariate import Polynomial
 from .vm import VirtualMachine
 
@@ -144,6 +145,8 @@ class BrainfuckStark:
     keep_intermediates = False      # True: prove() leaves trees, quotient codewords and the combination codeword in `_last` (tests)
     stage_timing = False            # True: prove() synchronises its stream after every stage so that `timing` splits the GPU time by stage
                                     # (bench.py's breakdown, tools/); False: `timing` holds host time per stage and the stages overlap freely
+    check_air = False               # True: prove() takes the Python stage path and checks the full AIR on the extended trace in HBM
+                                    # (bfs_air_check) before any quotient or FRI work; a violation raises AirViolationError
 
     # ---- several GPUs on one proof (shard.RowShardedSaltedMerkle): every rank runs the polynomial stages on all columns and hashes
     # only its range of the zipped rows; set by cooperate() and used inside shard.shared_randomness()
@@ -319,7 +322,7 @@ class BrainfuckStark:
         from .table import sample_base
         if os.environ.get("BFS_NATIVE_PROVE", "1") == "0" or not self.native_stages:
             return None
-        if (self._cooperation is not None or self.keep_intermediates or self.stage_timing or self._row_windows is not None
+        if (self._cooperation is not None or self.keep_intermediates or self.stage_timing or self.check_air or self._row_windows is not None
                 or self._shift_tweak is not None):
             return None
         # tables in the order of self.tables: processor, instruction, memory, input, output
@@ -590,6 +593,10 @@ class BrainfuckStark:
         initials = [sample_ext(draw(3 * 8)) for _ in self.permutation_arguments]
         extend_tables_device(self.tables, challenges, initials, prepared=prepared_extension)   # prefix scans on the trace columns lde() left in HBM
         terminals = self.get_terminals()
+        if self.check_air:              # the trace against the AIR it is about to be proven for, on the columns in HBM
+            violations = [v for t in self.tables if t.length for v in t.air_violations(challenges, terminals)]
+            if violations:
+                raise AirViolationError(violations)
         lap("extend")
 
         # extension codewords and their commitment (:194-201)
@@ -781,6 +788,57 @@ class BrainfuckStark:
         return proof
 
     # ------------------------------------------------------------------------------------------------------------
+    def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):
+        """Which constraints an execution trace breaks, on the GPU: a list of AirViolation, empty for an honest trace.  The base AIR of
+        every table on the matrices as given (test_vm.py::test_air); with challenges (11 triples) and initials (2 triples) also the
+        full AIR on padded, extended copies, each table against its own terminals, and then what no single table's AIR sees -- the
+        terminals of the two permutation arguments (processor against instruction / memory table) and the input, output and
+        program evaluation terminals against this stark's input_symbols, output_symbols and program (what verify() checks).
+        Those come back as kind "permutation" (index 0 instruction, 1 memory) / "evaluation" (0 input, 1 output, 2 program) with
+        first_row None.  The caller's matrices are left as they are."""
+        import copy
+        matrices = {0: processor_matrix, 1: instruction_matrix, 2: memory_matrix, 3: input_matrix, 4: output_matrix}
+        tables = []
+        for t in self.tables:
+            c = copy.copy(t)
+            c.matrix = matrices[t.table_index]
+            c._array_for = None
+            c.length = len(c.matrix)              # (the matrices given, not the claim this stark was made for)
+            c.height = c.roundup_npo2(c.length)
+            c.ext_columns = c._base_device = c._ext_device = c.base_codewords = c.ext_codewords = None
+            tables.append(c)
+        violations = [v for t in tables for v in t.air_violations()]
+        if challenges is None:
+            return violations
+        challenges = [tuple(int(x) for x in (c.limbs() if hasattr(c, "limbs") else c)) for c in challenges]
+        initials = [tuple(int(x) for x in (c.limbs() if hasattr(c, "limbs") else c)) for c in initials]
+        for t in tables:
+            t.pad()
+        for t in tables:
+            t.extend(challenges, initials)
+        pt, it, mt, inp, outp = tables
+        own = [pt.instruction_permutation_terminal, pt.memory_permutation_terminal, pt.input_evaluation_terminal,
+               pt.output_evaluation_terminal, it.evaluation_terminal]
+        for t in tables:
+            terminals = list(own)
+            if t is it:
+                terminals[0] = it.permutation_terminal
+            elif t is mt:
+                terminals[1] = mt.permutation_terminal
+            elif t is inp:
+                terminals[2] = inp.evaluation_terminal
+            elif t is outp:
+                terminals[3] = outp.evaluation_terminal
+            if t.length:
+                violations += t.air_violations(challenges, terminals)
+        pairs = [("processor", "permutation", 0, pt.instruction_permutation_terminal, it.permutation_terminal),
+                 ("processor", "permutation", 1, pt.memory_permutation_terminal, mt.permutation_terminal)]
+        for k, (name, terminal) in enumerate((("processor", pt.input_evaluation_terminal), ("processor", pt.output_evaluation_terminal),
+                                              ("instruction", it.evaluation_terminal))):
+            pairs.append((name, "evaluation", k, terminal, self.evaluation_arguments[k].compute_terminal(challenges)))
+        violations += [AirViolation(name, kind, k, None, 1) for name, kind, k, lhs, rhs in pairs if tuple(lhs) != tuple(rhs)]
+        return violations
+
     def verify(self, proof, proof_stream=None):
         """brainfuck_stark.py:343-579 -- host only, like the reference's verifier: Merkle paths of the opened rows, the
         non-linear combination recomputed from the opened rows (constraints evaluated through air.evaluate), FRI, and the

@@ -9,7 +9,7 @@
 #include <cstddef>
 #include <vector>
 
-#include "air_generated.hpp"
+#include "air_eval.hpp"
 #include "lazy.hpp"
 #include "runtime.hpp"
 
@@ -103,13 +103,6 @@ struct AirArgs {
     Xfe pr[1];
 };
 
-template <int TABLE> struct AirShape;
-template <> struct AirShape<0> { static constexpr int BW = airgen::PROCESSOR_BASE_WIDTH, XW = airgen::PROCESSOR_EXT_WIDTH, NB = airgen::PROCESSOR_NUM_BOUNDARY, NT = airgen::PROCESSOR_NUM_TRANSITION, NZ = airgen::PROCESSOR_NUM_TERMINAL; };
-template <> struct AirShape<1> { static constexpr int BW = airgen::INSTRUCTION_BASE_WIDTH, XW = airgen::INSTRUCTION_EXT_WIDTH, NB = airgen::INSTRUCTION_NUM_BOUNDARY, NT = airgen::INSTRUCTION_NUM_TRANSITION, NZ = airgen::INSTRUCTION_NUM_TERMINAL; };
-template <> struct AirShape<2> { static constexpr int BW = airgen::MEMORY_BASE_WIDTH, XW = airgen::MEMORY_EXT_WIDTH, NB = airgen::MEMORY_NUM_BOUNDARY, NT = airgen::MEMORY_NUM_TRANSITION, NZ = airgen::MEMORY_NUM_TERMINAL; };
-template <> struct AirShape<3> { static constexpr int BW = airgen::INPUT_BASE_WIDTH, XW = airgen::INPUT_EXT_WIDTH, NB = airgen::INPUT_NUM_BOUNDARY, NT = airgen::INPUT_NUM_TRANSITION, NZ = airgen::INPUT_NUM_TERMINAL; };
-template <> struct AirShape<4> { static constexpr int BW = airgen::OUTPUT_BASE_WIDTH, XW = airgen::OUTPUT_EXT_WIDTH, NB = airgen::OUTPUT_NUM_BOUNDARY, NT = airgen::OUTPUT_NUM_TRANSITION, NZ = airgen::OUTPUT_NUM_TERMINAL; };
-
 // the NEXT row of a thread kept in LDS ([value][thread], 64-bit words) and fetched where the constraint code uses it: 38 fewer live
 // registers in the processor table's combine kernel (A/B switch BFS_COMBINE_LDS_NEXT, profiles/r03/ab_combine_lds_next.txt)
 struct LdsNextBase {
@@ -120,15 +113,6 @@ struct LdsNextExt {
     const u64* p;
     __device__ __forceinline__ Xfe operator[](int k) const { return Xfe{{p[(3 * k) * 256], p[(3 * k + 1) * 256], p[(3 * k + 2) * 256]}}; }
 };
-
-template <int TABLE, class Sink, class BN, class XN>
-__device__ __forceinline__ void air_eval(const u64* bc, BN bn, const Xfe* xc, XN xn, const AirArgs& a, Sink& sink) {
-    if constexpr (TABLE == 0) airgen::air_processor(bc, bn, xc, xn, a.ch, a.tm, a.pr, sink);
-    else if constexpr (TABLE == 1) airgen::air_instruction(bc, bn, xc, xn, a.ch, a.tm, a.pr, sink);
-    else if constexpr (TABLE == 2) airgen::air_memory(bc, bn, xc, xn, a.ch, a.tm, a.pr, sink);
-    else if constexpr (TABLE == 3) airgen::air_input(bc, bn, xc, xn, a.ch, a.tm, a.pr, sink);
-    else airgen::air_output(bc, bn, xc, xn, a.ch, a.tm, a.pr, sink);
-}
 
 // zerofier inverses at x with ONE field inversion (Montgomery's trick over a = x - 1, b = x - omicron^-1, c = x^h - 1):
 //   boundary 1 / a (table.py:153-155), terminal 1 / b (:253-256), transition b / c (:180-188; 0 for an empty table)

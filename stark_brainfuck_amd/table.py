@@ -18,6 +18,7 @@ when `extend` (not `extend_device`) made them.
 """
 import ctypes
 import itertools
+from collections import namedtuple
 from os import urandom          # module-level on purpose: tests patch `table.urandom` for determinism
 from .randomness import source as random_source
 
@@ -336,6 +337,37 @@ def staging_empty(shape):
         except Exception:
             _POOLS["pinned"] = False
     return np.empty(shape, dtype=np.uint64)
+
+
+# one constraint that fails on the rows of a trace: table name, kind ("boundary" / "transition" / "terminal"), position within its kind
+# (as the reference numbers it), lowest failing row (of a transition pair: its current row), number of failing rows.  BrainfuckStark.
+# check_trace also reports facts between tables this way: kind "permutation" / "evaluation", first_row None.
+AirViolation = namedtuple("AirViolation", "table kind index first_row count")
+
+
+class AirViolationError(AssertionError):
+    """a trace breaks the AIR (BrainfuckStark.check_air); `violations` lists every failing constraint"""
+
+    def __init__(self, violations):
+        self.violations = list(violations)
+        super().__init__("the trace violates the AIR: " + "; ".join(
+            "%s %s constraint %d fails on %d row(s), first row %s" % (v.table, v.kind, v.index, v.count, v.first_row) for v in self.violations))
+
+
+_KIND_WORDS = {"boundary": "BOUNDARY", "transition": "TRNASITION", "terminal": "TERMINAL"}
+
+
+def first_failure_message(violations):
+    """the reference's message for the first failure in its loop order (kind, constraint index, row: table.py:48-110), or None.
+    `violations`: AirViolation entries of one table in any order."""
+    order = {"boundary": 0, "transition": 1, "terminal": 2}
+    failing = sorted((v for v in violations if v.count), key=lambda v: (order[v.kind], v.index))
+    if not failing:
+        return None
+    v = failing[0]
+    if v.kind == "boundary":
+        return "BOUNDARY constraint %d not satisfied in row %d" % (v.index, v.first_row)
+    return "%s constraint %d not satisfied in row %d" % (_KIND_WORDS[v.kind], v.index, v.first_row)
 
 
 class _PaddedMatrix:
@@ -796,6 +828,92 @@ class Table:
 
     def terminal_constraints_ext(self, challenges, terminals):
         return self._constraints_ext("terminal", challenges, terminals)
+
+    # ---- the base AIR as the reference presents it (processor_table.py:123-201, instruction_table.py:27-56, memory_table.py:46-112)
+    def _constraints_base(self, kind):
+        from .multivariate import MPolynomial
+        nvars = 2 * self.base_width if kind == "transition" else self.base_width
+        zeros, memo, out = [air.X0] * 11, {}, []
+        for e in dict(self.air.base())[kind]:
+            expansion = air.expand(e, nvars, zeros, zeros[:5], [], memo)
+            out.append(MPolynomial({air.unpack_exponents(k, nvars): BaseFieldElement(v[0], self.field) for k, v in expansion.items()}))
+        return out
+
+    def base_boundary_constraints(self):
+        return self._constraints_base("boundary")
+
+    def base_transition_constraints(self):
+        return self._constraints_base("transition")
+
+    # ---- the AIR checked on the trace rows (table.py:48-110) by bfs_air_check
+    def air_violations(self, challenges=None, terminals=None):
+        """failing constraints as AirViolation entries, in the order kind, constraint index.  Without challenges: the base AIR on
+        `matrix` as it stands (padded or not, len(matrix) rows).  With challenges (and terminals): the full AIR on the padded, extended
+        table (`height` rows), its extension columns from extend() (ext_columns) or extend_device() (checked in place in HBM)."""
+        lib, stream = _lib.load(), current_stream()
+        extended = challenges is not None
+        kinds = self.air.all() if extended else self.air.base()
+        nq = sum(len(c) for _, c in kinds)
+        if nq == 0:
+            return []
+        keep = []                       # device buffers that must live until the call has returned
+        ch = tm = pr = None
+        d_ext = None
+        if not extended:
+            arr = np.ascontiguousarray(self.base_array())
+            rows = arr.shape[1]
+            d_base = None
+            if rows:
+                keep.append(DeviceBuffer.from_numpy(arr.reshape(-1)))
+                d_base = keep[-1].ptr
+        else:
+            assert terminals is not None, "the full AIR needs the terminals"
+
+            def triple(v):
+                return tuple(v.limbs()) if hasattr(v, "limbs") else tuple(int(x) for x in v)
+            challenges = [triple(c) for c in challenges]
+            ch = (_u64 * 33)(*[v for c in challenges for v in c])
+            tm = (_u64 * 15)(*[v for t in terminals for v in triple(t)])
+            params = self.air_params(challenges)
+            pr = (_u64 * 3)(*params[0]) if params else None
+            rows = self.height
+            xw = self.full_width - self.base_width
+            if rows and self._ext_device is not None:            # after extend_device(): both sets of columns are in HBM already
+                assert self._base_device is not None and self._base_device.count >= self.base_width * rows
+                d_base, d_ext = self._base_device.ptr, self._ext_device.ptr
+            elif rows:
+                assert self.ext_columns is not None, "the full AIR is checked after extend() or extend_device()"
+                arr = np.ascontiguousarray(self.base_array())
+                assert arr.shape[1] == rows, "the full AIR is checked on the padded table"
+                cols = np.empty((3 * xw, rows), dtype=np.uint64)
+                np.concatenate(self.ext_columns, axis=0, out=cols)
+                keep += [DeviceBuffer.from_numpy(arr.reshape(-1)), DeviceBuffer.from_numpy(cols.reshape(-1))]
+                d_base, d_ext = keep[0].ptr, keep[1].ptr
+            else:
+                d_base = None
+        out = (_lib.AirViolation * nq)()
+        _lib.check(lib.bfs_air_check(self.table_index, 1 if extended else 0, d_base, d_ext, rows, rows, ch, tm, pr, out, stream))
+        result, q = [], 0
+        for kind, cons in kinds:
+            for i in range(len(cons)):
+                if out[q].count:
+                    result.append(AirViolation(self.air.name, kind, i, int(out[q].first_row), int(out[q].count)))
+                q += 1
+        return result
+
+    def test(self):
+        """Table.test (table.py:48-70): the base AIR on `matrix`; AssertionError at the first failure in the reference's order"""
+        message = first_failure_message(self.air_violations())
+        if message is not None:
+            raise AssertionError(message)
+
+    def xtest(self, challenges, terminals):
+        """Table.xtest (table.py:72-110): the full AIR on the padded, extended table; a table of length 0 is skipped"""
+        if self.length == 0:
+            return
+        message = first_failure_message(self.air_violations(challenges, terminals))
+        if message is not None:
+            raise AssertionError(message)
 
     # ---- host-side evaluation at one point (the verifier's use, table.py:283-311)
     def evaluate_all_constraints(self, point, next_point, challenges, terminals):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generates stark_brainfuck_amd/csrc/air_generated.hpp from the constraint graphs in stark_brainfuck_amd/air.py:
 one straight-line device function per table that evaluates every boundary / transition / terminal constraint at
-one point of the FRI domain ("needs the constraint polynomials hard-coded").
+one point of the FRI domain ("needs the constraint polynomials hard-coded").  Also generates
+csrc/air_base_generated.hpp: the same for the BASE AIR (TableAir.base(), what Table.test() checks on a base trace).
 
 Base columns stay single 64-bit residues until they meet an extension value (challenge, terminal, extension
 column); common subexpressions (deselectors, instruction zerofiers, differences of neighbouring rows) are shared.
@@ -20,6 +21,7 @@ air = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(air)
 
 OUT = os.path.join(ROOT, "stark_brainfuck_amd", "csrc", "air_generated.hpp")
+OUT_BASE = os.path.join(ROOT, "stark_brainfuck_amd", "csrc", "air_base_generated.hpp")
 
 
 class Gen:
@@ -115,6 +117,54 @@ def generic_degrees(ta):
     return out
 
 
+def write_if_changed(path, text):
+    if os.path.exists(path) and open(path).read() == text:
+        print("unchanged", path)          # keep the file's time stamp: the library build compares it with the .so
+    else:
+        with open(path, "w") as f:
+            f.write(text)
+        print("wrote", path)
+
+
+def main_base():
+    """air_base_generated.hpp: per table air_<table>_base(bc, bn, sink), base constraints only (boundary, then transition)"""
+    out = ["// air_base_generated.hpp -- GENERATED by tools/gen_air.py from stark_brainfuck_amd/air.py, do not edit.",
+           "// The BASE constraint polynomials of the five tables (TableAir.base_boundary / base_transition: the reference's",
+           "// base_boundary_constraints / base_transition_constraints) evaluated at one point (current row, next row) of a base trace.",
+           "// Values are handed to the sink as they are computed (`put_base<index>(value)`, boundary first, then transition).",
+           "#pragma once", '#include "gl.hpp"', "", "namespace bfs {", "namespace airgen {", "",
+           "struct BaseArraySink {", "    u64* out;", "    template <int I> BFS_HD void put_base(u64 v) { out[I] = v; }", "};", ""]
+    for ta in air.TABLE_AIRS:
+        g = Gen(ta.base_width)
+        body, n = [], 0
+        counts = []
+        for kind, cons in ta.base():
+            counts.append(len(cons))
+            for e in cons:
+                name, is_ext = g.emit(e)
+                assert not is_ext, "a base constraint reads an extension operand"
+                body.extend(g.lines)
+                g.lines = []
+                body.append("    sink.template put_base<%d>(%s);" % (n, name))
+                n += 1
+        up = ta.name.upper()
+        out.append("// %s table: %d base boundary, %d base transition constraints; %d operations" % (ta.name, counts[0], counts[1], g.n_base_ops))
+        out.append("constexpr int %s_BASE_NUM_BOUNDARY = %d, %s_BASE_NUM_TRANSITION = %d;" % (up, counts[0], up, counts[1]))
+        out.append("template <class Sink, class BN = const u64*>")
+        out.append("BFS_HD void air_%s_base(const u64* bc, BN bn, Sink& sink) {" % ta.name)
+        if not body:
+            out.append("    (void)bc; (void)bn; (void)sink;")
+        out.extend(body)
+        out.append("}")
+        out.append("BFS_HD void air_%s_base_values(const u64* bc, const u64* bn, u64* out) {" % ta.name)
+        out.append("    BaseArraySink sink{out};")
+        out.append("    air_%s_base(bc, bn, sink);" % ta.name)
+        out.append("}")
+        out.append("")
+    out += ["}  // namespace airgen", "}  // namespace bfs", ""]
+    write_if_changed(OUT_BASE, "\n".join(out))
+
+
 def main():
     out = ["// air_generated.hpp -- GENERATED by tools/gen_air.py from stark_brainfuck_amd/air.py, do not edit.",
            "// Constraint polynomials of the five tables evaluated at one point (current row, next row); replaces the symbolic",
@@ -165,16 +215,11 @@ def main():
         out.append("}")
         out.append("")
     out += ["}  // namespace airgen", "}  // namespace bfs", ""]
-    text = "\n".join(out)
-    if os.path.exists(OUT) and open(OUT).read() == text:
-        print("unchanged", OUT)          # keep the file's time stamp: the library build compares it with the .so
-    else:
-        with open(OUT, "w") as f:
-            f.write(text)
-        print("wrote", OUT)
+    write_if_changed(OUT, "\n".join(out))
     for c in counts:
         print("  %-12s boundary %d transition %d terminal %d | base ops %d, extension ops %d" % c)
 
 
 if __name__ == "__main__":
     main()
+    main_base()

@@ -286,7 +286,8 @@ int bfs_stark_push_openings(void* ps, const bfs_gather_request* base_row, uint32
  *   bfs_merkle_build_xfe   Merkle(codeword) over ExtensionFieldElement leaves   merkle.py:8-41 (leaf = blake2b(pickle.dumps(e)))
  *   bfs_merkle_build_bfe   same over BaseFieldElement leaves (stand-alone BaseField instance)
  *   bfs_merkle_build_bytes same over caller-pickled leaves: message i = lengths[i] bytes at d_data + 8*word_offsets[i]
- *                          (arbitrary picklable leaves, merkle.py:30; salted leaves, salted_merkle.py:32-35)
+ *                          (arbitrary picklable leaves, merkle.py:30; salted leaves, salted_merkle.py:32-35); a message occupies
+ *                          whole words, what its last word holds beyond lengths[i] bytes is not hashed
  *   bfs_merkle_open        Merkle.open(index): `depth` sibling digests, leaf level first      merkle.py:46-52 (synchronous)
  */
 int bfs_merkle_build_xfe(const uint64_t* d_limbs, uint64_t limb_stride, uint64_t n, uint8_t* d_nodes, void* stream);

@@ -90,7 +90,7 @@ __global__ void blake2b_batch_kernel(const u64* data, const u64* offsets, const 
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u64 h[8];
-    blake2b_staged(data + offsets[i], 1, lengths[i], h);
+    blake2b_staged<true>(data + offsets[i], 1, lengths[i], h);
     u64* out = digests + i * 8;
 #pragma unroll
     for (int j = 0; j < 8; ++j) out[j] = h[j];

@@ -7,17 +7,22 @@
 
 namespace bfs {
 
-// BLAKE2b of a message staged as word-major 64-bit words (word w at base[w*stride]); `total` bytes
+// BLAKE2b of a message staged as word-major 64-bit words (word w at base[w*stride]); `total` bytes.  Whole words are read.
+// MASK_TAIL = false: the bytes of the last word beyond the message are zero (a LeafWriter of this library staged it).
+// MASK_TAIL = true: they are anything (a caller's buffer, bfs_merkle_build_bytes) and are masked off before they reach the hash.
+template <bool MASK_TAIL = false>
 BFS_HD void blake2b_staged(const u64* base, u32 stride, u32 total, u64 h[8]) {
     blake2b_init(h);
     const u32 nwords = (total + 7) / 8;
     const u32 nblk = total ? (total + 127) / 128 : 1;
+    const u64 tail_mask = (total & 7) ? (~0ull >> (64 - 8 * (total & 7))) : ~0ull;
     for (u32 b = 0; b < nblk; ++b) {
         u64 m[16];
         BFS_UNROLL
         for (int j = 0; j < 16; ++j) {
             u32 w = b * 16 + (u32)j;
             m[j] = w < nwords ? base[(size_t)w * stride] : 0;
+            if (MASK_TAIL && w + 1 == nwords) m[j] &= tail_mask;
         }
         const bool last = (b + 1 == nblk);
         blake2b_compress(h, m, last ? (u64)total : (u64)(b + 1) * 128, last);

@@ -27,6 +27,9 @@ extern "C" int emu_bfe_leaf_pickle(u64 v, unsigned char* out /* >= 128 */) {
 
 extern "C" void emu_blake2b(const unsigned char* data, size_t len, unsigned char out[64]) { blake2b_host(data, len, out); }
 
+// the body of blake2b_batch_kernel: a message in a caller's buffer of whole words
+extern "C" void emu_blake2b_bytes(const u64* data, unsigned total, u64 out[8]) { blake2b_staged<true>(data, 1, total, out); }
+
 extern "C" void emu_shake256(const unsigned char* data, size_t len, unsigned char* out, size_t outlen) { shake256(data, len, out, outlen); }
 
 // full tree over an SoA extension codeword, emulating leaf kernel (64-lane word-major staging) + parent levels

@@ -301,6 +301,19 @@ def test_merkle_bodies_match_reference_trees(emu, oracle):
             assert got[i] == t["nodes"][i], (n, i)
 
 
+def test_batch_hash_of_caller_bytes_ignores_what_follows_the_message(emu):
+    """blake2b_batch_kernel's body (bfs_merkle_build_bytes) reads a caller's buffer in whole words: the bytes of the last word beyond
+    the message must not reach the hash.  Every length 0 ... 400 in a buffer of random bytes, against hashlib."""
+    rng = np.random.default_rng(0xB17E5)
+    words = rng.integers(0, 1 << 63, 64, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    data = words.tobytes()
+    emu.emu_blake2b_bytes.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+    for total in range(401):
+        out = np.zeros(8, dtype=np.uint64)
+        emu.emu_blake2b_bytes(words.ctypes.data, total, out.ctypes.data)
+        assert out.tobytes() == hashlib.blake2b(data[:total]).digest(), total
+
+
 # ------------------------------------------------------------------ zipped-row leaf kernel: the per-lane state machine
 def _pickle_int(v):
     """CPython's save_long for a non-negative int below 2^64 (what pickle protocol 4 writes for the reference's element values)"""

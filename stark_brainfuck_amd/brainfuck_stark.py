@@ -209,13 +209,11 @@ class BrainfuckStark:
         {index: handle of the combination leaf} for Fri.prove, or None when this route is not available."""
         if self._cooperation is not None or type(base_tree) is not ZippedSaltedMerkle or type(extension_tree) is not ZippedSaltedMerkle:
             return None
-        if not hasattr(proof_stream, "_adopt_lazy") or combination_tree._nodes_host is not None or combination_tree.num_leafs != n:
+        if combination_tree._nodes_host is not None or combination_tree.num_leafs != n:
             return None
-        transcript = proof_stream._native()
-        if getattr(proof_stream, "_cached", None) is not transcript or (transcript.xfield is not None and transcript.xfield is not xf):
+        transcript = BrainfuckStark._native_transcript(proof_stream, xf)
+        if transcript is None:
             return None
-        if transcript.xfield is None:
-            transcript.xfield = xf
 
         def requests(reqs):
             arr = (_lib.GatherRequest * len(reqs))()
@@ -240,6 +238,22 @@ class BrainfuckStark:
                                                out, stream))
         proof_stream._adopt_lazy(transcript, before, transcript.num_objects(), xf)
         return {index: int(handle) for index, handle in zip(indices, out)}
+
+    @staticmethod
+    def _native_transcript(proof_stream, xf, refuse_loaded=False):
+        """the native transcript of `proof_stream` if native code may append objects of extension field `xf` to it (the field is
+        claimed on first use), else None: a foreign proof stream, a transcript that is not the stream's cached one or belongs to
+        another field -- and, for a caller that has to map Python objects to handles, one that was read natively from bytes"""
+        if not hasattr(proof_stream, "_adopt_lazy"):
+            return None
+        transcript = proof_stream._native()
+        if getattr(proof_stream, "_cached", None) is not transcript or (transcript.xfield is not None and transcript.xfield is not xf):
+            return None
+        if refuse_loaded and transcript.loaded:
+            return None
+        if transcript.xfield is None:
+            transcript.xfield = xf
+        return transcript
 
     @staticmethod
     def _release(*holders):
@@ -333,15 +347,11 @@ class BrainfuckStark:
             return None
         if proof_stream is None:
             proof_stream = ProofStream()
-        if not hasattr(proof_stream, "_adopt_lazy"):
-            return None
         lib, stream = _lib.load(), current_stream()
         xf, n = self.xfield, self.fri.domain.length
-        transcript = proof_stream._native()
-        if getattr(proof_stream, "_cached", None) is not transcript or (transcript.xfield is not None and transcript.xfield is not xf) or transcript.loaded:
+        transcript = BrainfuckStark._native_transcript(proof_stream, xf, refuse_loaded=True)
+        if transcript is None:
             return None
-        if transcript.xfield is None:
-            transcript.xfield = xf
         import time
         t_begin = time.perf_counter()
         for table, matrix in zip(self.tables, ordered):

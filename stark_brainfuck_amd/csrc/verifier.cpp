@@ -17,6 +17,7 @@
 #include "blake2b.hpp"
 #include "refpickle.hpp"
 #include "runtime.hpp"
+#include "table_shapes.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -247,10 +248,6 @@ bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0) 
     }
     return true;
 }
-
-constexpr int NT = 5;
-constexpr u32 BASE_W[NT] = {7, 3, 4, 1, 1};
-constexpr u32 EXT_W[NT] = {4, 2, 1, 1, 1};
 
 int verify_finish(Transcript* t, const bfs_stark_verify_params& P, const u64* shifts, u32 num_terms) {
     Reader rd{t};

@@ -33,6 +33,9 @@ _ARRAY_GENERATION = itertools.count(1)      # keys of Table's per-matrix caches:
 
 P = air.P
 _u64 = ctypes.c_uint64
+# lde_tables: from this domain size on, one coset transform per run of tables with the same coefficient count instead of one for all
+# (csrc/prover.cpp states the same rule for the native stage driver, with a constant of the same name: change both together)
+LDE_GROUP_MIN_LOG_N = 20
 
 
 def _val(x):
@@ -258,23 +261,18 @@ def lde_tables(tables, domain, extension=False):
         raw = (_u64 * total)()
         _lib.check(lib.bfs_poly_support(coeffs.ptr, stride, n_in, total, raw, stream))
         masks = [int(v) for v in raw]
-    if log_n < 20:
+    if log_n < LDE_GROUP_MIN_LOG_N:
         raw_ntt(coeffs.ptr, n_in, stride, out.ptr, n, log_n, total, omega, offset, 1, stream)
     else:
         # large domains: one call per run of tables with the same coefficient count (csrc/prover.cpp: lde_all_tables does the same on the
         # native path) -- a transform's cost depends on its zero padding (ntt_plan.hpp: 2^16 + 1 coefficients on 2^22 points take the
         # two-pass expansion plan, 2^17 + 1 the plain three passes), and a table must not pay for its neighbour's height
-        k, first = 0, 0
-        while k < len(tables):
-            count = tables[k].height + (1 if tables[k].num_randomizers else 0) if tables[k].height else 0
-            u, cols = k, 0
-            while u < len(tables) and (tables[u].height + (1 if tables[u].num_randomizers else 0) if tables[u].height else 0) == count:
-                cols += widths[u]
-                u += 1
+        first = 0
+        for count, run in itertools.groupby(range(len(tables)), key=lambda k: tables[k].transform_coefficients()):
+            cols = sum(widths[k] for k in run)
             if cols:
                 raw_ntt(coeffs.ptr + 8 * first * stride, min(max(count, 1), n_in), stride, out.ptr + 8 * first * n, n, log_n, cols, omega, offset, 1, stream)
             first += cols
-            k = u
     from .device import DeviceView
     at = 0
     for t, w, d_in in zip(tables, widths, inputs):
@@ -440,6 +438,10 @@ class Table:
 
     def interpolant_degree(self):
         return self.get_interpolation_domain_length() - 1
+
+    def transform_coefficients(self):
+        """coefficients of this table's interpolant as the coset transform sees them: an empty table has none (its columns are zero)"""
+        return self.get_interpolation_domain_length() if self.height else 0
 
     # ---- rows
     def base_array(self):

@@ -109,6 +109,54 @@ def test_production_path_writes_the_reference_proof(name, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_a_refused_commit_leaves_the_threads_session_usable(monkeypatch):
+    """bfs_stark_commit refuses a call from its arguments alone (BFS_ERR_BAD_ARG = 6: a height that does not match the matrix, then no
+    salts for the extension commitment) on this thread's own session; the next proof on the same session is the reference's"""
+    from stark_brainfuck_amd import _lib, brainfuck_stark, salted_merkle, table
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    from stark_brainfuck_amd.vm import VirtualMachine
+    name = "loop"
+    g = json.load(open(os.path.join(GOLDEN, "stark_%s.json" % name)))
+    program = VirtualMachine.compile(g["program"])
+    running_time, input_symbols, output_symbols = VirtualMachine.run(program, input_data=list(g["input"]))
+    matrices = VirtualMachine.simulate(program, input_data=list(input_symbols))
+
+    def prove():
+        stream = Stream(name.encode())
+        for mod in (brainfuck_stark, salted_merkle, table):
+            monkeypatch.setattr(mod, "urandom", stream)
+        stark = BrainfuckStark(running_time, len(matrices[1]), program, input_symbols, output_symbols)
+        return stark.prove(program, *matrices)
+
+    lib = _lib.load()
+    commit = lib.bfs_stark_commit
+    session = BrainfuckStark._native_session()
+    seen = []
+
+    def wrong_height(params, rnd):
+        params.heights[1] *= 2
+
+    def no_extension_salts(params, rnd):
+        rnd.ext_salt_seed = rnd.ext_salts = None
+
+    def untouched(params, rnd):
+        pass
+
+    def forward(*args):
+        seen.append(args[0])
+        spoil(args[2]._obj, args[4]._obj)              # (the structures behind ctypes.byref)
+        return commit(*args)
+    monkeypatch.setattr(lib, "bfs_stark_commit", forward)
+    for spoil, message in ((wrong_height, "its constructor said height"), (no_extension_salts, "no salts for the extension commitment")):
+        with pytest.raises(RuntimeError, match="error 6: bfs_stark_commit: .*%s" % message):
+            prove()
+    spoil = untouched
+    proof = prove()
+    assert seen == [session] * 3, "the three calls were not all made on this thread's session"
+    assert len(proof) == g["proof_len"] and hashlib.sha256(proof).hexdigest() == g["proof_sha256"]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["loop", "two_io"])
 def test_combination_by_row_windows_writes_the_reference_proof(name, monkeypatch):
     """bfs_zerofier_inverses_rows / bfs_air_combine_rows / bfs_difference_combine_rows (a cooperative proof's share of the pointwise

@@ -371,14 +371,28 @@ int bfs_trace_pad(const bfs_trace_pad_table* tables, uint32_t count, void* strea
  * bfs_fri_query  : sample_indices + Fri.query / Fri.query_last (fri.py:62-86, 141-176, 186-197); writes the
  *                  top-level indices (Fri.prove's return value) to h_top_level_indices[num_colinearity_tests].
  * bfs_fri_prove  : Fri.prove(codeword, proof_stream) (fri.py:178-199) = commit + query with a temporary session.
+ *
+ * Folding factor.  A session folds its codeword by a = 2^log2_folding per round, log2_folding in {1, 2, 3}; 1 is the default and the
+ * reference's protocol.  One round of folding by 4 (8) with challenge alpha is two (three) split-and-fold steps with alpha, alpha^2
+ * (, alpha^4), offset and omega squared between them; the codewords in between are neither stored nor committed to.  With
+ * L = log2(n / expansion_factor) there are F = floor((L - 1) / log2_folding) folds (F >= 1 is required when a > 2) and F + 1
+ * codewords; each opening is the a elements in[c + j * len / a], j < a, the element c of the next codeword, and their paths.
+ * bfs_xfe_fold_multi          : bfs_xfe_fold applied log2_folding times (challenges alpha^(2^j), offset and omega squared each time)
+ *                               in one pass: out has n / a elements.  log_n >= log2_folding.
+ * bfs_fri_session_set_folding : before bfs_fri_commit; BFS_ERR_BAD_ARG for a value outside {1, 2, 3} or a session that has committed.
+ * bfs_fri_prove_folded        : bfs_fri_prove with a folding factor.
+ *
  * The codeword is limb-major in HBM (limb k at d_codeword + k*limb_stride); `ps` is a bfs_ps_new() stream, possibly
  * already holding earlier objects.  These calls synchronise `stream` (each round needs the root on the host).
  * Errors: BFS_ERR_NOT_ROOT ("omega does not have the right order", fri.py:104-105), BFS_ERR_TOO_MANY_INDICES (fri.py:69-70).
  */
 int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n,
                  const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream);
+int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, uint32_t log2_folding,
+                       const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream);
 void* bfs_fri_session_new(void);
 void bfs_fri_session_free(void* session);
+int bfs_fri_session_set_folding(void* session, uint32_t log2_folding);
 int bfs_fri_commit(void* session, void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
                    uint64_t omega, uint32_t expansion_factor, void* stream);
 int bfs_fri_query(void* session, void* ps, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream);
@@ -392,6 +406,9 @@ int bfs_fri_session_alias(void* session, void* ps, uint32_t round, uint64_t inde
 int bfs_fri_session_round0_tree(void* session, const uint8_t* d_nodes, const uint8_t h_root[64]);
 int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                   uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream);
+int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
+                         void* stream);
 /* wall-clock breakdown (ms) of the last commit/query on the calling thread: rounds, last codeword, Fiat-Shamir + sampling,
  * planning the openings, gather + sync, building transcript objects */
 void bfs_fri_last_timing(double out[6]);

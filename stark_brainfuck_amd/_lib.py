@@ -107,13 +107,16 @@ _SIGNATURES = {
     "bfs_random_fill": (ci, [ctypes.c_char_p, vp, u64, vp]),
     "bfs_xfe_sample_fill": (ci, [ctypes.c_char_p, vp, u64, u64, vp]),
     "bfs_xfe_fold": (ci, [vp, u64, vp, u64, u32, ctypes.POINTER(u64), u64, u64, vp]),
+    "bfs_xfe_fold_multi": (ci, [vp, u64, vp, u64, u32, u32, ctypes.POINTER(u64), u64, u64, vp]),
     "bfs_fri_session_new": (vp, []),
+    "bfs_fri_session_set_folding": (ci, [vp, u32]),
     "bfs_fri_session_free": (None, [vp]),
     "bfs_fri_commit": (ci, [vp, vp, vp, u64, u32, u64, u64, u32, vp]),
     "bfs_fri_query": (ci, [vp, vp, u32, ctypes.POINTER(u64), vp]),
     "bfs_fri_session_alias": (ci, [vp, vp, u32, u64, u64]),
     "bfs_fri_session_round0_tree": (ci, [vp, vp, ctypes.c_char_p]),
     "bfs_fri_prove": (ci, [vp, vp, u64, u32, u64, u64, u32, u32, ctypes.POINTER(u64), vp]),
+    "bfs_fri_prove_folded": (ci, [vp, vp, u64, u32, u64, u64, u32, u32, u32, ctypes.POINTER(u64), vp]),
     "bfs_fri_last_timing": (None, [ctypes.POINTER(ctypes.c_double)]),
     "bfs_fri_session_rounds": (u32, [vp]),
     "bfs_fri_session_round": (ci, [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(vp), vp]),

@@ -19,24 +19,32 @@ namespace bfs {
 int merkle_build_xfe_launch(const u64* d_limbs, u64 limb_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0);
 int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* lo_bits);
 
-BFS_HD u64 gl_half(u64 x) { return (x >> 1) + ((x & 1) ? 0x7FFFFFFF80000001ULL : 0); }  // x / 2 mod p
-
-// fri.py:127-128:  out[i] = 2^-1 * ((1 + alpha/x_i) * a + (1 - alpha/x_i) * b),  x_i = offset * omega^i
-//                         = (a + b)/2 + alpha * (2^-1 * offset^-1 * omega^-i) * (a - b)
-// winv_*: two-level powers of the ROUND-0 omega^-1 (exponent i << round_shift); scal = 2^-1 * offset_r^-1
-__global__ void fri_fold_kernel(const u64* in, u64 in_stride, u64* out, u64 out_stride, u64 half, Xfe alpha, u64 scal,
-                                const u64* winv_lo, const u64* winv_hi, u32 lo_bits, u32 round_shift) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += (u64)gridDim.x * blockDim.x) {
-        Xfe a{{in[i], in[in_stride + i], in[2 * in_stride + i]}};
-        Xfe b{{in[half + i], in[in_stride + half + i], in[2 * in_stride + half + i]}};
-        u64 s = gl_mul(scal, tw_pow(winv_lo, winv_hi, lo_bits, i << round_shift));
-        Xfe beta = xfe_scale(alpha, s);
-        Xfe sum = xfe_add(a, b), diff = xfe_sub(a, b);
-        Xfe prod = xfe_mul(beta, diff);
-        out[i] = gl_add(gl_half(sum.c[0]), prod.c[0]);
-        out[out_stride + i] = gl_add(gl_half(sum.c[1]), prod.c[1]);
-        out[2 * out_stride + i] = gl_add(gl_half(sum.c[2]), prod.c[2]);
+// the fold on its own (fri.py:127-128, K times: fri_fold_point in runtime.hpp): out[i], i < f.half, from the 2^K inputs in[i + m * f.half]
+// winv_*: two-level powers of the ROUND-0 omega^-1 (exponent i << round_shift)
+// (launched with 256 threads; saying so gives the K = 3 body, which holds 8 extension elements, the registers it needs: without the
+//  bound the compiler keeps to 128 VGPRs and spills two.  K = 1 keeps the default bound and with it the code it had.)
+template <int K>
+__global__ void __launch_bounds__(K == 1 ? 1024 : 256) fri_fold_kernel(FriFoldArgs f, u64* out, u64 out_stride) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < f.half; i += (u64)gridDim.x * blockDim.x) {
+        const Xfe r = fri_fold_point<K>(f, i);
+        out[i] = r.c[0];
+        out[out_stride + i] = r.c[1];
+        out[2 * out_stride + i] = r.c[2];
     }
+}
+
+constexpr u32 FRI_FOLD_GRID_MAX = 4096;       // workgroups of 256; longer codewords go round the grid-stride loop
+static int fri_fold_launch(const FriFoldArgs& f, u64* out, u64 out_stride, hipStream_t stream) {
+    u32 grid = (u32)((f.half + 255) / 256);
+    if (grid > FRI_FOLD_GRID_MAX) grid = FRI_FOLD_GRID_MAX;
+    switch (f.log2_folding) {
+    case 1: hipLaunchKernelGGL(fri_fold_kernel<1>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
+    case 2: hipLaunchKernelGGL(fri_fold_kernel<2>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
+    case 3: hipLaunchKernelGGL(fri_fold_kernel<3>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
+    default: set_error("internal: fold by 2^%u", f.log2_folding); return BFS_ERR_BAD_ARG;
+    }
+    BFS_HIP(hipGetLastError());
+    return BFS_OK;
 }
 
 // one request = `nwords` 64-bit words at base, base + stride, ...; requests and results live in pinned host memory that the
@@ -85,6 +93,7 @@ struct FriSession {
     bool use_workspace = false;
     RootMailbox mailbox;
     u32 log_n = 0;
+    u32 log2_folding = 1;   // every round folds its codeword by 2^log2_folding (bfs_fri_session_set_folding)
     // (round, index) -> the element / tree-node object.  One object per key: the reference pushes the same Python object
     // again when an index recurs, and pickle memoises by identity.
     struct Key {
@@ -129,17 +138,19 @@ struct FriSession {
     ~FriSession() { if (block) (void)device_release(block, block_stream); }
 };
 
-static u32 fri_num_rounds(u64 length, u32 expansion) {  // fri.py:54-60
+static u32 fri_num_rounds(u64 length, u32 expansion, u32 k = 1) {  // fri.py:54-60; folding by 2^k: floor((that - 1) / k) folds, one codeword more
     u32 r = 0;
     while (length > expansion) { length /= 2; ++r; }
-    return r;
+    return r == 0 ? 0 : (r - 1) / k + 1;
 }
 
 int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u32 log_n, u64 offset, u64 omega,
                u32 expansion, hipStream_t stream) {
     const double t_begin = now_ms();
     const u64 N = 1ull << log_n;
-    const u32 R = fri_num_rounds(N, expansion);
+    const u32 k = S.log2_folding;
+    const u32 R = fri_num_rounds(N, expansion, k);
+    if (k > 1 && R < 2) { set_error("cannot fold by %u with less than one fold", 1u << k); return BFS_ERR_BAD_ARG; }
     if (R < 1) { set_error("cannot do FRI with less than one round"); return BFS_ERR_BAD_ARG; }
     if (gl_pow(omega, N) != 1 || (log_n && gl_pow(omega, N / 2) == 1)) {
         set_error("error in commit: omega does not have the right order!");
@@ -149,7 +160,7 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     S.rounds.assign(R, FriRound());
     // one allocation: nodes of every round + codewords of rounds >= 1
     size_t words = 0;
-    for (u32 r = 0; r < R; ++r) words += (size_t)16 * (N >> r) + (r ? (size_t)3 * (N >> r) : 0);
+    for (u32 r = 0; r < R; ++r) words += (size_t)16 * (N >> (k * r)) + (r ? (size_t)3 * (N >> (k * r)) : 0);
     u64* p = nullptr;
     if (S.use_workspace) {
         void* w = nullptr;
@@ -164,7 +175,7 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     BFS_TRY(S.mailbox.init());
     for (u32 r = 0; r < R; ++r) {
         FriRound& fr = S.rounds[r];
-        fr.length = N >> r;
+        fr.length = N >> (k * r);
         fr.nodes = p; p += 16 * fr.length;
         if (r == 0) { fr.cw = d_cw; fr.stride = stride; }
         else { fr.cw = p; fr.stride = fr.length; p += 3 * fr.length; }
@@ -172,8 +183,7 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     const u64 *winv_lo = nullptr, *winv_hi = nullptr;
     u32 lo_bits = 0;
     BFS_TRY(ntt_power_tables(gl_inv(omega), log_n, &winv_lo, &winv_hi, &lo_bits));
-    const u64 half_inv = gl_inv(2);
-    u64 g = offset;
+    u64 g = offset, w = omega;                     // offset and generator of round r's domain
     constexpr u64 FRI_FOLD_IN_LEAVES_MIN = 16384;     // = FRI_FUSED_MAX: every round >= 1 folds inside its leaf kernel (must exceed QUAD_LEAVES_MAX)
     FriFoldArgs pending{};                         // the fold that produces round r's codeword, when round r runs fused
     pending.in = nullptr;
@@ -272,18 +282,18 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
         if (!speculating && !have_seed) ps.fiat_shamir(ps.objects.size(), seed, 32);   // fri.py:120
         Xfe alpha = rp::sample_xfe(seed, 32);
         FriRound& nx = S.rounds[r + 1];
-        const u64 half = fr.length / 2;
+        FriFoldArgs fold{};
+        fold.in = fr.cw; fold.in_stride = fr.stride;
+        fold.winv_lo = winv_lo; fold.winv_hi = winv_hi; fold.lo_bits = lo_bits; fold.round_shift = k * r;
+        fri_fold_constants(fold, k, fr.length, alpha, g, w);
+        const u64 half = fold.half;                       // = nx.length
         if (half >= 2 && (half <= FRI_FUSED_MAX || half > FRI_FOLD_IN_LEAVES_MIN)) {
             // the next round folds while it builds its tree (fri_round_quad_kernel, or merkle_leaves_xfe_fold_kernel for large rounds)
-            pending = FriFoldArgs{fr.cw, fr.stride, half, alpha, gl_mul(half_inv, gl_inv(g)), winv_lo, winv_hi, lo_bits, r};
+            pending = fold;
         } else {
-            u32 grid = (u32)((half + 255) / 256);
-            if (grid > 4096) grid = 4096;
-            hipLaunchKernelGGL(fri_fold_kernel, dim3(grid), dim3(256), 0, stream, fr.cw, fr.stride, (u64*)nx.cw, nx.stride, half, alpha,
-                               gl_mul(half_inv, gl_inv(g)), winv_lo, winv_hi, lo_bits, r);
-            BFS_HIP(hipGetLastError());
+            BFS_TRY(fri_fold_launch(fold, (u64*)nx.cw, nx.stride, stream));
         }
-        g = gl_sqr(g);  // fri.py:130-131 (omega is squared implicitly through round_shift)
+        for (u32 j = 0; j < k; ++j) { g = gl_sqr(g); w = gl_sqr(w); }  // fri.py:130-131, once per step (the kernels square omega through round_shift)
     }
     g_fri_timing[0] = now_ms() - t_begin;   // rounds: trees, roots, challenges, folds
     // fri.py:134: the last codeword goes into the transcript as a list of element objects
@@ -344,20 +354,19 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     // plan every opening first (fri.py:191-197), then fetch everything with one gather
     std::vector<std::vector<u64>> layer_idx;  // c indices per layer
     std::vector<u64> idx = top;
-    for (u32 i = 0; i + 2 < R; ++i) {  // len(trees) - 1 = R - 2 layers use query()
-        for (auto& x : idx) x %= S.rounds[i].length / 2;
+    for (u32 i = 0; i + 1 < R; ++i) {  // len(trees) - 1 = R - 2 layers use query(), the last one query_last()
+        for (auto& x : idx) x %= S.rounds[i + 1].length;      // = len(round i) / folding factor
         layer_idx.push_back(idx);
     }
-    for (auto& x : idx) x %= S.rounds[R - 1].length;
-    layer_idx.push_back(idx);  // query_last
 
     g_fri_timing[2] = now_ms() - t_begin;   // Fiat-Shamir + index sampling
     typedef FriSession::Key Key;
-    {   // what the openings can touch at most: 3 elements and 3 authentication paths per colinearity check and layer
+    const u32 fan = 1u << S.log2_folding;         // elements of round i that one element of round i + 1 depends on
+    {   // what the openings can touch at most: fan + 1 elements and authentication paths per colinearity check and layer
         size_t depth_sum = 0;
         for (u32 r = 0; r < R; ++r) depth_sum += 64 - (size_t)__builtin_clzll(S.rounds[r].length);
-        S.elements.reserve(S.elements.vals.size() + (size_t)3 * t * R + 8);
-        S.nodes.reserve((size_t)3 * t * depth_sum / 2 + 64);
+        S.elements.reserve(S.elements.vals.size() + (size_t)(fan + 1) * t * R + 8);
+        S.nodes.reserve((size_t)(fan + 1) * t * depth_sum / 2 + 64);
     }
     std::vector<GatherReq> reqs;                 // what to fetch
     std::vector<std::pair<int, Key>> order;      // what the fetched words are: (0 = element | 1 = tree node, key)
@@ -386,11 +395,12 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     for (u32 i = 0; i < (u32)layer_idx.size(); ++i) {
         const bool lastq = (i + 1 == layer_idx.size());
         const u32 cur = lastq ? R - 2 : i;
-        const u64 half = S.rounds[cur].length / 2;
+        const u64 q = S.rounds[cur + 1].length;
         for (u32 s = 0; s < t; ++s) {
             u64 c = layer_idx[i][s];
-            need_element(cur, c); need_element(cur, c + half); need_element(cur + 1, c);
-            need_path(cur, c); need_path(cur, c + half);
+            for (u32 m = 0; m < fan; ++m) need_element(cur, c + m * q);
+            need_element(cur + 1, c);
+            for (u32 m = 0; m < fan; ++m) need_path(cur, c + m * q);
             if (!lastq) need_path(cur + 1, c);
         }
     }
@@ -431,15 +441,18 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     for (u32 i = 0; i < (u32)layer_idx.size(); ++i) {
         const bool lastq = (i + 1 == layer_idx.size());
         const u32 cur = lastq ? R - 2 : i;
-        const u64 half = S.rounds[cur].length / 2;
+        const u64 q = S.rounds[cur + 1].length;
         for (u32 s = 0; s < t; ++s) {
             u64 c = layer_idx[i][s];
-            ps.objects.push_back(rp::mk_tuple({S.elements[Key(cur, c)], S.elements[Key(cur, c + half)], S.elements[Key(cur + 1, c)]}));
+            std::vector<rp::Ref> items;
+            items.reserve(fan + 1);
+            for (u32 m = 0; m < fan; ++m) items.push_back(S.elements[Key(cur, c + m * q)]);
+            items.push_back(S.elements[Key(cur + 1, c)]);
+            ps.objects.push_back(rp::mk_tuple(std::move(items)));
         }
         for (u32 s = 0; s < t; ++s) {
             u64 c = layer_idx[i][s];
-            ps.objects.push_back(path_obj(cur, c));
-            ps.objects.push_back(path_obj(cur, c + half));
+            for (u32 m = 0; m < fan; ++m) ps.objects.push_back(path_obj(cur, c + m * q));
             if (!lastq) ps.objects.push_back(path_obj(cur + 1, c));
         }
     }
@@ -465,10 +478,25 @@ int bfs_fri_query(void* session, void* ps, uint32_t num_colinearity_tests, uint6
     return fri_query(*(FriSession*)session, *(rp::Transcript*)ps, num_colinearity_tests, h_top_level_indices, (hipStream_t)stream);
 }
 
+int bfs_fri_session_set_folding(void* session, uint32_t log2_folding) {
+    FriSession* S = (FriSession*)session;
+    if (log2_folding < 1 || log2_folding > 3) { set_error("bfs_fri_session_set_folding: log2_folding must be 1, 2 or 3 (got %u)", log2_folding); return BFS_ERR_BAD_ARG; }
+    if (!S->rounds.empty()) { set_error("bfs_fri_session_set_folding: the session has already committed"); return BFS_ERR_BAD_ARG; }
+    S->log2_folding = log2_folding;
+    return BFS_OK;
+}
+
 int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                   uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream) {
+    return bfs_fri_prove_folded(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, 1, num_colinearity_tests, h_top_level_indices, stream);
+}
+
+int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
+                         void* stream) {
     FriSession S;
     S.use_workspace = true;
+    BFS_TRY(bfs_fri_session_set_folding(&S, log2_folding));
     BFS_TRY(fri_commit(S, *(rp::Transcript*)ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, (hipStream_t)stream));
     return fri_query(S, *(rp::Transcript*)ps, num_colinearity_tests, h_top_level_indices, (hipStream_t)stream);
 }
@@ -667,12 +695,29 @@ int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint
     u32 lo_bits = 0;
     BFS_TRY(ntt_power_tables(gl_inv(omega), log_n, &lo, &hi, &lo_bits));
     Xfe a{{alpha[0] % GL_P, alpha[1] % GL_P, alpha[2] % GL_P}};
-    const u64 half = N / 2;
-    u32 grid = (u32)((half + 255) / 256);
-    hipLaunchKernelGGL(fri_fold_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0, (hipStream_t)stream, d_in, in_stride, d_out, out_stride, half, a,
-                       gl_mul(gl_inv(2), gl_inv(offset % GL_P)), lo, hi, lo_bits, 0u);
-    BFS_HIP(hipGetLastError());
-    return BFS_OK;
+    FriFoldArgs f{};
+    f.in = d_in; f.in_stride = in_stride;
+    f.winv_lo = lo; f.winv_hi = hi; f.lo_bits = lo_bits; f.round_shift = 0;
+    fri_fold_constants(f, 1, N, a, offset % GL_P, omega);
+    return fri_fold_launch(f, d_out, out_stride, (hipStream_t)stream);
+}
+
+int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, uint32_t log2_folding,
+                       const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream) {
+    const u64 N = 1ull << log_n;
+    if (log2_folding < 1 || log2_folding > 3) { set_error("bfs_xfe_fold_multi: log2_folding must be 1, 2 or 3 (got %u)", log2_folding); return BFS_ERR_BAD_ARG; }
+    if (log_n < log2_folding || log_n > 32) { set_error("cannot fold a codeword of length 2^%u by %u", log_n, 1u << log2_folding); return BFS_ERR_BAD_ARG; }
+    if (in_stride < N || out_stride < (N >> log2_folding)) { set_error("bfs_xfe_fold_multi: a limb stride is shorter than its codeword"); return BFS_ERR_BAD_ARG; }
+    if (gl_pow(omega, N) != 1 || gl_pow(omega, N / 2) == 1) { set_error("error in commit: omega does not have the right order!"); return BFS_ERR_NOT_ROOT; }
+    const u64 *lo = nullptr, *hi = nullptr;
+    u32 lo_bits = 0;
+    BFS_TRY(ntt_power_tables(gl_inv(omega), log_n, &lo, &hi, &lo_bits));
+    Xfe a{{alpha[0] % GL_P, alpha[1] % GL_P, alpha[2] % GL_P}};
+    FriFoldArgs f{};
+    f.in = d_in; f.in_stride = in_stride;
+    f.winv_lo = lo; f.winv_hi = hi; f.lo_bits = lo_bits; f.round_shift = 0;
+    fri_fold_constants(f, log2_folding, N, a, offset % GL_P, omega);
+    return fri_fold_launch(f, d_out, out_stride, (hipStream_t)stream);
 }
 
 }  // extern "C"

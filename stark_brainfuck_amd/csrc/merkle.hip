@@ -44,24 +44,18 @@ __global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_xfe_kernel(const u
 
 // the same for a FRI round whose codeword does not exist yet: every thread first PRODUCES its element (the split-and-fold step of the
 // previous round, fri.py:127-128), stores it for the later openings and hashes it -- one launch and one pass over the codeword less
+// (K: the fold is by 2^K, fri_fold_point in runtime.hpp)
+template <int K>
 __global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_xfe_fold_kernel(FriFoldArgs f, u64* cw, u64 cw_stride, u64 n, u64* leaf_digests, const u64* midstates) {
     __shared__ u64 stage[LEAF_STAGE_WORDS];
     const u64 i = (u64)blockIdx.x * LEAF_THREADS + threadIdx.x;
     const bool active = i < n;
     u64 c0 = 0, c1 = 0, c2 = 0;
     if (active) {
-        const Xfe a{{f.in[i], f.in[f.in_stride + i], f.in[2 * f.in_stride + i]}};
-        const Xfe b{{f.in[f.half + i], f.in[f.in_stride + f.half + i], f.in[2 * f.in_stride + f.half + i]}};
-        const u64 sc = gl_mul(f.scal, tw_pow(f.winv_lo, f.winv_hi, f.lo_bits, i << f.round_shift));
-        const Xfe beta = xfe_scale(f.alpha, sc);
-        const Xfe sum = xfe_add(a, b), diff = xfe_sub(a, b);
-        const Xfe prod = xfe_mul(beta, diff);
-        const u64 x = (sum.c[0] >> 1) + ((sum.c[0] & 1) ? 0x7FFFFFFF80000001ULL : 0);      // / 2 mod p
-        const u64 y = (sum.c[1] >> 1) + ((sum.c[1] & 1) ? 0x7FFFFFFF80000001ULL : 0);
-        const u64 z = (sum.c[2] >> 1) + ((sum.c[2] & 1) ? 0x7FFFFFFF80000001ULL : 0);
-        c0 = gl_add(x, prod.c[0]);
-        c1 = gl_add(y, prod.c[1]);
-        c2 = gl_add(z, prod.c[2]);
+        const Xfe r = fri_fold_point<K>(f, i);
+        c0 = r.c[0];
+        c1 = r.c[1];
+        c2 = r.c[2];
         cw[i] = c0;
         cw[cw_stride + i] = c1;
         cw[2 * cw_stride + i] = c2;
@@ -296,13 +290,12 @@ __global__ void __launch_bounds__(256) merkle_leaves_xfe_quad_kernel(const u64* 
 // leaf and builds the levels above them in LDS.  A codeword of <= FRI_WG_LEAVES elements is finished by a single workgroup, which
 // also drops the root into the host mailbox; larger ones leave one digest per workgroup to merkle_top_quad_kernel.
 // n must be a power of two (FRI codewords are).
-BFS_HD u64 gl_half_m(u64 x) { return (x >> 1) + ((x & 1) ? 0x7FFFFFFF80000001ULL : 0); }  // x / 2 mod p
-
 // 64 leaves = 64 quads = 4 waves per workgroup: ONE wave per SIMD, so that every compression of the chain runs at the speed of a
 // lone wave (~2 us).  With 256 leaves in a 1024-thread workgroup the leaf phase and the two widest levels had 4 and 2 waves per SIMD
 // taking turns: a 256-element round took 36 us against 11 compressions x 2.2 us.
 constexpr u32 FRI_WG_LEAVES = 64;
 
+template <int K>      // the fold that produces the codeword is by 2^K
 __global__ void __launch_bounds__(4 * FRI_WG_LEAVES) fri_round_quad_kernel(FriFoldArgs f, u64* cw, u64 cw_stride, u64 n, u64* nodes, const u64* midstates,
                                                               u64* root_out, u64 seq) {
 #if defined(__HIP_DEVICE_COMPILE__)   // DPP builtins exist only in the device pass
@@ -319,15 +312,8 @@ __global__ void __launch_bounds__(4 * FRI_WG_LEAVES) fri_round_quad_kernel(FriFo
         const u64 i = first + tid;
         u64 c0, c1, c2;
         if (f.in != nullptr) {
-            const Xfe a{{f.in[i], f.in[f.in_stride + i], f.in[2 * f.in_stride + i]}};
-            const Xfe b{{f.in[f.half + i], f.in[f.in_stride + f.half + i], f.in[2 * f.in_stride + f.half + i]}};
-            const u64 sc = gl_mul(f.scal, tw_pow(f.winv_lo, f.winv_hi, f.lo_bits, i << f.round_shift));
-            const Xfe beta = xfe_scale(f.alpha, sc);
-            const Xfe sum = xfe_add(a, b), diff = xfe_sub(a, b);
-            const Xfe prod = xfe_mul(beta, diff);
-            c0 = gl_add(gl_half_m(sum.c[0]), prod.c[0]);
-            c1 = gl_add(gl_half_m(sum.c[1]), prod.c[1]);
-            c2 = gl_add(gl_half_m(sum.c[2]), prod.c[2]);
+            const Xfe r = fri_fold_point<K>(f, i);
+            c0 = r.c[0]; c1 = r.c[1]; c2 = r.c[2];
             cw[i] = c0; cw[cw_stride + i] = c1; cw[2 * cw_stride + i] = c2;
         } else {
             c0 = cw[i]; c1 = cw[cw_stride + i]; c2 = cw[2 * cw_stride + i];
@@ -457,7 +443,13 @@ int fri_round_fused_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u6
     const u64* d_ms = nullptr;
     BFS_TRY(get_leaf_midstates(&d_ms));
     const u32 groups = (u32)(n <= FRI_WG_LEAVES ? 1 : n / FRI_WG_LEAVES);
-    hipLaunchKernelGGL(fri_round_quad_kernel, dim3(groups), dim3(4 * FRI_WG_LEAVES), 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq);
+    const dim3 grid(groups), block(4 * FRI_WG_LEAVES);
+    switch (fold.in == nullptr ? 1u : fold.log2_folding) {
+    case 1: hipLaunchKernelGGL(fri_round_quad_kernel<1>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
+    case 2: hipLaunchKernelGGL(fri_round_quad_kernel<2>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
+    case 3: hipLaunchKernelGGL(fri_round_quad_kernel<3>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
+    default: set_error("internal: fold by 2^%u", fold.log2_folding); return BFS_ERR_BAD_ARG;
+    }
     BFS_HIP(hipGetLastError());
     if (groups == 1) return BFS_OK;
     u32 depth = 0;
@@ -473,8 +465,13 @@ int merkle_build_xfe_fold_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stri
     u32 depth = 0;
     while ((1ull << depth) < n) ++depth;
     const u64 npo2 = 1ull << depth;
-    hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel, dim3((u32)((n + LEAF_THREADS - 1) / LEAF_THREADS)), dim3(LEAF_THREADS), 0, stream,
-                       fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms);
+    const dim3 grid((u32)((n + LEAF_THREADS - 1) / LEAF_THREADS)), block(LEAF_THREADS);
+    switch (fold.log2_folding) {
+    case 1: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<1>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
+    case 2: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<2>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
+    case 3: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<3>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
+    default: set_error("internal: fold by 2^%u", fold.log2_folding); return BFS_ERR_BAD_ARG;
+    }
     BFS_HIP(hipGetLastError());
     return merkle_inner_launch(d_nodes, depth, n, stream, root_out, seq);
 }

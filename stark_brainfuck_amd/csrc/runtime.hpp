@@ -60,15 +60,74 @@ int cached_table(uint64_t key_a, uint64_t key_b, uint64_t key_c, const u64* host
 bool cached_table_lookup(uint64_t key_a, uint64_t key_b, uint64_t key_c, const u64** d_out);
 
 // ---- FRI rounds on small codewords, one launch (merkle.hip: fri_round_quad_kernel) ----
+// A round folds its codeword by a = 2^k, k = log2_folding in {1, 2, 3}: k successive split-and-fold steps (fri.py:127-128) with the
+// challenges alpha, alpha^2, alpha^4, offset and omega squared between the steps.  Output c, c < half = n / a, depends on the a inputs
+// in[c + m * half]; step j pairs v[m] with v[m + h], h = 2^(k-1-j), at abscissa offset^(2^j) * omega^(2^j * (c + m * half)), and
+// omega^half is a primitive a-th root of unity zeta.  So the factor 2^-1 / x of pair m in step j is
+//     scal[off_j + m] * (omega^-c)^(2^j),   scal[off_j + m] = 2^-1 * offset^-(2^j) * zeta^-(m * 2^j),   off_j = a - 2^(k-j)
+// -- 1, 3 or 7 kernel-argument constants -- and the thread looks up omega^-c once.
 struct FriFoldArgs {
     const u64* in;             // previous round's codeword (null: this round's codeword is already at cw)
     u64 in_stride, half;       // half = length of this round's codeword
-    Xfe alpha;                 // fri.py:120
-    u64 scal;                  // 2^-1 * offset_r^-1
+    Xfe alpha[3];              // fri.py:120 and its squares: alpha^(2^j), j < k
+    u64 scal[7];               // see above; k = 1: scal[0] = 2^-1 * offset_r^-1
     const u64* winv_lo;        // two-level powers of the round-0 omega^-1
     const u64* winv_hi;
-    u32 lo_bits, round_shift;
+    u32 lo_bits, round_shift;  // omega_r = omega_0^(2^round_shift)
+    u32 log2_folding;          // k
 };
+// host side: the constants of one fold by 2^k of a codeword of length n over offset * <omega> (omega of order n)
+inline void fri_fold_constants(FriFoldArgs& f, u32 k, u64 n, const Xfe& alpha, u64 offset, u64 omega) {
+    f.log2_folding = k;
+    f.half = n >> k;
+    f.alpha[0] = alpha;
+    for (u32 j = 1; j < 3; ++j) f.alpha[j] = j < k ? xfe_mul(f.alpha[j - 1], f.alpha[j - 1]) : Xfe{{0, 0, 0}};
+    u64 gj = gl_mul(gl_inv(2), gl_inv(offset));                 // 2^-1 * offset^-(2^j)
+    u64 zj = k > 1 ? gl_pow(gl_inv(omega), f.half) : 1;          // zeta^-(2^j)
+    u32 off = 0;
+    for (u32 j = 0; j < k; ++j) {
+        const u32 h = 1u << (k - 1 - j);
+        u64 z = 1;
+        for (u32 m = 0; m < h; ++m) { f.scal[off + m] = gl_mul(gj, z); z = gl_mul(z, zj); }
+        off += h;
+        gj = gl_mul(gl_mul(gj, gj), 2);                          // (2^-1 g)^2 * 2 = 2^-1 g^2
+        zj = gl_sqr(zj);
+    }
+    for (; off < 7; ++off) f.scal[off] = 0;
+}
+
+BFS_HD u64 gl_half(u64 x) { return (x >> 1) + ((x & 1) ? 0x7FFFFFFF80000001ULL : 0); }  // x / 2 mod p
+
+// one output element of a fold by 2^K: element i of the folded codeword, from f.in[i + m * f.half], m < 2^K (limb-major, stride
+// f.in_stride).  The K steps run in registers; K = 1 is fri.py:127-128 as it stands:
+//     out[i] = 2^-1 * ((1 + alpha/x_i) * a + (1 - alpha/x_i) * b) = (a + b)/2 + alpha * (2^-1 * offset^-1 * omega^-i) * (a - b)
+template <int K>
+BFS_HD Xfe fri_fold_point(const FriFoldArgs& f, u64 i) {
+    constexpr int A = 1 << K;
+    Xfe v[A];
+    BFS_UNROLL
+    for (int m = 0; m < A; ++m) {
+        const u64 at = (u64)m * f.half + i;
+        v[m] = Xfe{{f.in[at], f.in[f.in_stride + at], f.in[2 * f.in_stride + at]}};
+    }
+    u64 w = tw_pow(f.winv_lo, f.winv_hi, f.lo_bits, i << f.round_shift);    // omega_r^-i
+    int off = 0;
+    BFS_UNROLL
+    for (int j = 0; j < K; ++j) {
+        const int h = 1 << (K - 1 - j);
+        BFS_UNROLL
+        for (int m = 0; m < h; ++m) {
+            const u64 s = gl_mul(f.scal[off + m], w);
+            const Xfe beta = xfe_scale(f.alpha[j], s);
+            const Xfe sum = xfe_add(v[m], v[m + h]), diff = xfe_sub(v[m], v[m + h]);
+            const Xfe prod = xfe_mul(beta, diff);
+            v[m] = Xfe{{gl_add(gl_half(sum.c[0]), prod.c[0]), gl_add(gl_half(sum.c[1]), prod.c[1]), gl_add(gl_half(sum.c[2]), prod.c[2])}};
+        }
+        off += h;
+        if (j + 1 < K) w = gl_sqr(w);
+    }
+    return v[0];
+}
 constexpr u64 FRI_FUSED_MAX = 16384;     // up to 256 workgroups of 64 leaves (their roots: one top kernel)
 int merkle_build_xfe_fold_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out, u64 seq);
 int fri_round_fused_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out, u64 seq);

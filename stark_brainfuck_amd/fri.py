@@ -1,12 +1,18 @@
 """FRI low-degree test, prover on the GPU -- mirror of the reference's `fri.py` (/root/reference/code/fri.py:13-319).
 
-    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield)
+    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2)
       .domain   Fri.Domain: offset, omega, length, __call__, list, evaluate, xevaluate, interpolate, xinterpolate
       .num_rounds()  .sample_indices(...)  .commit(...)  .query(...)  .query_last(...)  .prove(...)  .verify(...)
 
 `prove` / `commit` run the whole round loop natively (csrc/fri.hip): Merkle trees, folding and openings on the GPU,
 Fiat-Shamir on the host in C++.  `codeword` may be a Python list of ExtensionFieldElement (as in the reference) or an
 XArray already in HBM.  `verify` is the verifier: host-side, as in the reference.
+
+`folding_factor` a = 2^k in (2, 4, 8) is how much shorter each round's codeword is than the one before.  2 is the reference's protocol,
+byte for byte.  A round of folding by 4 (8) with challenge alpha is two (three) of the reference's split-and-fold steps with the
+challenges alpha, alpha^2 (, alpha^4), offset and omega squared between them; the codewords in between are neither kept nor committed
+to.  With L = log2(N / expansion_factor) there are F = (L - 1) // k folds and F + 1 codewords; a colinearity test opens, per layer, the
+a elements C_i[c + j * q], q = len(C_i) / a, and C_{i+1}[c] as one tuple, then their a (+ 1) authentication paths.
 """
 import ctypes
 from hashlib import blake2b
@@ -91,19 +97,27 @@ class Fri:
         def xinterpolate(self, values):
             return fast_coset_interpolate(self.offset, self.omega, values)
 
-    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield):
+    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2):
+        assert folding_factor in (2, 4, 8), "folding factor must be 2, 4 or 8"
         self.domain = Fri.Domain(offset, omega, initial_domain_length)
         self.field = xfield
         self.expansion_factor = expansion_factor
         self.num_colinearity_tests = num_colinearity_tests
+        self.folding_factor = folding_factor
+        self._log2_folding = folding_factor.bit_length() - 1
         assert self.num_rounds() >= 1, "cannot do FRI with less than one round"
+        # (folding by 2 keeps the reference's rule: one round constructs, and prove() fails for want of a second codeword)
+        assert folding_factor == 2 or self.num_rounds() >= 2, "cannot do FRI with less than one fold"
 
     def num_rounds(self):
+        """number of codewords: the reference's count of halvings h (fri.py:54-60) when folding by 2, (h - 1) // k + 1 in general"""
         length, rounds = self.domain.length, 0
         while length > self.expansion_factor:
             length //= 2
             rounds += 1
-        return rounds
+        if self._log2_folding == 1 or rounds == 0:
+            return rounds
+        return (rounds - 1) // self._log2_folding + 1
 
     @staticmethod
     def sample_index(byte_array, size):
@@ -148,6 +162,8 @@ class Fri:
         before = transcript.num_objects()
         session = lib.bfs_fri_session_new()
         try:
+            if self._log2_folding != 1:
+                _lib.check(lib.bfs_fri_session_set_folding(session, self._log2_folding))
             if round0_tree is not None and round0_tree._nodes_host is None and round0_tree.num_leafs == n:
                 _lib.check(lib.bfs_fri_session_round0_tree(session, round0_tree._nodes.ptr, round0_tree.root()))
             _lib.check(lib.bfs_fri_commit(session, transcript.handle, arr.ptr, arr.stride, n.bit_length() - 1,
@@ -198,27 +214,27 @@ class Fri:
         return codewords, trees
 
     def query(self, current_tree, next_tree, c_indices, proof_stream):
-        """fri.py:141-158"""
-        half = len(current_tree.leafs) // 2
-        a_indices, b_indices = list(c_indices), [i + half for i in c_indices]
+        """fri.py:141-158; folding by a: the a elements c + j * q of the current codeword instead of the two c, c + half"""
+        a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
+        opened = [[i + j * q for i in c_indices] for j in range(a)]          # (a = 2: a_indices, b_indices)
         for s in range(self.num_colinearity_tests):
-            proof_stream.push((current_tree.leafs[a_indices[s]], current_tree.leafs[b_indices[s]], next_tree.leafs[c_indices[s]]))
+            proof_stream.push(tuple(current_tree.leafs[opened[j][s]] for j in range(a)) + (next_tree.leafs[c_indices[s]],))
         for s in range(self.num_colinearity_tests):
-            proof_stream.push(current_tree.open(a_indices[s]))
-            proof_stream.push(current_tree.open(b_indices[s]))
+            for j in range(a):
+                proof_stream.push(current_tree.open(opened[j][s]))
             proof_stream.push(next_tree.open(c_indices[s]))
-        return a_indices + b_indices
+        return [i for column in opened for i in column]
 
     def query_last(self, current_tree, last_codeword, c_indices, proof_stream):
         """fri.py:160-176"""
-        half = len(current_tree.leafs) // 2
-        a_indices, b_indices = list(c_indices), [i + half for i in c_indices]
+        a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
+        opened = [[i + j * q for i in c_indices] for j in range(a)]
         for s in range(self.num_colinearity_tests):
-            proof_stream.push((current_tree.leafs[a_indices[s]], current_tree.leafs[b_indices[s]], last_codeword[c_indices[s]]))
+            proof_stream.push(tuple(current_tree.leafs[opened[j][s]] for j in range(a)) + (last_codeword[c_indices[s]],))
         for s in range(self.num_colinearity_tests):
-            proof_stream.push(current_tree.open(a_indices[s]))
-            proof_stream.push(current_tree.open(b_indices[s]))
-        return a_indices + b_indices
+            for j in range(a):
+                proof_stream.push(current_tree.open(opened[j][s]))
+        return [i for column in opened for i in column]
 
     def prove(self, codeword, proof_stream, known_leafs=None, round0_tree=None):
         """fri.py:178-199: commit + query in one native call; returns the top-level indices.
@@ -256,12 +272,15 @@ class Fri:
             return False
         n_last = len(last_codeword)
         degree = (n_last // self.expansion_factor) - 1
-        last_omega_v = pow(omega_v, 1 << (rounds - 1), P)
+        k, a = self._log2_folding, self.folding_factor
+        last_omega_v = pow(omega_v, 1 << (k * (rounds - 1)), P)
         assert pow(last_omega_v, n_last, P) == 1, "omega does not have right order"
         top = _interpolant_degree(last_omega_v, [tuple(e.limbs()) for e in last_codeword])
         if top > degree:
             return False
-        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), N >> 1, N >> (rounds - 1), t)
+        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), N >> k, N >> (k * (rounds - 1)), t)
+        if a != 2:
+            return self._verify_folded_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
         for r in range(rounds - 1):
             half = N >> (r + 1)
             c_indices = [i % half for i in top_level_indices]
@@ -298,6 +317,55 @@ class Fri:
                         print("leafs in last round do not correspond to last codeword")
                         return False
             omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
+        return True
+
+    def _verify_folded_layers(self, proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v):
+        """the layers of `verify` when a round folds by a = 4 or 8: per test the a opened values C_r[c + j * q] are folded pairwise, k
+        times (fri.py:127-128 on integer residues, with alpha^(2^step), offset and omega squared between the steps), and the result must
+        be the opened C_{r+1}[c]; then a paths into tree r and -- except on the last layer, whose next codeword is in the proof -- one
+        into tree r + 1."""
+        from .air import P, xadd, xmul, xscale, xsub
+        rounds, t, N, k, a = self.num_rounds(), self.num_colinearity_tests, self.domain.length, self._log2_folding, self.folding_factor
+        half_inv = pow(2, P - 2, P)
+        for r in range(rounds - 1):
+            q = N >> (k * (r + 1))
+            c_indices = [i % q for i in top_level_indices]
+            opened, nexts = [], []
+            for s in range(t):
+                values = proof_stream.pull()
+                if not isinstance(values, tuple) or len(values) != a + 1:
+                    print("colinearity check failure")
+                    return False
+                opened.append(values[:a]); nexts.append(values[a])
+                v = [tuple(e.limbs()) for e in values[:a]]
+                alpha, g, w = tuple(alphas[r].limbs()), offset_v, omega_v
+                for step in range(k):
+                    h = len(v) // 2
+                    folded = []
+                    for m in range(h):
+                        x_inv = pow(g * pow(w, c_indices[s] + m * q, P) % P, P - 2, P)
+                        beta = xscale(alpha, half_inv * x_inv % P)
+                        folded.append(xadd(xscale(xadd(v[m], v[m + h]), half_inv), xmul(beta, xsub(v[m], v[m + h]))))
+                    v, alpha, g, w = folded, xmul(alpha, alpha), g * g % P, w * w % P
+                if v[0] != tuple(values[a].limbs()):
+                    print("colinearity check failure")
+                    return False
+            for i in range(t):
+                for j in range(a):
+                    if not Merkle.verify(roots[r], c_indices[i] + j * q, proof_stream.pull(), opened[i][j]):
+                        print("merkle authentication path verification fails for opened value %d" % j)
+                        return False
+                if r + 1 != rounds - 1:
+                    if not Merkle.verify(roots[r + 1], c_indices[i], proof_stream.pull(), nexts[i]):
+                        print("merkle authentication path verification fails for cc")
+                        return False
+            if r + 1 == rounds - 1:
+                for i in range(t):
+                    if nexts[i] != last_codeword[c_indices[i]]:
+                        print("leafs in last round do not correspond to last codeword")
+                        return False
+            for _ in range(k):
+                omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
         return True
 
 

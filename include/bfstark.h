@@ -296,6 +296,19 @@ int bfs_merkle_build_bytes(const uint8_t* d_data, const uint64_t* d_word_offsets
                            uint8_t* d_nodes, void* stream);
 int bfs_merkle_open(const uint8_t* d_nodes, uint32_t depth, uint64_t index, uint8_t* h_path, void* stream);
 /*
+ * bfs_merkle_build_xfe_cosets   Merkle(list of tuples) with one leaf per folding coset of an extension codeword of n = a q elements,
+ *     a = 2^log2_coset in (2, 4, 8), n a power of two: leaf c, c < q, = blake2b(pickle.dumps((C[c], C[c + q], .., C[c + (a - 1) q]))),
+ *     the a elements one fold by a consumes (merkle.py:29-32 on the tuple of distinct element objects, unsalted).  q leaves in
+ *     bfs_merkle_build_xfe's node layout: d_nodes holds 2 q digests.  The pickles are streamed into BLAKE2b by csrc/coset.hip; a tuple
+ *     with an element that stores fewer than three coefficients sends the tree through bfs_merkle_build_rows_range's encoder instead.
+ *     Synchronises the stream.  What Fri(..., coset_leaves=True) commits to per round; see bfs_fri_session_set_coset_leaves.
+ */
+int bfs_merkle_build_xfe_cosets(const uint64_t* d_limbs, uint64_t limb_stride, uint64_t n, uint32_t log2_coset, uint8_t* d_nodes, void* stream);
+/* Diagnostic, not part of the protocol: a caller reads it to see whether its codewords take the slow path.  How many coset trees of
+ * this process (bfs_merkle_build_xfe_cosets, rounds of a coset-leaf FRI session) were hashed by the zipped-row encoder because a tuple
+ * held an element with fewer than three coefficients (the tests check that no other tree is). */
+uint64_t bfs_coset_trees_by_rows(void);
+/*
  * bfs_merkle_build_rows   SaltedMerkle(list(zip(*codewords)))  (brainfuck_stark.py:178-179, 197-198; salted_merkle.py:22-47):
  *     leaf i = blake2b(pickle.dumps(tuple of the i-th element of every column) || pickle.dumps(salt_i)).  Columns are
  *     codewords in HBM (at most 32, at most 16 of them extension columns): an extension column is three limb planes of n
@@ -382,6 +395,23 @@ int bfs_trace_pad(const bfs_trace_pad_table* tables, uint32_t count, void* strea
  * bfs_fri_session_set_folding : before bfs_fri_commit; BFS_ERR_BAD_ARG for a value outside {1, 2, 3} or a session that has committed.
  * bfs_fri_prove_folded        : bfs_fri_prove with a folding factor.
  *
+ * Coset leaves.  bfs_fri_session_set_coset_leaves(session, 1), before bfs_fri_commit (BFS_ERR_BAD_ARG after it), with any folding
+ * factor: every codeword C_i but the last is committed to with ONE LEAF PER FOLDING COSET.  With q_i = len(C_i) / a = len(C_{i+1}) the
+ * tree of round i < F has q_i leaves, leaf c = blake2b(pickle.dumps((C_i[c], C_i[c + q_i], .., C_i[c + (a - 1) q_i]))), exactly
+ * bfs_merkle_build_xfe_cosets; the tree of the last codeword C_F stays one leaf per element and C_F is pushed as a list.  Roots (r > 0),
+ * challenges and folds are those of the per-element protocol.  Query: top-level indices sample_indices(seed, len(C_1), len(C_F), t) as
+ * before; per layer i < F, with c_i = index mod q_i, first the t tuples (C_i[c_i + j q_i]), j < a -- a elements, nothing of the next
+ * codeword -- then the t paths of leaf c_i in tree i, log2 q_i digests each; no path into tree i + 1.  The verifier folds the a opened
+ * values and finds the result as element number c_i / q_{i+1} of the tuple opened on layer i + 1 (row c_{i+1} = c_i mod q_{i+1}) or,
+ * on the last layer, as last_codeword[c_i].  F >= 1 is required.  The session allocates 16 q_r words of nodes for round r < F.
+ * bfs_fri_session_round0_coset_tree : bfs_fri_session_round0_tree for a tree of bfs_merkle_build_xfe_cosets; bfs_fri_commit answers
+ *                               BFS_ERR_BAD_ARG unless num_leaves is the n / a of this session (and refuses a per-element tree
+ *                               handed to a coset session, and the other way round).
+ * bfs_fri_session_alias       : refused (BFS_ERR_BAD_ARG) in this mode: whole cosets are opened, and the caller cannot hold the element
+ *                               objects of one it has not opened.
+ * bfs_fri_prove_cosets        : bfs_fri_prove_folded with the flag.
+ * bfs_fri_session_round_leaves: leaves of round r's tree (the round's length, or q_r); 0 for a round the session does not have.
+ *
  * The codeword is limb-major in HBM (limb k at d_codeword + k*limb_stride); `ps` is a bfs_ps_new() stream, possibly
  * already holding earlier objects.  These calls synchronise `stream` (each round needs the root on the host).
  * Errors: BFS_ERR_NOT_ROOT ("omega does not have the right order", fri.py:104-105), BFS_ERR_TOO_MANY_INDICES (fri.py:69-70).
@@ -393,6 +423,7 @@ int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out
 void* bfs_fri_session_new(void);
 void bfs_fri_session_free(void* session);
 int bfs_fri_session_set_folding(void* session, uint32_t log2_folding);
+int bfs_fri_session_set_coset_leaves(void* session, int on);
 int bfs_fri_commit(void* session, void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
                    uint64_t omega, uint32_t expansion_factor, void* stream);
 int bfs_fri_query(void* session, void* ps, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream);
@@ -404,15 +435,20 @@ int bfs_fri_session_alias(void* session, void* ps, uint32_t round, uint64_t inde
  * with its root) -- BrainfuckStark.prove commits to the combination codeword and then hands the same codeword to FRI, whose round 0
  * would hash it again (brainfuck_stark.py:301, fri.py:108).  The nodes must stay valid while the session is used. */
 int bfs_fri_session_round0_tree(void* session, const uint8_t* d_nodes, const uint8_t h_root[64]);
+int bfs_fri_session_round0_coset_tree(void* session, const uint8_t* d_nodes, uint64_t num_leaves, const uint8_t h_root[64]);
 int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                   uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream);
 int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                          uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
                          void* stream);
+int bfs_fri_prove_cosets(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, int coset_leaves, uint32_t num_colinearity_tests,
+                         uint64_t* h_top_level_indices, void* stream);
 /* wall-clock breakdown (ms) of the last commit/query on the calling thread: rounds, last codeword, Fiat-Shamir + sampling,
  * planning the openings, gather + sync, building transcript objects */
 void bfs_fri_last_timing(double out[6]);
 uint32_t bfs_fri_session_rounds(void* session);
+uint64_t bfs_fri_session_round_leaves(void* session, uint32_t round);
 int bfs_fri_session_round(void* session, uint32_t round, const uint64_t** d_codeword, uint64_t* length, uint64_t* limb_stride,
                           const uint8_t** d_nodes, uint8_t h_root[64]);
 

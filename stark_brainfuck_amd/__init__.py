@@ -5,7 +5,7 @@ Same call surface as the reference's flat modules:
     from stark_brainfuck_amd import (BaseField, BaseFieldElement, ExtensionField, ExtensionFieldElement, Polynomial,
                                      ntt, intt, fast_multiply, fast_coset_evaluate, fast_coset_interpolate,
                                      batch_inverse, fast_coset_divide, fast_zerofier, fast_evaluate, fast_interpolate,
-                                     SubproductTree, Merkle, SaltedMerkle, ProofStream, Fri)
+                                     SubproductTree, Merkle, CosetMerkle, SaltedMerkle, ProofStream, Fri)
 
 All bulk work runs in hand-written HIP kernels behind the C ABI of libbfstark_hip.so (include/bfstark.h); there is
 no CPU fallback -- importing the compute entry points without the built library raises BackendUnavailable.
@@ -17,7 +17,7 @@ from .extension_field import ExtensionField, ExtensionFieldElement
 from .arrays import BaseArray, XArray
 from .ntt import (ntt, intt, fast_multiply, fast_coset_evaluate, fast_coset_interpolate, batch_inverse,
                   fast_coset_divide, fast_zerofier, fast_evaluate, fast_interpolate, SubproductTree)
-from .merkle import Merkle
+from .merkle import CosetMerkle, Merkle
 from .salted_merkle import SaltedMerkle
 from .ip import ProofStream, reference_pickle
 from .fri import Fri
@@ -26,5 +26,5 @@ from .table import AirViolation, AirViolationError
 
 __all__ = ["BaseField", "BaseFieldElement", "xgcd", "Polynomial", "colinear", "ExtensionField",
            "ExtensionFieldElement", "BaseArray", "XArray", "ntt", "intt", "fast_multiply", "fast_coset_evaluate",
-           "fast_coset_interpolate", "batch_inverse", "fast_coset_divide", "SubproductTree", "Merkle", "SaltedMerkle", "ProofStream",
+           "fast_coset_interpolate", "batch_inverse", "fast_coset_divide", "SubproductTree", "Merkle", "CosetMerkle", "SaltedMerkle", "ProofStream",
            "reference_pickle", "Fri", "BackendUnavailable", "AirViolation", "AirViolationError"]

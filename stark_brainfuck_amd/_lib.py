@@ -93,6 +93,8 @@ _SIGNATURES = {
     "bfs_xfe_sample": (None, [ctypes.c_char_p, sz, ctypes.POINTER(u64)]),
     "bfs_gather": (ci, [vp, u32, vp, vp]),
     "bfs_merkle_build_xfe": (ci, [vp, u64, u64, vp, vp]),
+    "bfs_merkle_build_xfe_cosets": (ci, [vp, u64, u64, u32, vp, vp]),
+    "bfs_coset_trees_by_rows": (u64, []),
     "bfs_merkle_build_bfe": (ci, [vp, u64, vp, vp]),
     "bfs_merkle_build_bytes": (ci, [vp, vp, vp, u64, vp, vp]),
     "bfs_merkle_open": (ci, [vp, u32, u64, vp, vp]),
@@ -110,6 +112,10 @@ _SIGNATURES = {
     "bfs_xfe_fold_multi": (ci, [vp, u64, vp, u64, u32, u32, ctypes.POINTER(u64), u64, u64, vp]),
     "bfs_fri_session_new": (vp, []),
     "bfs_fri_session_set_folding": (ci, [vp, u32]),
+    "bfs_fri_session_set_coset_leaves": (ci, [vp, ci]),
+    "bfs_fri_session_round0_coset_tree": (ci, [vp, vp, u64, ctypes.c_char_p]),
+    "bfs_fri_prove_cosets": (ci, [vp, vp, u64, u32, u64, u64, u32, u32, ci, u32, ctypes.POINTER(u64), vp]),
+    "bfs_fri_session_round_leaves": (u64, [vp, u32]),
     "bfs_fri_session_free": (None, [vp]),
     "bfs_fri_commit": (ci, [vp, vp, vp, u64, u32, u64, u64, u32, vp]),
     "bfs_fri_query": (ci, [vp, vp, u32, ctypes.POINTER(u64), vp]),

@@ -18,6 +18,10 @@ namespace bfs {
 
 int merkle_build_xfe_launch(const u64* d_limbs, u64 limb_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0);
 int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* lo_bits);
+// coset.hip: the tree with one leaf per folding coset
+int coset_tree_launch(const FriFoldArgs* fold, u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, hipStream_t stream, u64* not_mine,
+                      u64 token, u64* root_out, u64 seq);
+int coset_tree_rows(const u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, unsigned char h_root[64], hipStream_t stream);
 
 // the fold on its own (fri.py:127-128, K times: fri_fold_point in runtime.hpp): out[i], i < f.half, from the 2^K inputs in[i + m * f.half]
 // winv_*: two-level powers of the ROUND-0 omega^-1 (exponent i << round_shift)
@@ -68,11 +72,13 @@ static inline double now_ms() { return std::chrono::duration<double, std::milli>
 struct FriRound {
     const u64* cw = nullptr;  // limb-major codeword
     u64 stride = 0, length = 0;
-    u64* nodes = nullptr;     // 2*length digests of 8 words
+    u64 leaves = 0;           // leaves of the round's tree: length, or length / a when the round commits one leaf per coset
+    u64* nodes = nullptr;     // 2*leaves digests of 8 words
     unsigned char root[64];
 };
 
-// pinned, host-visible mailbox the tree kernel drops each round's root into (9 words: digest + sequence flag)
+// pinned, host-visible mailbox the tree kernel drops each round's root into: words 0-7 the digest, word 8 the sequence flag; word 9 is
+// the coset-leaf kernel's not_mine token (coset.hip)
 struct RootMailbox {
     u64* host = nullptr;
     u64* dev = nullptr;
@@ -94,6 +100,8 @@ struct FriSession {
     RootMailbox mailbox;
     u32 log_n = 0;
     u32 log2_folding = 1;   // every round folds its codeword by 2^log2_folding (bfs_fri_session_set_folding)
+    bool coset_leaves = false;   // every round but the last commits one leaf per folding coset (bfs_fri_session_set_coset_leaves)
+    u64 round0_leaves = 0;       // leaves of round0_nodes' tree when the caller said (bfs_fri_session_round0_coset_tree), else 0
     // (round, index) -> the element / tree-node object.  One object per key: the reference pushes the same Python object
     // again when an index recurs, and pickle memoises by identity.
     struct Key {
@@ -160,7 +168,15 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     S.rounds.assign(R, FriRound());
     // one allocation: nodes of every round + codewords of rounds >= 1
     size_t words = 0;
-    for (u32 r = 0; r < R; ++r) words += (size_t)16 * (N >> (k * r)) + (r ? (size_t)3 * (N >> (k * r)) : 0);
+    const bool coset = S.coset_leaves;
+    if (coset && R < 2) { set_error("cannot commit to cosets with less than one fold"); return BFS_ERR_BAD_ARG; }
+    if (S.round0_nodes && S.round0_leaves != (coset ? N >> k : 0)) {
+        set_error("the round-0 tree handed to the session has %llu leaves, this session's has %llu", (unsigned long long)(S.round0_leaves ? S.round0_leaves : N),
+                  (unsigned long long)(coset ? N >> k : N));
+        return BFS_ERR_BAD_ARG;
+    }
+    auto tree_leaves = [&](u32 r) { return (coset && r + 1 < R) ? N >> (k * (r + 1)) : N >> (k * r); };
+    for (u32 r = 0; r < R; ++r) words += (size_t)16 * tree_leaves(r) + (r ? (size_t)3 * (N >> (k * r)) : 0);
     u64* p = nullptr;
     if (S.use_workspace) {
         void* w = nullptr;
@@ -176,7 +192,8 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     for (u32 r = 0; r < R; ++r) {
         FriRound& fr = S.rounds[r];
         fr.length = N >> (k * r);
-        fr.nodes = p; p += 16 * fr.length;
+        fr.leaves = tree_leaves(r);
+        fr.nodes = p; p += 16 * fr.leaves;
         if (r == 0) { fr.cw = d_cw; fr.stride = stride; }
         else { fr.cw = p; fr.stride = fr.length; p += 3 * fr.length; }
     }
@@ -209,45 +226,13 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
         const double t_round = trace ? now_ms() : 0;
         double t_launched = 0, t_absorbed = 0, t_root = 0;
         rp::Transcript::Speculation speculation;
-        const bool fused = fr.length >= 2 && fr.length <= FRI_FUSED_MAX && !(r == 0 && S.round0_nodes);
-        if (fused) {
-            // small codeword: fold (of the previous round) + leaves + subtrees in one launch, root through the mailbox
-            const u64 seq = ++S.mailbox.seq;
-            BFS_TRY(fri_round_fused_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
-            pending.in = nullptr;
-            if (trace) t_launched = now_ms();
-            if (r >= 1) begin_lookahead();
-            if (r + 1 < R) {
-                if (r == 0) { ps.fiat_shamir(ps.objects.size(), seed, 32); have_seed = true; }
-                else if (!looking) { ps.speculate(speculation); speculating = true; }
-            }
-            if (trace) t_absorbed = now_ms();
-            volatile u64* flag = S.mailbox.host + 8;
-            u64 spins = 0;
-            while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                if (++spins > (1ull << 22)) {
-                    BFS_HIP(hipStreamSynchronize(stream));
-                    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) { set_error("root mailbox was not written"); return BFS_ERR_HIP; }
-                    break;
-                }
-            }
-            memcpy(fr.root, S.mailbox.host, 64);
-        } else if (r == 0 && S.round0_nodes) {
-            fr.nodes = (u64*)S.round0_nodes;          // the STARK prover has just committed to this very codeword (brainfuck_stark.py:301 / fri.py:108)
-            memcpy(fr.root, S.round0_root, 64);
-        } else if (fr.length >= 2) {
-            // the tree kernel writes the root straight into pinned host memory; poll the sequence flag instead of
-            // paying a copy command + stream synchronisation per round
-            const u64 seq = ++S.mailbox.seq;
-            if (pending.in != nullptr) {               // the leaf kernel folds the previous round's codeword on the way
-                BFS_TRY(merkle_build_xfe_fold_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
-                pending.in = nullptr;
-            } else {
-                BFS_TRY(merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));  // fri.py:108
-            }
-            // While the GPU hashes: the next challenge is SHAKE256 of the WHOLE transcript including this root (fri.py:112-120), tens
-            // of KB -- as long as the tree kernels of the late rounds.  Everything in front of the root's 64 bytes is known already,
-            // so the sponge absorbs it now and only the last block or two wait for the root.
+        const bool coset_round = coset && r + 1 < R;
+        // what follows every launch of a tree whose root comes through the mailbox.  The tree kernel writes the root straight into pinned
+        // host memory; poll the sequence flag instead of paying a copy command + stream synchronisation per round.  While the GPU
+        // hashes: the next challenge is SHAKE256 of the WHOLE transcript including this root (fri.py:112-120), tens of KB -- as long as
+        // the tree kernels of the late rounds.  Everything in front of the root's 64 bytes is known already, so the sponge absorbs it
+        // now and only the last block or two wait for the root.
+        auto await_root = [&](u64 seq) -> int {
             if (trace) t_launched = now_ms();
             if (r >= 1) begin_lookahead();
             if (r + 1 < R) {
@@ -265,6 +250,40 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
                 }
             }
             memcpy(fr.root, S.mailbox.host, 64);
+            return BFS_OK;
+        };
+        const bool fused = !coset_round && fr.length >= 2 && fr.length <= FRI_FUSED_MAX && !(r == 0 && S.round0_nodes);
+        if (coset_round && !(r == 0 && S.round0_nodes)) {
+            // one leaf per folding coset (coset.hip): the leaf kernel makes the codeword on the way (rounds >= 1), the levels above
+            // the fr.leaves leaves and the root's way to the host are those of the per-element tree
+            const u64 seq = ++S.mailbox.seq;
+            BFS_TRY(coset_tree_launch(pending.in != nullptr ? &pending : nullptr, (u64*)fr.cw, fr.stride, fr.leaves, k, fr.nodes, stream, S.mailbox.dev + 9, seq,
+                                      S.mailbox.dev, seq));
+            pending.in = nullptr;
+            BFS_TRY(await_root(seq));
+            if (__atomic_load_n(S.mailbox.host + 9, __ATOMIC_ACQUIRE) == seq) {
+                // a tuple with an element that stores fewer than three coefficients: the zipped-row interpreter hashes the tree again
+                // (the codeword is in HBM by now) -- every other codeword than one lifted from the base field never comes here
+                BFS_TRY(coset_tree_rows(fr.cw, fr.stride, fr.leaves, k, fr.nodes, fr.root, stream));
+            }
+        } else if (fused) {
+            // small codeword: fold (of the previous round) + leaves + subtrees in one launch, root through the mailbox
+            const u64 seq = ++S.mailbox.seq;
+            BFS_TRY(fri_round_fused_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
+            pending.in = nullptr;
+            BFS_TRY(await_root(seq));
+        } else if (r == 0 && S.round0_nodes) {
+            fr.nodes = (u64*)S.round0_nodes;          // the STARK prover has just committed to this very codeword (brainfuck_stark.py:301 / fri.py:108)
+            memcpy(fr.root, S.round0_root, 64);
+        } else if (fr.length >= 2) {
+            const u64 seq = ++S.mailbox.seq;
+            if (pending.in != nullptr) {               // the leaf kernel folds the previous round's codeword on the way
+                BFS_TRY(merkle_build_xfe_fold_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
+                pending.in = nullptr;
+            } else {
+                BFS_TRY(merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));  // fri.py:108
+            }
+            BFS_TRY(await_root(seq));
         } else {
             BFS_TRY(merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream));
             if (r >= 1) begin_lookahead();
@@ -362,6 +381,7 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     g_fri_timing[2] = now_ms() - t_begin;   // Fiat-Shamir + index sampling
     typedef FriSession::Key Key;
     const u32 fan = 1u << S.log2_folding;         // elements of round i that one element of round i + 1 depends on
+    const bool coset = S.coset_leaves;            // a test opens one leaf of fan elements and one path per layer, nothing of the next round
     {   // what the openings can touch at most: fan + 1 elements and authentication paths per colinearity check and layer
         size_t depth_sum = 0;
         for (u32 r = 0; r < R; ++r) depth_sum += 64 - (size_t)__builtin_clzll(S.rounds[r].length);
@@ -383,7 +403,7 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     };
     auto need_path = [&](u32 r, u64 leaf) {      // merkle.py:46-52
         const FriRound& fr = S.rounds[r];
-        for (u64 k = fr.length | leaf; k > 1; k >>= 1) {
+        for (u64 k = fr.leaves | leaf; k > 1; k >>= 1) {
             Key key(r, k ^ 1);
             if (S.nodes.count(key)) continue;
             S.nodes[key] = rp::Ref();
@@ -399,6 +419,7 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
         for (u32 s = 0; s < t; ++s) {
             u64 c = layer_idx[i][s];
             for (u32 m = 0; m < fan; ++m) need_element(cur, c + m * q);
+            if (coset) { need_path(cur, c); continue; }
             need_element(cur + 1, c);
             for (u32 m = 0; m < fan; ++m) need_path(cur, c + m * q);
             if (!lastq) need_path(cur + 1, c);
@@ -433,8 +454,8 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     }
     auto path_obj = [&](u32 r, u64 leaf) {
         std::vector<rp::Ref> items;
-        items.reserve(64 - (size_t)__builtin_clzll(S.rounds[r].length));
-        for (u64 k = S.rounds[r].length | leaf; k > 1; k >>= 1) items.push_back(S.nodes[Key(r, k ^ 1)]);
+        items.reserve(64 - (size_t)__builtin_clzll(S.rounds[r].leaves));
+        for (u64 k = S.rounds[r].leaves | leaf; k > 1; k >>= 1) items.push_back(S.nodes[Key(r, k ^ 1)]);
         return rp::mk_list(std::move(items));
     };
     // push in the reference's order: per layer, t leaf triples then the authentication paths (fri.py:147-156, 166-174)
@@ -447,11 +468,12 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
             std::vector<rp::Ref> items;
             items.reserve(fan + 1);
             for (u32 m = 0; m < fan; ++m) items.push_back(S.elements[Key(cur, c + m * q)]);
-            items.push_back(S.elements[Key(cur + 1, c)]);
+            if (!coset) items.push_back(S.elements[Key(cur + 1, c)]);
             ps.objects.push_back(rp::mk_tuple(std::move(items)));
         }
         for (u32 s = 0; s < t; ++s) {
             u64 c = layer_idx[i][s];
+            if (coset) { ps.objects.push_back(path_obj(cur, c)); continue; }
             for (u32 m = 0; m < fan; ++m) ps.objects.push_back(path_obj(cur, c + m * q));
             if (!lastq) ps.objects.push_back(path_obj(cur + 1, c));
         }
@@ -486,6 +508,13 @@ int bfs_fri_session_set_folding(void* session, uint32_t log2_folding) {
     return BFS_OK;
 }
 
+int bfs_fri_session_set_coset_leaves(void* session, int on) {
+    FriSession* S = (FriSession*)session;
+    if (!S->rounds.empty()) { set_error("bfs_fri_session_set_coset_leaves: the session has already committed"); return BFS_ERR_BAD_ARG; }
+    S->coset_leaves = on != 0;
+    return BFS_OK;
+}
+
 int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                   uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream) {
     return bfs_fri_prove_folded(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, 1, num_colinearity_tests, h_top_level_indices, stream);
@@ -494,9 +523,17 @@ int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, ui
 int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
                          uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
                          void* stream) {
+    return bfs_fri_prove_cosets(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, log2_folding, 0, num_colinearity_tests,
+                                h_top_level_indices, stream);
+}
+
+int bfs_fri_prove_cosets(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, int coset_leaves, uint32_t num_colinearity_tests,
+                         uint64_t* h_top_level_indices, void* stream) {
     FriSession S;
     S.use_workspace = true;
     BFS_TRY(bfs_fri_session_set_folding(&S, log2_folding));
+    BFS_TRY(bfs_fri_session_set_coset_leaves(&S, coset_leaves));
     BFS_TRY(fri_commit(S, *(rp::Transcript*)ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, (hipStream_t)stream));
     return fri_query(S, *(rp::Transcript*)ps, num_colinearity_tests, h_top_level_indices, (hipStream_t)stream);
 }
@@ -661,6 +698,16 @@ int bfs_gather(const bfs_gather_request* requests, uint32_t count, uint64_t* h_o
 int bfs_fri_session_round0_tree(void* session, const uint8_t* d_nodes, const uint8_t h_root[64]) {
     FriSession* S = (FriSession*)session;
     S->round0_nodes = (const u64*)d_nodes;
+    S->round0_leaves = 0;
+    memcpy(S->round0_root, h_root, 64);
+    return BFS_OK;
+}
+
+int bfs_fri_session_round0_coset_tree(void* session, const uint8_t* d_nodes, uint64_t num_leaves, const uint8_t h_root[64]) {
+    FriSession* S = (FriSession*)session;
+    if (num_leaves == 0 || (num_leaves & (num_leaves - 1))) { set_error("bfs_fri_session_round0_coset_tree: %llu leaves", (unsigned long long)num_leaves); return BFS_ERR_BAD_ARG; }
+    S->round0_nodes = (const u64*)d_nodes;
+    S->round0_leaves = num_leaves;
     memcpy(S->round0_root, h_root, 64);
     return BFS_OK;
 }
@@ -668,6 +715,10 @@ int bfs_fri_session_round0_tree(void* session, const uint8_t* d_nodes, const uin
 int bfs_fri_session_alias(void* session, void* ps, uint32_t round, uint64_t index, uint64_t element_handle) {
     rp::Ref r = ((rp::Transcript*)ps)->get(element_handle);
     if (!r) { set_error("bfs_fri_session_alias: unknown object handle"); return BFS_ERR_BAD_ARG; }
+    if (((FriSession*)session)->coset_leaves) {
+        set_error("bfs_fri_session_alias: a session that commits to cosets opens whole cosets; the caller cannot hold elements of one it has not opened");
+        return BFS_ERR_BAD_ARG;
+    }
     ((FriSession*)session)->elements[FriSession::Key(round, index)] = r;
     return BFS_OK;
 }
@@ -681,9 +732,14 @@ int bfs_fri_session_round(void* session, uint32_t r, const uint64_t** d_codeword
     FriSession* S = (FriSession*)session;
     if (r >= S->rounds.size()) { set_error("round %u out of range", r); return BFS_ERR_BAD_ARG; }
     const FriRound& fr = S->rounds[r];
-    *d_codeword = fr.cw; *length = fr.length; *limb_stride = fr.stride; *d_nodes = (const uint8_t*)fr.nodes;
+    *d_codeword = fr.cw; *length = fr.length; *limb_stride = fr.stride; *d_nodes = (const uint8_t*)fr.nodes;     // (fr.leaves leaves: bfs_fri_session_round_leaves)
     memcpy(h_root, fr.root, 64);
     return BFS_OK;
+}
+
+uint64_t bfs_fri_session_round_leaves(void* session, uint32_t r) {
+    FriSession* S = (FriSession*)session;
+    return r < S->rounds.size() ? S->rounds[r].leaves : 0;
 }
 
 int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, const uint64_t alpha[3],

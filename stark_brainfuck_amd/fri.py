@@ -1,6 +1,6 @@
 """FRI low-degree test, prover on the GPU -- mirror of the reference's `fri.py` (/root/reference/code/fri.py:13-319).
 
-    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2)
+    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False)
       .domain   Fri.Domain: offset, omega, length, __call__, list, evaluate, xevaluate, interpolate, xinterpolate
       .num_rounds()  .sample_indices(...)  .commit(...)  .query(...)  .query_last(...)  .prove(...)  .verify(...)
 
@@ -13,6 +13,13 @@ byte for byte.  A round of folding by 4 (8) with challenge alpha is two (three) 
 challenges alpha, alpha^2 (, alpha^4), offset and omega squared between them; the codewords in between are neither kept nor committed
 to.  With L = log2(N / expansion_factor) there are F = (L - 1) // k folds and F + 1 codewords; a colinearity test opens, per layer, the
 a elements C_i[c + j * q], q = len(C_i) / a, and C_{i+1}[c] as one tuple, then their a (+ 1) authentication paths.
+
+`coset_leaves=True` (with any folding factor) commits to every codeword but the last with ONE MERKLE LEAF PER FOLDING COSET: the tree of
+round i < F has q_i = len(C_i) / a leaves, leaf c = blake2b(pickle.dumps((C_i[c], C_i[c + q_i], .., C_i[c + (a - 1) q_i]))) -- `CosetMerkle`
+(merkle.py).  A colinearity test then opens, per layer, that tuple of a elements and ONE path of log2 q_i digests; nothing of C_{i+1} is
+opened on layer i, because the value the tuple folds to is element number c_i // q_{i+1} of the tuple opened on layer i + 1 (and
+last_codeword[c_i] on the last layer).  The caller's root is the coset root of C_0: `CosetMerkle(codeword, a).root()`.  The default,
+False, is the per-element protocol above, byte for byte.
 """
 import ctypes
 from hashlib import blake2b
@@ -21,7 +28,7 @@ from . import _lib
 from .arrays import BaseArray, XArray
 from .device import current_stream
 from .ip import NativeTranscript, ProofStream
-from .merkle import Merkle
+from .merkle import CosetMerkle, Merkle
 from .ntt import _base_value, _transform, fast_coset_interpolate
 from .univariate import Polynomial, colinear
 
@@ -97,8 +104,10 @@ class Fri:
         def xinterpolate(self, values):
             return fast_coset_interpolate(self.offset, self.omega, values)
 
-    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2):
+    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False):
         assert folding_factor in (2, 4, 8), "folding factor must be 2, 4 or 8"
+        assert coset_leaves is True or coset_leaves is False, "coset_leaves must be True or False"
+        self.coset_leaves = coset_leaves
         self.domain = Fri.Domain(offset, omega, initial_domain_length)
         self.field = xfield
         self.expansion_factor = expansion_factor
@@ -108,6 +117,7 @@ class Fri:
         assert self.num_rounds() >= 1, "cannot do FRI with less than one round"
         # (folding by 2 keeps the reference's rule: one round constructs, and prove() fails for want of a second codeword)
         assert folding_factor == 2 or self.num_rounds() >= 2, "cannot do FRI with less than one fold"
+        assert not coset_leaves or self.num_rounds() >= 2, "cannot commit to cosets with less than one fold"
 
     def num_rounds(self):
         """number of codewords: the reference's count of halvings h (fri.py:54-60) when folding by 2, (h - 1) // k + 1 in general"""
@@ -146,6 +156,13 @@ class Fri:
         return codeword if isinstance(codeword, XArray) else XArray.from_elements(list(codeword))
 
     def _run_native(self, codeword, proof_stream, with_query, known_leafs=None, round0_tree=None):
+        if self.coset_leaves:
+            assert not known_leafs, "known_leafs: a Fri that commits to cosets opens whole cosets, the caller cannot hold elements of one"
+            assert round0_tree is None or (isinstance(round0_tree, CosetMerkle) and round0_tree.coset_size == self.folding_factor
+                                           and round0_tree.num_leafs * self.folding_factor == len(codeword)), \
+                "round0_tree must be a CosetMerkle over this codeword with coset_size = the folding factor"
+        else:
+            assert not isinstance(round0_tree, CosetMerkle), "round0_tree is a CosetMerkle, this Fri commits to single elements"
         lib, stream = _lib.load(), current_stream()
         arr = self._as_xarray(codeword)
         n = len(arr)
@@ -164,7 +181,11 @@ class Fri:
         try:
             if self._log2_folding != 1:
                 _lib.check(lib.bfs_fri_session_set_folding(session, self._log2_folding))
-            if round0_tree is not None and round0_tree._nodes_host is None and round0_tree.num_leafs == n:
+            if self.coset_leaves:
+                _lib.check(lib.bfs_fri_session_set_coset_leaves(session, 1))
+                if round0_tree is not None and round0_tree._nodes_host is None:
+                    _lib.check(lib.bfs_fri_session_round0_coset_tree(session, round0_tree._nodes.ptr, round0_tree.num_leafs, round0_tree.root()))
+            elif round0_tree is not None and round0_tree._nodes_host is None and round0_tree.num_leafs == n:
                 _lib.check(lib.bfs_fri_session_round0_tree(session, round0_tree._nodes.ptr, round0_tree.root()))
             _lib.check(lib.bfs_fri_commit(session, transcript.handle, arr.ptr, arr.stride, n.bit_length() - 1,
                                           _base_value(self.domain.offset), _base_value(self.domain.omega), self.expansion_factor, stream))
@@ -209,12 +230,16 @@ class Fri:
             if r + 1 == len(rounds):
                 view._items = proof_stream.objects[-1]      # fri.py:134 pushes this very list: keep object identity
             codewords.append(view)
-            if r + 1 < len(rounds):
+            if r + 1 < len(rounds) and self.coset_leaves:
+                trees.append(CosetMerkle(view, self.folding_factor, _device_nodes=_Borrowed(nodes, keeper)))
+            elif r + 1 < len(rounds):
                 trees.append(Merkle(view, _device_nodes=_Borrowed(nodes, keeper)))
         return codewords, trees
 
     def query(self, current_tree, next_tree, c_indices, proof_stream):
         """fri.py:141-158; folding by a: the a elements c + j * q of the current codeword instead of the two c, c + half"""
+        if self.coset_leaves:
+            return self._query_cosets(current_tree, c_indices, proof_stream)      # (nothing of the next tree is opened)
         a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
         opened = [[i + j * q for i in c_indices] for j in range(a)]          # (a = 2: a_indices, b_indices)
         for s in range(self.num_colinearity_tests):
@@ -227,6 +252,8 @@ class Fri:
 
     def query_last(self, current_tree, last_codeword, c_indices, proof_stream):
         """fri.py:160-176"""
+        if self.coset_leaves:
+            return self._query_cosets(current_tree, c_indices, proof_stream)
         a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
         opened = [[i + j * q for i in c_indices] for j in range(a)]
         for s in range(self.num_colinearity_tests):
@@ -235,6 +262,17 @@ class Fri:
             for j in range(a):
                 proof_stream.push(current_tree.open(opened[j][s]))
         return [i for column in opened for i in column]
+
+    def _query_cosets(self, current_tree, c_indices, proof_stream):
+        """one layer of the coset protocol: the t opened cosets (tuples of a elements), then their t paths; returns the indices of the
+        opened elements, column by column as `query` does"""
+        a, q = self.folding_factor, current_tree.num_leafs
+        assert isinstance(current_tree, CosetMerkle) and current_tree.coset_size == a, "a Fri that commits to cosets queries CosetMerkle trees"
+        for s in range(self.num_colinearity_tests):
+            proof_stream.push(current_tree.leafs[c_indices[s]])
+        for s in range(self.num_colinearity_tests):
+            proof_stream.push(current_tree.open(c_indices[s]))
+        return [i + j * q for j in range(a) for i in c_indices]
 
     def prove(self, codeword, proof_stream, known_leafs=None, round0_tree=None):
         """fri.py:178-199: commit + query in one native call; returns the top-level indices.
@@ -279,6 +317,8 @@ class Fri:
         if top > degree:
             return False
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), N >> k, N >> (k * (rounds - 1)), t)
+        if self.coset_leaves:
+            return self._verify_coset_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
         if a != 2:
             return self._verify_folded_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
         for r in range(rounds - 1):
@@ -367,6 +407,65 @@ class Fri:
             for _ in range(k):
                 omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
         return True
+
+    def _verify_coset_layers(self, proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v):
+        """the layers of `verify` when every round commits one leaf per folding coset: per layer r the t opened cosets -- tuples of the a
+        values C_r[c + j * q], c = index mod q, q = len(C_r) / a -- then their t paths (log2 q digests each) into tree r.  The value a
+        coset folds to (the arithmetic of _verify_folded_layers; one step when a = 2) is not in the stream: it must be element number
+        c_{r-1} // q of the coset the same test opens on this layer, and on the last layer last_codeword[c]."""
+        from .air import P
+        rounds, t, N, k, a = self.num_rounds(), self.num_colinearity_tests, self.domain.length, self._log2_folding, self.folding_factor
+        expected = None                                   # per test: (position in this layer's tuple, the value the previous layer folded to)
+        for r in range(rounds - 1):
+            q = N >> (k * (r + 1))
+            c_indices = [i % q for i in top_level_indices]
+            opened, folded = [], []
+            for s in range(t):
+                values = proof_stream.pull()
+                if not isinstance(values, tuple) or len(values) != a or not all(hasattr(e, "limbs") for e in values):
+                    print("colinearity check failure")
+                    return False
+                v = [tuple(e.limbs()) for e in values]
+                if expected is not None and v[expected[s][0]] != expected[s][1]:
+                    print("colinearity check failure")
+                    return False
+                opened.append(values)
+                folded.append(_fold_coset(v, tuple(alphas[r].limbs()), offset_v, omega_v, c_indices[s], q, k))
+            if r + 1 == rounds - 1:
+                for s in range(t):
+                    if folded[s] != tuple(last_codeword[c_indices[s]].limbs()):
+                        print("leafs in last round do not correspond to last codeword")
+                        return False
+            for s in range(t):
+                path = proof_stream.pull()
+                if not isinstance(path, list) or len(path) != q.bit_length() - 1 or not all(isinstance(node, (bytes, bytearray)) for node in path):
+                    print("merkle authentication path verification fails for the opened coset")
+                    return False
+                if not Merkle.verify(roots[r], c_indices[s], path, opened[s]):
+                    print("merkle authentication path verification fails for the opened coset")
+                    return False
+            q_next = q >> k
+            expected = [(c_indices[s] // q_next, folded[s]) for s in range(t)] if q_next else None
+            for _ in range(k):
+                omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
+        return True
+
+
+def _fold_coset(values, alpha, g, w, c, q, k):
+    """the a = 2^k values C[c + j q] (integer triples) folded k times: fri.py:127-128 on integer residues, with alpha^(2^step), offset g
+    and generator w squared between the steps -- the arithmetic of Fri._verify_folded_layers"""
+    from .air import P, xadd, xmul, xscale, xsub
+    half_inv = pow(2, P - 2, P)
+    v = list(values)
+    for _ in range(k):
+        h = len(v) // 2
+        folded = []
+        for m in range(h):
+            x_inv = pow(g * pow(w, c + m * q, P) % P, P - 2, P)
+            beta = xscale(alpha, half_inv * x_inv % P)
+            folded.append(xadd(xscale(xadd(v[m], v[m + h]), half_inv), xmul(beta, xsub(v[m], v[m + h]))))
+        v, alpha, g, w = folded, xmul(alpha, alpha), g * g % P, w * w % P
+    return v[0]
 
 
 def _host_merkle_root(leaves):

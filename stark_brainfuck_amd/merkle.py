@@ -191,3 +191,49 @@ class Merkle:
             running = blake2b(running + node).digest() if index % 2 == 0 else blake2b(node + running).digest()
             index >>= 1
         return running == root
+
+
+class CosetMerkle(Merkle):
+    """Merkle tree with one leaf per folding coset of a codeword: for `coset_size` a in (2, 4, 8) and q = len(codeword) / a, leaf c < q
+    is the tuple (codeword[c], codeword[c + q], .., codeword[c + (a - 1) q]) -- the a elements one fold by a consumes -- hashed as the
+    reference's Merkle hashes any leaf, blake2b(pickle.dumps(tuple)) (merkle.py:29-32): this is Merkle([those tuples]), built from the
+    limbs in HBM (bfs_merkle_build_xfe_cosets, csrc/coset.hip).  What Fri(..., folding_factor=a, coset_leaves=True) commits to:
+
+        tree = CosetMerkle(codeword, a)
+        fri.prove(codeword, proof_stream, round0_tree=tree)
+        fri.verify(proof_stream, tree.root())
+
+    `codeword` is an XArray or a list of ExtensionFieldElement whose length is a power of two.  `.root()`, `.open(row)`, `.nodes` and
+    `CosetMerkle.verify` are Merkle's; `.leafs[row]` is the tuple."""
+
+    def __init__(self, codeword, coset_size, _device_nodes=None):
+        assert coset_size in (2, 4, 8), "coset size must be 2, 4 or 8"
+        n = len(codeword)
+        assert n >= coset_size and n & (n - 1) == 0, "codeword length must be a power of two, at least the coset size"
+        self.coset_size = coset_size
+        self.num_leafs = n // coset_size
+        self._npo2, self.depth = _tree_shape(self.num_leafs)
+        self._data = codeword
+        self._leafs = None
+        self._nodes_host = None
+        self._node_cache = {}
+        if _device_nodes is not None:            # tree already built in HBM (Fri.commit)
+            self._nodes = _device_nodes
+            return
+        self._nodes = DeviceBuffer(max(2 * self._npo2, 2) * 8)
+        arr = getattr(codeword, "array", codeword)
+        if not isinstance(arr, XArray):
+            assert all(isinstance(e, ExtensionFieldElement) for e in codeword), "CosetMerkle is over extension-field codewords"
+            arr = XArray.from_elements(list(codeword))
+        stream = current_stream()
+        _lib.check(_lib.load().bfs_merkle_build_xfe_cosets(arr.ptr, arr.stride, n, coset_size.bit_length() - 1, self._nodes.ptr, stream))
+        synchronize(stream)
+
+    @property
+    def leafs(self):
+        if self._leafs is None:
+            d = self._data
+            elements = d.to_elements() if isinstance(d, XArray) else list(d)
+            a, q = self.coset_size, self.num_leafs
+            self._leafs = [tuple(elements[c + j * q] for j in range(a)) for c in range(q)]
+        return self._leafs

@@ -1,12 +1,14 @@
-"""Times FRI with folding factors 2, 4 and 8, and folding by 2 against another build of the library (A/B).
+"""Times FRI with folding factors 2, 4 and 8, with one Merkle leaf per element and per folding coset (coset_leaves), and folding by 2
+against another build of the library (A/B).
 
     python tools/fri_folding_time.py [--sizes 20,24] [--reps 30] [--other-lib PATH] [--stark] [--json FILE]
 
 One process, every shape warmed before it is timed, a host clock around calls that end in a stream synchronise, the variants
 alternated call by call (so drift of the clock or of the host hits all of them alike).  N = 2^size, expansion 4, 4 colinearity tests.
 
-  1. Fri.prove (the Python call, fresh ProofStream each time) and bfs_fri_prove_folded (the C ABI, codeword resident in HBM) for
-     folding 2, 4, 8: median and fastest time, proof bytes, number of stream objects.
+  1. Fri.prove (the Python call, fresh ProofStream each time) and bfs_fri_prove_cosets (the C ABI, codeword resident in HBM) for
+     folding 2, 4, 8, each with per-element and with coset leaves: median and fastest time, proof bytes, number of stream objects, and
+     the ratio coset / per-element at the same folding factor.
   2. with --other-lib: bfs_fri_prove and bfs_xfe_fold of THIS build and of the library at PATH (e.g. one built from the parent
      commit), both loaded into this process and alternated.  Each build is measured as two interleaved series; the distance between
      the medians of the two series of one build is the spread of this run, and the builds differ measurably only beyond it.
@@ -26,7 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 EXPANSION, TESTS, OFFSET = 4, 4, 7
-NEW_SYMBOLS = ("bfs_xfe_fold_multi", "bfs_fri_session_set_folding", "bfs_fri_prove_folded")
+NEW_SYMBOLS = ("bfs_xfe_fold_multi", "bfs_fri_session_set_folding", "bfs_fri_prove_folded", "bfs_merkle_build_xfe_cosets", "bfs_coset_trees_by_rows",
+               "bfs_fri_session_set_coset_leaves", "bfs_fri_session_round0_coset_tree", "bfs_fri_prove_cosets", "bfs_fri_session_round_leaves")
 
 
 def _load_package_library():
@@ -81,7 +84,9 @@ def folding_variants(lib, _lib, log_n, reps):
     XF = sb.ExtensionField.main()
     BF = XF.modulus.coefficients[0].field
     cw = sb.XArray(d_cw, N, XF, N)
-    fris = {a: sb.Fri(BF.generator(), BF.primitive_nth_root(N), N, EXPANSION, TESTS, XF, folding_factor=a) for a in (2, 4, 8)}
+    # variant = (folding factor, coset leaves)
+    fris = {(a, coset): sb.Fri(BF.generator(), BF.primitive_nth_root(N), N, EXPANSION, TESTS, XF, folding_factor=a, coset_leaves=coset)
+            for a in (2, 4, 8) for coset in (False, True)}
     out = {a: {"python_ms": [], "c_abi_ms": []} for a in fris}
 
     def python_call(a):
@@ -96,7 +101,7 @@ def folding_variants(lib, _lib, log_n, reps):
         ps = lib.bfs_ps_new()
         idx = (ctypes.c_uint64 * TESTS)()
         t0 = time.perf_counter()
-        _lib.check(lib.bfs_fri_prove_folded(ps, d_cw.ptr, N, log_n, OFFSET, omega, EXPANSION, a.bit_length() - 1, TESTS, idx, 0))
+        _lib.check(lib.bfs_fri_prove_cosets(ps, d_cw.ptr, N, log_n, OFFSET, omega, EXPANSION, a[0].bit_length() - 1, int(a[1]), TESTS, idx, 0))
         _lib.check(lib.bfs_stream_synchronize(0))
         dt = time.perf_counter() - t0
         return dt, ps
@@ -119,7 +124,7 @@ def folding_variants(lib, _lib, log_n, reps):
     for a in fris:
         out[a]["python"], out[a]["c_abi"] = _stats(out[a].pop("python_ms")), _stats(out[a].pop("c_abi_ms"))
     d_cw.free()
-    return out
+    return {"%d%s" % (a, "c" if coset else ""): r for (a, coset), r in out.items()}
 
 
 def _ab_report(series):
@@ -221,11 +226,12 @@ def main():
     result = {"expansion": EXPANSION, "colinearity_tests": TESTS, "reps": args.reps, "sizes": {}}
     for log_n in [int(x) for x in args.sizes.split(",")]:
         entry = {"folding": folding_variants(lib, _lib, log_n, args.reps)}
-        print("N = 2^%d  (Fri.prove: Python call; C ABI: bfs_fri_prove_folded)" % log_n)
-        print("  folding  codewords  objects  proof bytes   Fri.prove median / min ms    C ABI median / min ms")
+        print("N = 2^%d  (Fri.prove: Python call; C ABI: bfs_fri_prove_cosets; folding 4c = folding by 4 with coset leaves)" % log_n)
+        print("  folding  codewords  objects  proof bytes   Fri.prove median / min ms    C ABI median / min ms   C ABI coset / per-element")
         for a, r in entry["folding"].items():
-            print("  %7d  %9d  %7d  %11d   %10.3f / %-10.3f   %10.3f / %-10.3f" % (a, r["codewords"], r["objects"], r["proof_bytes"], r["python"]["median_ms"],
-                                                                                r["python"]["min_ms"], r["c_abi"]["median_ms"], r["c_abi"]["min_ms"]))
+            ratio = "%.3f" % (r["c_abi"]["median_ms"] / entry["folding"][a[:-1]]["c_abi"]["median_ms"]) if a.endswith("c") else ""
+            print("  %7s  %9d  %7d  %11d   %10.3f / %-10.3f   %10.3f / %-10.3f   %s" % (a, r["codewords"], r["objects"], r["proof_bytes"], r["python"]["median_ms"],
+                                                                                     r["python"]["min_ms"], r["c_abi"]["median_ms"], r["c_abi"]["min_ms"], ratio))
         if other is not None:
             entry["ab"] = ab_folding_two(lib, other, _lib, log_n, args.reps)
             for what, r in entry["ab"].items():

@@ -805,7 +805,8 @@ class BrainfuckStark:
         terminals of the two permutation arguments (processor against instruction / memory table) and the input, output and
         program evaluation terminals against this stark's input_symbols, output_symbols and program (what verify() checks).
         Those come back as kind "permutation" (index 0 instruction, 1 memory) / "evaluation" (0 input, 1 output, 2 program) with
-        first_row None.  The caller's matrices are left as they are."""
+        first_row None; an input or output MATRIX that does not hold the symbols the processor read or wrote comes back the same way
+        under the table name "input" / "output".  The caller's matrices are left as they are."""
         import copy
         matrices = {0: processor_matrix, 1: instruction_matrix, 2: memory_matrix, 3: input_matrix, 4: output_matrix}
         tables = []
@@ -846,6 +847,10 @@ class BrainfuckStark:
         for k, (name, terminal) in enumerate((("processor", pt.input_evaluation_terminal), ("processor", pt.output_evaluation_terminal),
                                               ("instruction", it.evaluation_terminal))):
             pairs.append((name, "evaluation", k, terminal, self.evaluation_arguments[k].compute_terminal(challenges)))
+        # ... and the input / output table against the processor's running evaluations: prove() sends the processor's terminals, and the
+        # IO tables' terminal constraints are taken against those
+        pairs += [("input", "evaluation", 0, inp.evaluation_terminal, pt.input_evaluation_terminal),
+                  ("output", "evaluation", 1, outp.evaluation_terminal, pt.output_evaluation_terminal)]
         violations += [AirViolation(name, kind, k, None, 1) for name, kind, k, lhs, rhs in pairs if tuple(lhs) != tuple(rhs)]
         return violations
 
@@ -959,6 +964,13 @@ class BrainfuckStark:
         # ... and as STORED, for the three evaluation arguments at the end: the reference compares the pulled object with a computed
         # element through Polynomial.__eq__ / BaseFieldElement.__eq__, i.e. the coefficient values as they were pickled (round-5 advice)
         stored_terminals = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
+        # io_table.py:54-56, which the reference reaches through num_quotients below (brainfuck_stark.py:394-395): a non-empty input
+        # (output) table against a terminal stored as all zeros raises there instead of ending in False; input table first.  NOT where
+        # the claim's own symbols evaluate to zero too (a single symbol 0: `-+.`): such claims are proven and verified here, while the
+        # reference's prover stops at that very assertion.
+        for io, ea in zip((self.input_table, self.output_table), self.evaluation_arguments):
+            if io.height != 0 and not any(stored_terminals[io.terminal_index]):
+                assert not any(ea.compute_terminal(challenges)), "evaluation terminal for non-empty IOTable is zero but shouldn't be!"
 
         base_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.base_width)]
         extension_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.full_width - t.base_width)]

@@ -419,6 +419,21 @@ int bfs_stark_verify_begin(void* ps, const bfs_stark_verify_params* params, uint
         Reader rd{t};
         Begin b;
         read_begin(rd, b);
+        // io_table.py:54-56, which the reference reaches through num_quotients right behind the terminals (brainfuck_stark.py:394-395): a
+        // non-empty input (output) table against a terminal stored as all zeros is an AssertionError there, not False; the input table is
+        // asked first.  NOT where the claim's own symbols evaluate to zero as well (a single symbol 0: `-+.`): such claims are proven and
+        // verified here, the reference's prover stops at the same assertion.
+        if (params != nullptr) {
+            const u64* symbols[2] = {params->input, params->output};
+            const size_t counts[2] = {(size_t)params->n_input, (size_t)params->n_output};
+            for (int k = 0; k < 2; ++k) {
+                if (params->heights[3 + k] == 0 || !xfe_is_zero(b.terminals_stored[2 + k])) continue;
+                const Xfe point{{b.challenges[3 * (8 + k)], b.challenges[3 * (8 + k) + 1], b.challenges[3 * (8 + k) + 2]}};
+                Xfe acc{{0, 0, 0}};
+                for (size_t i = 0; i < counts[k]; ++i) acc = xfe_add_base(xfe_mul(acc, point), symbols[k][i] % GL_P);
+                if (!xfe_is_zero(acc)) throw Assertion{"evaluation terminal for non-empty IOTable is zero but shouldn't be!"};
+            }
+        }
         // Fiat-Shamir ahead of time.  The read positions at which FRI asks are known from the protocol parameters alone: behind the
         // openings (four objects per opened row, two per combination leaf) it asks before every round's root and once behind the last
         // codeword -- each time over ~50 KB.  Exactly those prefixes go to the helper threads now, in the order they will be needed; the

@@ -94,7 +94,10 @@ uint64_t bfs_gl_pow(uint64_t a, uint64_t e);
  * Transform b reads d_in + b*in_stride (n_in elements) and writes d_out + b*out_stride (2^log_n elements).  The input is left
  * untouched when input and output do not overlap, and then the transform needs no intermediate memory (its first pass writes the
  * output, later passes run in place there); the two ranges may also overlap in any way -- d_in == d_out, an output that starts inside
- * the input -- in which case the first two passes go through a library buffer of the output's size.  Stream-ordered: the call only
+ * the input, an output of one transform that covers the inputs of others (d_in == d_out with in_stride < out_stride) -- in which
+ * case the call goes through a library buffer: above 2^12 the first two passes, through a buffer of the output's size; up to 2^12,
+ * where one workgroup loads a whole transform before it stores, only when the overlap is not d_in == d_out with equal strides, and
+ * then the input is copied to a buffer of its size first.  Stream-ordered: the call only
  * enqueues kernels (it never measures, synchronises or allocates candidate buffers by itself; it may be captured into a hipGraph once
  * its tables exist, i.e. after one plain call of the same shape).  A pair of buffers that bfs_ntt_tune() found a faster route for is
  * served through the library buffer that call kept.
@@ -128,18 +131,23 @@ int bfs_ntt_route_forget(const void* d_ptr, size_t* forgotten);
  * buffer chosen; *probes = measurements taken so far (0: none yet, us / route are then 0 / -1).  Any pointer may be NULL. */
 int bfs_ntt_route_probe_info(float* us, int* route, unsigned long long* probes);
 
-/* Polynomial.scale(factor): out[b][i] = in[b][i] * factor^i                         univariate.py:168-169 */
+/* Polynomial.scale(factor): out[b][i] = in[b][i] * factor^i                         univariate.py:168-169
+ * Aliasing: d_out may be d_in (in place; both use `stride`); any other overlap of output and input is not supported. */
 int bfs_gl_scale(const uint64_t* d_in, uint64_t* d_out, uint64_t n, uint64_t stride, uint32_t batch, uint64_t factor,
                  void* stream);
 
 /* Hadamard product (ntt.py:76) out = a * b, and batch inversion (ntt.py:177-188; Fermat inverse per element).
- * bfs_gl_batch_inverse synchronises the stream and returns BFS_ERR_ZERO_IN_BATCH_INVERSE if any input is 0. */
+ * bfs_gl_batch_inverse synchronises the stream and returns BFS_ERR_ZERO_IN_BATCH_INVERSE if any input is 0 (its output is 0 there).
+ * Aliasing: d_out may be an input (in place: d_out == d_a, d_out == d_b, both; d_out == d_in); any other overlap of output and
+ * input is not supported. */
 int bfs_gl_mul_pointwise(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
 int bfs_gl_batch_inverse(const uint64_t* d_in, uint64_t* d_out, uint64_t n, void* stream);
 /* The same two over the cubic extension F_p[X]/(X^3 - X + 1) (limb planes `*_stride` words apart): what fast_multiply's
  * hadamard_product (ntt.py:74-76) and fast_coset_divide's batch_inverse (ntt.py:226-229) compute when their operands are
  * ExtensionFieldElements -- the way Table.ldex reaches them (table.py:133-134 -> ntt.py:126-161 -> 82-98 -> 45-79), with
- * ExtensionField.multiply / inverse (extension_field.py:71-83) per point.  In place (d_out == an input) is allowed.
+ * ExtensionField.multiply / inverse (extension_field.py:71-83) per point.
+ * Aliasing: d_out may be an input with the same stride (in place: d_out == d_a, d_out == d_b, both; d_out == d_in); any other
+ * overlap of output and input is not supported.
  * bfs_xfe_batch_inverse synchronises the stream; a zero element gives BFS_ERR_ZERO_IN_BATCH_INVERSE (its output is zero). */
 int bfs_xfe_mul_pointwise(const uint64_t* d_a, uint64_t a_stride, const uint64_t* d_b, uint64_t b_stride, uint64_t* d_out, uint64_t out_stride,
                           uint64_t n, void* stream);
@@ -164,6 +172,7 @@ int bfs_xfe_batch_inverse(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_
  * Stream-ordered: every call enqueues its kernels on `stream` and takes its temporaries from the pool; the tree is ready for work
  * ordered after bfs_ptree_build on its stream.  bfs_ptree_interpolate synchronises the stream once (the batch inverse of Z'(x_i),
  * as bfs_gl_batch_inverse): two equal points give BFS_ERR_ZERO_IN_BATCH_INVERSE and leave d_out unwritten.
+ * Aliasing: d_out must not overlap the points, coefficients or values (the tree is the library's own memory).
  */
 typedef struct bfs_ptree bfs_ptree;
 int bfs_ptree_build(const uint64_t* d_points, uint64_t n, void* stream, bfs_ptree** out);
@@ -282,7 +291,8 @@ int bfs_stark_push_openings(void* ps, const bfs_gather_request* base_row, uint32
  * two >= n, leaf i at index npo2 + i, parent k = BLAKE2b-512(nodes[2k] || nodes[2k+1]), root at index 1.  Index 0
  * and the slots of absent leaves are not written (the reference keeps 32 zero bytes there; the parent of an absent
  * leaf hashes those 32 zero bytes, which these kernels reproduce).  d_nodes must hold 2*npo2*64 bytes and be 16-byte aligned
- * (BFS_ERR_BAD_ARG otherwise).
+ * (BFS_ERR_BAD_ARG otherwise).  Aliasing: d_nodes must not overlap the leaves' data (codewords, columns, messages, salts), which are
+ * only read; this holds for every bfs_merkle_build_* below.
  *   bfs_merkle_build_xfe   Merkle(codeword) over ExtensionFieldElement leaves   merkle.py:8-41 (leaf = blake2b(pickle.dumps(e)))
  *   bfs_merkle_build_bfe   same over BaseFieldElement leaves (stand-alone BaseField instance)
  *   bfs_merkle_build_bytes same over caller-pickled leaves: message i = lengths[i] bytes at d_data + 8*word_offsets[i]
@@ -344,7 +354,8 @@ int bfs_row_template_steps(const bfs_row_column* columns, uint32_t ncols, uint32
  * layouts do and that other layouts do not). */
 uint64_t bfs_row_generated_launches(void);
 /* nwords (a multiple of 8) pseudo-random words in HBM: 64-byte block j = BLAKE2b-512(seed || j).  For salts that never visit
- * the host (the reference draws os.urandom(24) per leaf, salted_merkle.py:25; the caller seeds this from os.urandom(32)). */
+ * the host (the reference draws os.urandom(24) per leaf, salted_merkle.py:25; the caller seeds this from os.urandom(32)).  Another
+ * nwords is refused (BFS_ERR_BAD_ARG) and nothing is written. */
 int bfs_random_fill(const uint8_t seed[32], uint64_t* d_out, uint64_t nwords, void* stream);
 /* `count` pseudo-random extension elements (limb planes `limb_stride` words apart) in HBM: ExtensionField.sample
  * (extension_field.py:100-111) of 27 bytes per element, element i taking bytes [27 i, 27 i + 27) of the stream made of the first 63
@@ -362,7 +373,8 @@ int bfs_xfe_sample_fill(const uint8_t seed[32], uint64_t* d_out, uint64_t count,
  *   kind 1 instruction (width >= 2): d_mask0 = rows of the running product, d_mask1 = rows of the running evaluation
  *   kind 2 memory      (width >= 4): d_mask0 = non-dummy rows
  *   kind 3 / 4 input / output: padding rows are zero rows, no masks.
- * Stream-ordered; at most five tables per call.
+ * Masks a kind does not have are not written.  Stream-ordered; at most five tables per call.
+ * Aliasing: not supported -- d_out and the masks must not overlap d_rows or each other (the call transposes).
  */
 typedef struct bfs_trace_pad_table {
     const uint64_t* d_rows;
@@ -414,6 +426,10 @@ int bfs_trace_pad(const bfs_trace_pad_table* tables, uint32_t count, void* strea
  *
  * The codeword is limb-major in HBM (limb k at d_codeword + k*limb_stride); `ps` is a bfs_ps_new() stream, possibly
  * already holding earlier objects.  These calls synchronise `stream` (each round needs the root on the host).
+ * Aliasing: bfs_xfe_fold and bfs_xfe_fold_multi: d_out may be d_in with out_stride == in_stride (in place: the folded codeword
+ * replaces the first n / a elements of every limb plane, the rest of the plane is left as it was); any other overlap of output and
+ * input is not supported.  bfs_fri_commit / bfs_fri_prove*: the caller's codeword and a tree handed in with
+ * bfs_fri_session_round0_tree / _coset_tree are only read; the rounds' codewords and trees are the session's own memory.
  * Errors: BFS_ERR_NOT_ROOT ("omega does not have the right order", fri.py:104-105), BFS_ERR_TOO_MANY_INDICES (fri.py:69-70).
  */
 int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n,
@@ -519,6 +535,9 @@ int bfs_host_transpose(const uint64_t* src, size_t rows, size_t src_stride, size
  *     d_x1 is read `shift1` rows ahead (cyclically), the three limb planes of the result go to d_out, d_out + out_stride,
  *     d_out + 2 out_stride.  The final state is written to d_terminal (device, three words) and / or terminal (host; this
  *     synchronises the stream); either may be NULL.
+ *     Aliasing: not supported -- d_out and d_terminal must not overlap d_x1..d_x3, d_mask or each other (a workgroup's rows are read
+ *     by other workgroups' lookback); the same holds for every scan of bfs_xfe_scan_device_many, whose outputs must not overlap
+ *     another scan's operands either.
  */
 int bfs_xfe_scan_device(int kind, const uint64_t* d_x1, const uint64_t* d_x2, const uint64_t* d_x3, uint64_t shift1,
                         const uint8_t* d_mask, uint64_t n, const uint64_t constants[12], const uint64_t initial[3],
@@ -618,7 +637,9 @@ int bfs_zerofier_inverses(uint32_t log_n, uint64_t offset, uint64_t omega, uint3
  * The same three on a RANGE of the domain's points, rows [first_row, first_row + num_rows): every rank of a cooperative proof
  * (BrainfuckStark.cooperate; brainfuck_stark.py:204-298 split by rows) holds all codewords and computes the pointwise stages for its own
  * rows only -- a row's neighbour at unit_distance is read from the rank's own copy, so there is no halo to exchange -- and the ranks then
- * all-gather the combination codeword.  d_out / d_acc are the FULL buffers (the range is written in place).
+ * all-gather the combination codeword.  d_out / d_acc are the FULL buffers (the range is written in place; rows outside it are
+ * neither read nor written).  Aliasing: d_out / d_acc must not overlap the codewords read (d_base, d_ext, d_lhs, d_rhs, the randomizer,
+ * the zerofier inverses); d_acc is read and written at the rows of the range only.
  */
 int bfs_air_combine_rows(int table, const uint64_t* d_base, const uint64_t* d_ext, uint32_t log_n, uint64_t unit_distance, uint64_t height,
                          uint64_t omicron_inv, uint64_t offset, uint64_t omega, const uint64_t* h_challenges, const uint64_t* h_terminals,

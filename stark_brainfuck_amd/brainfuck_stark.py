@@ -151,7 +151,7 @@ class BrainfuckStark:
     # ---- several GPUs on one proof (shard.RowShardedSaltedMerkle): every rank runs the polynomial stages on all columns and hashes
     # only its range of the zipped rows; set by cooperate() and used inside shard.shared_randomness()
     _cooperation = None
-    _row_windows = None      # tests: [(first, count), ...] tiling the FRI domain -- the combination stage runs window by window
+    _row_windows = None      # tests: [(first, count), ...] tiling the FRI domain, in any order -- the combination stage runs window by window
     _shift_tweak = None      # tests: shifts -> shifts, applied to the combination's degree shifts (both combination paths see the result)
 
     def cooperate(self, world_size, rank, group=None, device=None):
@@ -740,8 +740,9 @@ class BrainfuckStark:
             windows = [rows]
             if rows is None and self._row_windows is not None:
                 windows = list(self._row_windows)
-                ends = [first + count for first, count in windows]
-                assert [first for first, _ in windows] == [0] + ends[:-1] and ends[-1] == n, "the windows must tile the domain in order"
+                # run in the order given (every window initialises its own rows of the accumulator): any order of a tiling
+                ends = [first + count for first, count in sorted(windows)]
+                assert [first for first, _ in sorted(windows)] == [0] + ends[:-1] and ends[-1] == n, "the windows must tile the domain"
             for window in windows:
                 inverse_buffer, inverses = zerofier_inverses(self.tables, domain, rows=window)      # all zerofier denominators, one inversion per point
                 base_at = ext_at = 0

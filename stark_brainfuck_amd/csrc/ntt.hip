@@ -573,6 +573,21 @@ int ntt_launch(const u64* d_in, u64 n_in, u64 in_stride, u64* d_out, u64 out_str
                   (unsigned long long)in_stride, (unsigned long long)n_in, (unsigned long long)out_stride, (unsigned long long)n);
         return BFS_ERR_BAD_ARG;
     }
+    if (log_n <= NTT_TILE_LOG && n_in != 0) {
+        // No pass or one: one workgroup per transform, which loads all it reads before it stores anything, so a transform may
+        // overwrite its OWN input (d_in == d_out with equal strides).  Any other overlap lets transform b write where another
+        // transform, possibly of a workgroup that has not started yet, still has to read: the input goes through the library
+        // buffer first (multi-pass plans stage such calls below).  Decided on the whole batch, before it is sliced.
+        const u64* in_end = d_in + (u64)(batch - 1) * in_stride + n_in;
+        const u64* out_end = d_out + (u64)(batch - 1) * out_stride + n;
+        if (d_in < out_end && d_out < in_end && !(d_in == d_out && in_stride == out_stride)) {
+            void* w = nullptr;
+            const size_t span = (size_t)(in_end - d_in) * sizeof(u64);
+            BFS_TRY(workspace(0, span, stream, &w));
+            BFS_HIP(hipMemcpyAsync(w, d_in, span, hipMemcpyDeviceToDevice, stream));
+            d_in = (const u64*)w;
+        }
+    }
     if (batch > 65535) {
         // grid.y carries the batch index and is limited to 65535: larger batches go in slices (transforms are independent)
         for (u32 done = 0; done < batch;) {

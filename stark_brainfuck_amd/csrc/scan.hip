@@ -210,10 +210,36 @@ static void scan_fill(ScanArgs& a, int kind, const u64* d_x1, const u64* d_x2, c
     a.kind = (u32)kind;
 }
 
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char *pa = (const char*)a, *pb = (const char*)b;
+    return pa && pb && a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// Do the outputs of one scan (three limb planes, the terminal) overlap the operands of a scan (its own or another of the same call)?
+// The row updates are read twice, by the reduction and again when the running values are applied, and x1 is read `shift1` rows
+// ahead by another thread: an output that aliases an operand is not supported (include/bfstark.h) and refused.
+static bool scan_output_aliases(const u64* d_out, u64 out_stride, u64 n_out, const u64* d_terminal, const u64* d_x1, const u64* d_x2,
+                                const u64* d_x3, const unsigned char* d_mask, u64 n) {
+    const void* operands[4] = {d_x1, d_x2, d_x3, d_mask};
+    const size_t bytes[4] = {(size_t)n * sizeof(u64), (size_t)n * sizeof(u64), (size_t)n * sizeof(u64), (size_t)n};
+    for (int k = 0; k < 4; ++k) {
+        if (ranges_overlap(d_out, (size_t)(2 * out_stride + n_out) * sizeof(u64), operands[k], bytes[k])) return true;
+        if (ranges_overlap(d_terminal, 3 * sizeof(u64), operands[k], bytes[k])) return true;
+    }
+    return false;
+}
+
 extern "C" int bfs_xfe_scan_device_many(const bfs_scan_spec* specs, uint32_t count, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (count == 0) return BFS_OK;
     if (count > 64) { set_error("bfs_xfe_scan_device_many: at most 64 scans per call"); return BFS_ERR_BAD_ARG; }
+    for (uint32_t o = 0; o < count; ++o)
+        for (uint32_t i = 0; i < count; ++i)
+            if (specs[o].d_out && scan_output_aliases(specs[o].d_out, specs[o].out_stride, specs[o].n, specs[o].d_terminal, specs[i].d_x1, specs[i].d_x2,
+                                                      specs[i].d_x3, specs[i].d_mask, specs[i].n)) {
+                set_error("bfs_xfe_scan_device_many: the output of scan %u overlaps an operand of scan %u", o, i);
+                return BFS_ERR_BAD_ARG;
+            }
     std::vector<ScanArgs> args(count);
     const size_t per = (3 * 256 + 8) * sizeof(Xfe);
     void* w = nullptr;
@@ -256,6 +282,10 @@ extern "C" int bfs_xfe_scan_device(int kind, const uint64_t* d_x1, const uint64_
         return BFS_OK;
     }
     if (out_stride < n) { set_error("bfs_xfe_scan_device: out_stride < n"); return BFS_ERR_BAD_ARG; }
+    if (scan_output_aliases(d_out, out_stride, n, d_terminal, d_x1, d_x2, d_x3, d_mask, n)) {
+        set_error("bfs_xfe_scan_device: the output overlaps an operand");
+        return BFS_ERR_BAD_ARG;
+    }
     ScanArgs a{};
     a.x1 = d_x1; a.x2 = d_x2; a.x3 = d_x3; a.mask = d_mask; a.n = n; a.shift1 = d_x1 ? shift1 % n : 0;
     for (int j = 0; j < 4; ++j) a.c[j] = Xfe{{constants[3 * j] % GL_P, constants[3 * j + 1] % GL_P, constants[3 * j + 2] % GL_P}};
@@ -348,6 +378,22 @@ extern "C" int bfs_trace_pad(const bfs_trace_pad_table* tables, uint32_t count, 
         }
         a.t[k] = t;
         tallest = t.height > tallest ? t.height : tallest;
+    }
+    // the call transposes (thread r reads row r and writes element r of every column): no output may overlap any table's rows
+    for (uint32_t i = 0; i < count; ++i) {
+        const bfs_trace_pad_table& in = tables[i];
+        if (in.rows == 0) continue;
+        const size_t in_bytes = (size_t)((in.rows - 1) * in.row_stride + in.width) * sizeof(u64);
+        for (uint32_t o = 0; o < count; ++o) {
+            const bfs_trace_pad_table& out = tables[o];
+            const uint8_t* masks[3] = {out.d_mask0, out.d_mask1, out.d_mask2};
+            bool hit = ranges_overlap(in.d_rows, in_bytes, out.d_out, (size_t)out.width * out.height * sizeof(u64));
+            for (int m = 0; m < 3; ++m) hit = hit || ranges_overlap(in.d_rows, in_bytes, masks[m], (size_t)out.height);
+            if (hit) {
+                bfs::set_error("bfs_trace_pad: an output of table %u overlaps the rows of table %u", o, i);
+                return BFS_ERR_BAD_ARG;
+            }
+        }
     }
     if (tallest == 0) return BFS_OK;
     hipLaunchKernelGGL(bfs::trace_pad_kernel, dim3((u32)((tallest + 255) / 256), count), dim3(256), 0, stream, a);

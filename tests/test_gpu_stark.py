@@ -159,11 +159,14 @@ def test_a_refused_commit_leaves_the_threads_session_usable(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("order", ["ascending", "descending", "interleaved"])
 @pytest.mark.parametrize("name", ["loop", "two_io"])
-def test_combination_by_row_windows_writes_the_reference_proof(name, monkeypatch):
+def test_combination_by_row_windows_writes_the_reference_proof(name, order, monkeypatch):
     """bfs_zerofier_inverses_rows / bfs_air_combine_rows / bfs_difference_combine_rows (a cooperative proof's share of the pointwise
     stages) with the domain cut into ragged windows -- one point, an odd count, a piece that ends one short of the middle, the rest:
-    the accumulator must come out as from one launch over the whole domain, i.e. the proof is still the reference's"""
+    the accumulator must come out as from one launch over the whole domain, i.e. the proof is still the reference's.  The windows
+    run in ascending order, in descending order and interleaved: a write that lands in rows outside its window is hidden when a
+    LATER window initialises those rows (always so in ascending order for a write past the window's end), not when they were done."""
     from stark_brainfuck_amd import brainfuck_stark, salted_merkle, table
     from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
     from stark_brainfuck_amd.vm import VirtualMachine
@@ -174,7 +177,8 @@ def test_combination_by_row_windows_writes_the_reference_proof(name, monkeypatch
     stark = BrainfuckStark(running_time, len(matrices[1]), program, input_symbols, output_symbols)
     n = stark.fri.domain.length
     cuts = [0, 1, 258, n // 2 - 1, n]
-    stark._row_windows = [(a, b - a) for a, b in zip(cuts, cuts[1:])]
+    windows = [(a, b - a) for a, b in zip(cuts, cuts[1:])]
+    stark._row_windows = {"ascending": windows, "descending": windows[::-1], "interleaved": [windows[k] for k in (2, 0, 3, 1)]}[order]
     stream = Stream(name.encode())
     for mod in (brainfuck_stark, salted_merkle, table):
         monkeypatch.setattr(mod, "urandom", stream)

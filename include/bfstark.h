@@ -424,6 +424,20 @@ int bfs_trace_pad(const bfs_trace_pad_table* tables, uint32_t count, void* strea
  * bfs_fri_prove_cosets        : bfs_fri_prove_folded with the flag.
  * bfs_fri_session_round_leaves: leaves of round r's tree (the round's length, or q_r); 0 for a round the session does not have.
  *
+ * Grinding.  bfs_fri_session_set_grinding(session, bits, window), before bfs_fri_commit (BFS_ERR_BAD_ARG after it, and for bits > 40),
+ * in any of the modes above: bfs_fri_query then does a proof of work before it draws the indices.  With seed = the 32 bytes of
+ * Fiat-Shamir randomness over the stream up to the last codeword, it pushes the SMALLEST nonce n >= 0 with
+ *     int.from_bytes(blake2b(seed + n.to_bytes(8, "little")).digest()[:8], "little") >> (64 - bits) == 0
+ * as a plain int (the object of bfs_ps_obj_int) and samples the indices from the randomness over the stream that holds the nonce.
+ * bits = 0, the default, pushes nothing: the protocol above, byte for byte.  `window`: nonces per search step, 0 = the library's
+ * default (2^24, one launch of a millisecond or two); the steps ascend from 0 and the first one with a hit ends the search, which
+ * gives up with an error after 2^(bits + 6) nonces.  With grinding, slot 2 of bfs_fri_last_timing includes the search.
+ * bfs_pow_check  : host only, no GPU needed: *ok = 1 iff `nonce` satisfies the condition above for `seed`; bits in 1..40.
+ * bfs_pow_search : the smallest such nonce in [first_nonce, first_nonce + count) on the GPU: *found = 0 if there is none, else
+ *                  *nonce.  One or more bounded launches; synchronises the stream.  BFS_ERR_BAD_ARG: bits outside 1..40, count = 0, a
+ *                  window that goes beyond 2^64.  The search writes no memory of the caller's on the device.
+ * The one-shot bfs_fri_prove* entries do not grind.
+ *
  * The codeword is limb-major in HBM (limb k at d_codeword + k*limb_stride); `ps` is a bfs_ps_new() stream, possibly
  * already holding earlier objects.  These calls synchronise `stream` (each round needs the root on the host).
  * Aliasing: bfs_xfe_fold and bfs_xfe_fold_multi: d_out may be d_in with out_stride == in_stride (in place: the folded codeword
@@ -440,6 +454,9 @@ void* bfs_fri_session_new(void);
 void bfs_fri_session_free(void* session);
 int bfs_fri_session_set_folding(void* session, uint32_t log2_folding);
 int bfs_fri_session_set_coset_leaves(void* session, int on);
+int bfs_fri_session_set_grinding(void* session, uint32_t bits, uint64_t window);
+int bfs_pow_check(const uint8_t seed[32], uint32_t bits, uint64_t nonce, int* ok);
+int bfs_pow_search(const uint8_t seed[32], uint32_t bits, uint64_t first_nonce, uint64_t count, uint64_t* nonce, int* found, void* stream);
 int bfs_fri_commit(void* session, void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
                    uint64_t omega, uint32_t expansion_factor, void* stream);
 int bfs_fri_query(void* session, void* ps, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream);

@@ -113,6 +113,9 @@ _SIGNATURES = {
     "bfs_fri_session_new": (vp, []),
     "bfs_fri_session_set_folding": (ci, [vp, u32]),
     "bfs_fri_session_set_coset_leaves": (ci, [vp, ci]),
+    "bfs_fri_session_set_grinding": (ci, [vp, u32, u64]),
+    "bfs_pow_check": (ci, [ctypes.c_char_p, u32, u64, ctypes.POINTER(ci)]),
+    "bfs_pow_search": (ci, [ctypes.c_char_p, u32, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(ci), vp]),
     "bfs_fri_session_round0_coset_tree": (ci, [vp, vp, u64, ctypes.c_char_p]),
     "bfs_fri_prove_cosets": (ci, [vp, vp, u64, u32, u64, u64, u32, u32, ci, u32, ctypes.POINTER(u64), vp]),
     "bfs_fri_session_round_leaves": (u64, [vp, u32]),

@@ -101,6 +101,8 @@ struct FriSession {
     u32 log_n = 0;
     u32 log2_folding = 1;   // every round folds its codeword by 2^log2_folding (bfs_fri_session_set_folding)
     bool coset_leaves = false;   // every round but the last commits one leaf per folding coset (bfs_fri_session_set_coset_leaves)
+    u32 grinding_bits = 0;       // bfs_fri_query grinds a nonce of that many zero bits before it draws the indices (bfs_fri_session_set_grinding)
+    u64 grinding_window = POW_DEFAULT_WINDOW;   // nonces per search step
     u64 round0_leaves = 0;       // leaves of round0_nodes' tree when the caller said (bfs_fri_session_round0_coset_tree), else 0
     // (round, index) -> the element / tree-node object.  One object per key: the reference pushes the same Python object
     // again when an index recurs, and pickle memoises by identity.
@@ -360,12 +362,35 @@ static int sample_indices(const unsigned char seed[32], u64 size, u64 reduced_si
     return BFS_OK;
 }
 
+// proof of work: the smallest nonce whose hash with the seed drawn after the last codeword starts with S.grinding_bits zero bits goes
+// into the transcript as a plain int.  The windows ascend, so the first one with a hit holds the smallest nonce there is; the search
+// gives up after 2^(bits + 6) nonces (a seed without a hit among them has probability e^-64).
+static int fri_grind(const FriSession& S, const unsigned char seed[32], hipStream_t stream, rp::Transcript& ps) {
+    u64 words[4];
+    memcpy(words, seed, 32);
+    const u64 limit = 1ULL << (S.grinding_bits + 6);
+    for (u64 first = 0; first < limit;) {
+        const u64 count = limit - first < S.grinding_window ? limit - first : S.grinding_window;
+        u64 nonce = 0;
+        bool found = false;
+        BFS_TRY(pow_search(words, S.grinding_bits, first, count, &nonce, &found, stream));
+        if (found) { ps.objects.push_back(rp::mk_int(nonce)); return BFS_OK; }
+        first += count;
+    }
+    set_error("bfs_fri_query: no nonce of %u grinding bits among the first 2^%u", S.grinding_bits, S.grinding_bits + 6);
+    return BFS_ERR_BAD_ARG;
+}
+
 int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t stream) {
     const u32 R = (u32)S.rounds.size();
     if (R < 2) { set_error("Fri.prove needs at least two rounds (fri.py:186 indexes codewords[1])"); return BFS_ERR_BAD_ARG; }
     const double t_begin = now_ms();
     unsigned char seed[32];
     ps.fiat_shamir(ps.objects.size(), seed, 32);
+    if (S.grinding_bits) {
+        BFS_TRY(fri_grind(S, seed, stream, ps));
+        ps.fiat_shamir(ps.objects.size(), seed, 32);      // the indices come from the stream that holds the nonce
+    }
     std::vector<u64> top;
     BFS_TRY(sample_indices(seed, S.rounds[1].length, S.rounds[R - 1].length, t, top));  // fri.py:186-187
     for (u32 s = 0; s < t; ++s) h_top[s] = top[s];
@@ -512,6 +537,15 @@ int bfs_fri_session_set_coset_leaves(void* session, int on) {
     FriSession* S = (FriSession*)session;
     if (!S->rounds.empty()) { set_error("bfs_fri_session_set_coset_leaves: the session has already committed"); return BFS_ERR_BAD_ARG; }
     S->coset_leaves = on != 0;
+    return BFS_OK;
+}
+
+int bfs_fri_session_set_grinding(void* session, uint32_t bits, uint64_t window) {
+    FriSession* S = (FriSession*)session;
+    if (bits > 40) { set_error("bfs_fri_session_set_grinding: bits must be in 0..40 (got %u)", bits); return BFS_ERR_BAD_ARG; }
+    if (!S->rounds.empty()) { set_error("bfs_fri_session_set_grinding: the session has already committed"); return BFS_ERR_BAD_ARG; }
+    S->grinding_bits = bits;
+    S->grinding_window = window ? window : POW_DEFAULT_WINDOW;
     return BFS_OK;
 }
 

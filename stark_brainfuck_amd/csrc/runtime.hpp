@@ -140,6 +140,12 @@ void ntt_route_trim();
 int ntt_launch(const u64* d_in, u64 n_in, u64 in_stride, u64* d_out, u64 out_stride, u32 log_n, u32 batch, u64 root,
                u64 shift, u64 post_scale, hipStream_t stream);
 
+// pow.hip: the smallest nonce in [first, first + count) whose hash with `seed` starts with `bits` zero bits (pow_core.hpp); bounded
+// launches in ascending order, the stream synchronised after each.  POW_DEFAULT_WINDOW: the nonces of one search step of a FRI
+// session that was given no window of its own -- one full launch, a millisecond or two.
+constexpr u64 POW_DEFAULT_WINDOW = 1ULL << 24;
+int pow_search(const u64 seed[4], u32 bits, u64 first, u64 count, u64* nonce, bool* found, hipStream_t stream);
+
 // pinned, device-visible staging for one gather call: a lease on a block of the pooled pinned-host allocator (runtime.cpp:
 // mutex-guarded, size classes, no hipHostMalloc / hipHostFree on the hot path).  One lease per call, so that concurrent provers
 // -- threads, or several devices driven by one process -- never share a staging buffer; the lease goes back when the call returns.

@@ -1,8 +1,10 @@
 """FRI low-degree test, prover on the GPU -- mirror of the reference's `fri.py` (/root/reference/code/fri.py:13-319).
 
-    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False)
+    Fri(offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False,
+        grinding_bits=0)
       .domain   Fri.Domain: offset, omega, length, __call__, list, evaluate, xevaluate, interpolate, xinterpolate
       .num_rounds()  .sample_indices(...)  .commit(...)  .query(...)  .query_last(...)  .prove(...)  .verify(...)
+    grind(seed, bits, first_nonce=0, count=None)  check_grinding(seed, nonce, bits)
 
 `prove` / `commit` run the whole round loop natively (csrc/fri.hip): Merkle trees, folding and openings on the GPU,
 Fiat-Shamir on the host in C++.  `codeword` may be a Python list of ExtensionFieldElement (as in the reference) or an
@@ -20,6 +22,14 @@ round i < F has q_i = len(C_i) / a leaves, leaf c = blake2b(pickle.dumps((C_i[c]
 opened on layer i, because the value the tuple folds to is element number c_i // q_{i+1} of the tuple opened on layer i + 1 (and
 last_codeword[c_i] on the last layer).  The caller's root is the coset root of C_0: `CosetMerkle(codeword, a).root()`.  The default,
 False, is the per-element protocol above, byte for byte.
+
+`grinding_bits=b`, 1 <= b <= 40 (in any of the modes above), puts a PROOF OF WORK between the commit phase and the queries.  With seed =
+the Fiat-Shamir randomness drawn after the last codeword -- the call that yields the index seed when b = 0 -- `prove` pushes the smallest
+int n >= 0 for which blake2b(seed + n.to_bytes(8, "little")).digest()[:8], read as a little-endian integer, has its b top bits zero
+(`check_grinding`), and samples the indices from the randomness over the stream that holds n.  The search runs on the GPU (`grind`,
+csrc/pow.hip); the verifier's check is one hashlib call.  Re-rolling the indices costs a cheating prover 2^b hashes per attempt, so the
+conjectured security is t * log2(expansion_factor) + b bits and t can shrink accordingly.  `commit` on its own pushes no nonce: grinding
+belongs to `prove`.  The default, 0, pushes nothing: the protocols above, byte for byte.
 """
 import ctypes
 from hashlib import blake2b
@@ -33,6 +43,24 @@ from .ntt import _base_value, _transform, fast_coset_interpolate
 from .univariate import Polynomial, colinear
 
 _u64 = ctypes.c_uint64
+MAX_GRINDING_BITS = 40
+
+
+def check_grinding(seed, nonce, bits):
+    """the proof-of-work predicate: blake2b(seed + nonce as 8 little-endian bytes) starts, read as a little-endian 64-bit integer, with
+    `bits` zero bits.  hashlib only: the verifier's side."""
+    assert len(seed) == 32 and 1 <= bits <= 64 and 0 <= nonce < 1 << 64
+    return int.from_bytes(blake2b(bytes(seed) + nonce.to_bytes(8, "little")).digest()[:8], "little") >> (64 - bits) == 0
+
+
+def grind(seed, bits, first_nonce=0, count=None):
+    """the smallest nonce in [first_nonce, first_nonce + count) that `check_grinding` accepts, or None; searched on the GPU
+    (bfs_pow_search).  count=None: up to 2^(bits + 6) nonces, where a seed without a hit has probability e^-64."""
+    assert len(seed) == 32, "the seed is 32 bytes"
+    count = min(1 << (bits + 6), (1 << 64) - first_nonce) if count is None else count
+    nonce, found = _u64(), ctypes.c_int()
+    _lib.check(_lib.load().bfs_pow_search(bytes(seed), bits, first_nonce, count, ctypes.byref(nonce), ctypes.byref(found), current_stream()))
+    return int(nonce.value) if found.value else None
 
 
 class _Codeword:
@@ -104,10 +132,14 @@ class Fri:
         def xinterpolate(self, values):
             return fast_coset_interpolate(self.offset, self.omega, values)
 
-    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False):
+    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, xfield, folding_factor=2, coset_leaves=False,
+                 grinding_bits=0):
         assert folding_factor in (2, 4, 8), "folding factor must be 2, 4 or 8"
         assert coset_leaves is True or coset_leaves is False, "coset_leaves must be True or False"
+        assert type(grinding_bits) is int and 0 <= grinding_bits <= MAX_GRINDING_BITS, "grinding_bits must be an int from 0 to 40"
         self.coset_leaves = coset_leaves
+        self.grinding_bits = grinding_bits
+        self._grinding_window = None          # nonces per search step; None: the library's default
         self.domain = Fri.Domain(offset, omega, initial_domain_length)
         self.field = xfield
         self.expansion_factor = expansion_factor
@@ -181,6 +213,8 @@ class Fri:
         try:
             if self._log2_folding != 1:
                 _lib.check(lib.bfs_fri_session_set_folding(session, self._log2_folding))
+            if self.grinding_bits:
+                _lib.check(lib.bfs_fri_session_set_grinding(session, self.grinding_bits, self._grinding_window or 0))
             if self.coset_leaves:
                 _lib.check(lib.bfs_fri_session_set_coset_leaves(session, 1))
                 if round0_tree is not None and round0_tree._nodes_host is None:
@@ -316,6 +350,12 @@ class Fri:
         top = _interpolant_degree(last_omega_v, [tuple(e.limbs()) for e in last_codeword])
         if top > degree:
             return False
+        if self.grinding_bits:
+            seed = proof_stream.verifier_fiat_shamir()          # over the stream up to the last codeword
+            nonce = proof_stream.pull()
+            if type(nonce) is not int or not 0 <= nonce < 1 << 64 or not check_grinding(seed, nonce, self.grinding_bits):
+                print("proof of work check failure")
+                return False
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), N >> k, N >> (k * (rounds - 1)), t)
         if self.coset_leaves:
             return self._verify_coset_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)

@@ -322,7 +322,13 @@ class ProofStream:
         # SHAKE256 of pickle.dumps(objects[:read_index]) (ip.py:29-30).  The pickle of a prefix of the list is what the
         # (cached) transcript of the whole list holds for its first read_index objects -- memo indices and frame cuts only
         # depend on what came before -- so nothing is re-encoded per call.
-        return self._native().fiat_shamir(self.read_index, num_bytes)
+        try:
+            transcript = self._native()
+        except TypeError:
+            # something further on is nothing the native transcript takes (a bool, an int outside [0, 2^64)): what was pulled so far can
+            # still be hashed, and the verifier refuses the odd object when it pulls it
+            return self._build(self.objects[:self.read_index]).fiat_shamir(None, num_bytes)
+        return transcript.fiat_shamir(self.read_index, num_bytes)
 
     def deserialize(self, bb):
         """ip.py:27-30.  The Python objects come from CPython's unpickler (into this package's classes); the verifier's Fiat-Shamir

@@ -103,7 +103,7 @@ static int coset_block0_states(const u64** d_table) {
     return cached_table(KEY, A, 0, host.data(), host.size(), d_table);
 }
 
-template <int A, int KF>      // KF = log2 A
+template <int KF, int A = 1 << KF>
 static int coset_leaves_launch_a(const FriFoldArgs* fold, u64* d_cw, u64 cw_stride, u64 q, u64* d_leaf_digests, hipStream_t stream, u64* not_mine, u64 token) {
     const u64* d_states = nullptr;
     BFS_TRY(coset_block0_states<A>(&d_states));
@@ -121,16 +121,10 @@ int coset_tree_launch(const FriFoldArgs* fold, u64* d_cw, u64 cw_stride, u64 q, 
                       u64 token, u64* root_out, u64 seq) {
     if (q == 0 || (q & (q - 1))) { set_error("internal: coset tree over %llu leaves", (unsigned long long)q); return BFS_ERR_BAD_ARG; }
     if (fold != nullptr && (fold->log2_folding != log2_coset || fold->half != (q << log2_coset))) { set_error("internal: coset tree and fold disagree"); return BFS_ERR_BAD_ARG; }
-    u32 depth = 0;
-    while ((1ull << depth) < q) ++depth;
-    u64* leaves = d_nodes + q * 8;
-    switch (log2_coset) {
-    case 1: BFS_TRY((coset_leaves_launch_a<2, 1>(fold, d_cw, cw_stride, q, leaves, stream, not_mine, token))); break;
-    case 2: BFS_TRY((coset_leaves_launch_a<4, 2>(fold, d_cw, cw_stride, q, leaves, stream, not_mine, token))); break;
-    case 3: BFS_TRY((coset_leaves_launch_a<8, 3>(fold, d_cw, cw_stride, q, leaves, stream, not_mine, token))); break;
-    default: set_error("coset size must be 2, 4 or 8 (log2 = %u)", log2_coset); return BFS_ERR_BAD_ARG;
-    }
-    return merkle_inner_launch(d_nodes, depth, q, stream, root_out, seq);
+    BFS_TRY(with_fold_factor(log2_coset, [&](auto k) -> int {
+        return coset_leaves_launch_a<decltype(k)::value>(fold, d_cw, cw_stride, q, d_nodes + q * 8, stream, not_mine, token);
+    }));
+    return merkle_inner_launch(d_nodes, tree_depth(q), q, stream, root_out, seq);
 }
 
 static std::atomic<u64> g_coset_trees_by_rows{0};     // how often a coset tree went through the interpreter (the tests ask)

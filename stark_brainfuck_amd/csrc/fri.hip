@@ -3,6 +3,10 @@
 // host, the Fiat-Shamir challenge from the transcript (host: pickle + SHAKE256, ip.py:21-22), the split-and-fold
 // step (GPU, fri.py:127-128); then index sampling (fri.py:62-86) and one batched gather of every revealed leaf and
 // authentication-path node.
+// Both halves plan first and run second.  fri_commit: plan_rounds checks the arguments, lays every round out in one block and names
+// the kernels of its tree (TreePath); the round loop is launch_round_tree, await_root, the transcript step, the next fold's constants.
+// fri_query: one list of openings in the reference's push order (Opening) gives the gather requests and, after the one gather
+// (gather_run, shared with the STARK openings and bfs_gather), the tuples and paths that are pushed.
 #include <algorithm>
 #include <chrono>
 #include <map>
@@ -41,14 +45,11 @@ constexpr u32 FRI_FOLD_GRID_MAX = 4096;       // workgroups of 256; longer codew
 static int fri_fold_launch(const FriFoldArgs& f, u64* out, u64 out_stride, hipStream_t stream) {
     u32 grid = (u32)((f.half + 255) / 256);
     if (grid > FRI_FOLD_GRID_MAX) grid = FRI_FOLD_GRID_MAX;
-    switch (f.log2_folding) {
-    case 1: hipLaunchKernelGGL(fri_fold_kernel<1>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
-    case 2: hipLaunchKernelGGL(fri_fold_kernel<2>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
-    case 3: hipLaunchKernelGGL(fri_fold_kernel<3>, dim3(grid), dim3(256), 0, stream, f, out, out_stride); break;
-    default: set_error("internal: fold by 2^%u", f.log2_folding); return BFS_ERR_BAD_ARG;
-    }
-    BFS_HIP(hipGetLastError());
-    return BFS_OK;
+    return with_fold_factor(f.log2_folding, [&](auto k) -> int {
+        hipLaunchKernelGGL(fri_fold_kernel<decltype(k)::value>, dim3(grid), dim3(256), 0, stream, f, out, out_stride);
+        BFS_HIP(hipGetLastError());
+        return BFS_OK;
+    });
 }
 
 // one request = `nwords` 64-bit words at base, base + stride, ...; requests and results live in pinned host memory that the
@@ -65,15 +66,40 @@ __global__ void gather_requests_kernel(const GatherReq* req, u32 count, u64* out
     }
 }
 
+// the gather sequence: the requests into a pinned area the GPU reads, one launch, the stream synchronised; *words = the `nwords` gathered
+// words, in a pinned area the GPU wrote (valid while the caller holds the two leases).  reqs is not empty.
+static int gather_run(const std::vector<GatherReq>& reqs, u64 nwords, hipStream_t stream, PinnedLease& req_area, PinnedLease& res_area, const u64** words) {
+    BFS_TRY(req_area.get(reqs.size() * sizeof(GatherReq)));
+    BFS_TRY(res_area.get(nwords * sizeof(u64)));
+    memcpy(req_area.host, reqs.data(), reqs.size() * sizeof(GatherReq));
+    hipLaunchKernelGGL(gather_requests_kernel, dim3((u32)((reqs.size() + 255) / 256)), dim3(256), 0, stream, (const GatherReq*)req_area.dev, (u32)reqs.size(),
+                       (u64*)res_area.dev);
+    BFS_HIP(hipGetLastError());
+    BFS_HIP(hipStreamSynchronize(stream));
+    *words = (const u64*)res_area.host;
+    return BFS_OK;
+}
+
 // wall-clock breakdown of the last bfs_fri_commit / bfs_fri_query on this thread (ms): see bfs_fri_last_timing
 static thread_local double g_fri_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 static inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// Which kernels build a round's tree.  plan_rounds decides it from the round's length and position; launch_round_tree acts on it.
+enum class TreePath : unsigned char {
+    Borrowed,       // round 0: the tree the caller has built over the input codeword (bfs_fri_session_round0_tree / _round0_coset_tree)
+    Coset,          // one leaf per folding coset (coset.hip); the leaf kernel makes the codeword on the way in rounds >= 1
+    OneLaunch,      // length <= FRI_FUSED_MAX: fold + leaves + subtrees in one launch (fri_round_quad_kernel)
+    FoldInLeaves,   // a longer round >= 1: the leaf kernel folds the previous round's codeword on the way
+    Codeword,       // a longer round 0: the tree over the codeword that is there (fri.py:108)
+    SingleElement,  // length 1: fold on its own, the leaf is the root, copied back without the mailbox
+};
 
 struct FriRound {
     const u64* cw = nullptr;  // limb-major codeword
     u64 stride = 0, length = 0;
     u64 leaves = 0;           // leaves of the round's tree: length, or length / a when the round commits one leaf per coset
     u64* nodes = nullptr;     // 2*leaves digests of 8 words
+    TreePath path = TreePath::Codeword;
     unsigned char root[64];
 };
 
@@ -148,15 +174,18 @@ struct FriSession {
     ~FriSession() { if (block) (void)device_release(block, block_stream); }
 };
 
+// Every round is at least 2 long when expansion >= 1: with h halvings, N >> h <= expansion < N >> (h - 1), and the last of the
+// R = (h - 1) / k + 1 rounds has length N >> k (R - 1) >= N >> (h - 1) > expansion >= 1.  Only expansion = 0 (h = log2 N + 1) ends on a
+// single element, when k divides log2 N: TreePath::SingleElement.
 static u32 fri_num_rounds(u64 length, u32 expansion, u32 k = 1) {  // fri.py:54-60; folding by 2^k: floor((that - 1) / k) folds, one codeword more
     u32 r = 0;
     while (length > expansion) { length /= 2; ++r; }
     return r == 0 ? 0 : (r - 1) / k + 1;
 }
 
-int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u32 log_n, u64 offset, u64 omega,
-               u32 expansion, hipStream_t stream) {
-    const double t_begin = now_ms();
+// (N, expansion, k, coset leaves, round-0 tree) -> S.rounds: the argument checks, one allocation for the nodes of every round and the
+// codewords of rounds >= 1, and per round its length, leaves, place in the block and tree path
+static int plan_rounds(FriSession& S, const u64* d_cw, u64 stride, u32 log_n, u64 omega, u32 expansion, hipStream_t stream) {
     const u64 N = 1ull << log_n;
     const u32 k = S.log2_folding;
     const u32 R = fri_num_rounds(N, expansion, k);
@@ -168,8 +197,6 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
     }
     S.log_n = log_n;
     S.rounds.assign(R, FriRound());
-    // one allocation: nodes of every round + codewords of rounds >= 1
-    size_t words = 0;
     const bool coset = S.coset_leaves;
     if (coset && R < 2) { set_error("cannot commit to cosets with less than one fold"); return BFS_ERR_BAD_ARG; }
     if (S.round0_nodes && S.round0_leaves != (coset ? N >> k : 0)) {
@@ -177,8 +204,20 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
                   (unsigned long long)(coset ? N >> k : N));
         return BFS_ERR_BAD_ARG;
     }
-    auto tree_leaves = [&](u32 r) { return (coset && r + 1 < R) ? N >> (k * (r + 1)) : N >> (k * r); };
-    for (u32 r = 0; r < R; ++r) words += (size_t)16 * tree_leaves(r) + (r ? (size_t)3 * (N >> (k * r)) : 0);
+    size_t words = 0;
+    for (u32 r = 0; r < R; ++r) {
+        FriRound& fr = S.rounds[r];
+        const bool coset_round = coset && r + 1 < R;
+        fr.length = N >> (k * r);
+        fr.leaves = coset_round ? fr.length >> k : fr.length;
+        fr.path = r == 0 && S.round0_nodes ? TreePath::Borrowed
+                  : coset_round            ? TreePath::Coset
+                  : fr.length < 2          ? TreePath::SingleElement
+                  : fr.length <= FRI_FUSED_MAX ? TreePath::OneLaunch
+                  : r >= 1                 ? TreePath::FoldInLeaves
+                                           : TreePath::Codeword;
+        words += (size_t)16 * fr.leaves + (r ? (size_t)3 * fr.length : 0);
+    }
     u64* p = nullptr;
     if (S.use_workspace) {
         void* w = nullptr;
@@ -190,22 +229,62 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
         S.block_stream = stream;
         p = (u64*)S.block;
     }
-    BFS_TRY(S.mailbox.init());
     for (u32 r = 0; r < R; ++r) {
         FriRound& fr = S.rounds[r];
-        fr.length = N >> (k * r);
-        fr.leaves = tree_leaves(r);
         fr.nodes = p; p += 16 * fr.leaves;
         if (r == 0) { fr.cw = d_cw; fr.stride = stride; }
         else { fr.cw = p; fr.stride = fr.length; p += 3 * fr.length; }
     }
+    return S.mailbox.init();
+}
+
+// The kernels of round r's tree.  fold: what makes the round's codeword out of the previous one's (fold.in == nullptr in round 0, whose
+// codeword is there); every path of a round >= 1 folds on the way.  *seq != 0 afterwards: the root comes through the mailbox under that
+// sequence number (await_root); 0: fr.root is set (Borrowed) or the caller copies it back (SingleElement).
+static int launch_round_tree(FriSession& S, u32 r, const FriFoldArgs& fold, hipStream_t stream, u64* seq) {
+    FriRound& fr = S.rounds[r];
+    const bool folds = fold.in != nullptr;
+    u64* const cw = (u64*)fr.cw;
+    u64* const box = S.mailbox.dev;
+    *seq = 0;
+    if (folds != (r >= 1)) { set_error("internal: round %u of the plan and its fold disagree", r); return BFS_ERR_BAD_ARG; }
+    switch (fr.path) {
+    case TreePath::Borrowed:
+        fr.nodes = (u64*)S.round0_nodes;          // the STARK prover has just committed to this very codeword (brainfuck_stark.py:301 / fri.py:108)
+        memcpy(fr.root, S.round0_root, 64);
+        return BFS_OK;
+    case TreePath::SingleElement:
+        if (folds) BFS_TRY(fri_fold_launch(fold, cw, fr.stride, stream));
+        return merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream);
+    case TreePath::Coset:
+        // the levels above the fr.leaves leaves and the root's way to the host are those of the per-element tree
+        *seq = ++S.mailbox.seq;
+        return coset_tree_launch(folds ? &fold : nullptr, cw, fr.stride, fr.leaves, S.log2_folding, fr.nodes, stream, box + 9, *seq, box, *seq);
+    case TreePath::OneLaunch:
+        *seq = ++S.mailbox.seq;
+        return fri_round_fused_launch(fold, cw, fr.stride, fr.length, fr.nodes, stream, box, *seq);
+    case TreePath::FoldInLeaves:
+        *seq = ++S.mailbox.seq;
+        return merkle_build_xfe_fold_launch(fold, cw, fr.stride, fr.length, fr.nodes, stream, box, *seq);
+    case TreePath::Codeword:
+        *seq = ++S.mailbox.seq;
+        return merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream, box, *seq);  // fri.py:108
+    }
+    set_error("internal: round %u has no tree path", r);
+    return BFS_ERR_BAD_ARG;
+}
+
+int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u32 log_n, u64 offset, u64 omega,
+               u32 expansion, hipStream_t stream) {
+    const double t_begin = now_ms();
+    BFS_TRY(plan_rounds(S, d_cw, stride, log_n, omega, expansion, stream));
+    const u32 k = S.log2_folding;
+    const u32 R = (u32)S.rounds.size();
     const u64 *winv_lo = nullptr, *winv_hi = nullptr;
     u32 lo_bits = 0;
     BFS_TRY(ntt_power_tables(gl_inv(omega), log_n, &winv_lo, &winv_hi, &lo_bits));
     u64 g = offset, w = omega;                     // offset and generator of round r's domain
-    constexpr u64 FRI_FOLD_IN_LEAVES_MIN = 16384;     // = FRI_FUSED_MAX: every round >= 1 folds inside its leaf kernel (must exceed QUAD_LEAVES_MAX)
-    FriFoldArgs pending{};                         // the fold that produces round r's codeword, when round r runs fused
-    pending.in = nullptr;
+    FriFoldArgs fold{};                            // the fold that produces round r's codeword; none in round 0
     // Fiat-Shamir look-ahead: with a long transcript in front (a STARK proof: tens of KB), helper threads absorb the SHAKE256 prefix of
     // every coming challenge now (Transcript::Lookahead); rounds 1 .. R-2 push a root and draw a challenge
     rp::Transcript::Lookahead look;
@@ -228,7 +307,6 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
         const double t_round = trace ? now_ms() : 0;
         double t_launched = 0, t_absorbed = 0, t_root = 0;
         rp::Transcript::Speculation speculation;
-        const bool coset_round = coset && r + 1 < R;
         // what follows every launch of a tree whose root comes through the mailbox.  The tree kernel writes the root straight into pinned
         // host memory; poll the sequence flag instead of paying a copy command + stream synchronisation per round.  While the GPU
         // hashes: the next challenge is SHAKE256 of the WHOLE transcript including this root (fri.py:112-120), tens of KB -- as long as
@@ -254,40 +332,16 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
             memcpy(fr.root, S.mailbox.host, 64);
             return BFS_OK;
         };
-        const bool fused = !coset_round && fr.length >= 2 && fr.length <= FRI_FUSED_MAX && !(r == 0 && S.round0_nodes);
-        if (coset_round && !(r == 0 && S.round0_nodes)) {
-            // one leaf per folding coset (coset.hip): the leaf kernel makes the codeword on the way (rounds >= 1), the levels above
-            // the fr.leaves leaves and the root's way to the host are those of the per-element tree
-            const u64 seq = ++S.mailbox.seq;
-            BFS_TRY(coset_tree_launch(pending.in != nullptr ? &pending : nullptr, (u64*)fr.cw, fr.stride, fr.leaves, k, fr.nodes, stream, S.mailbox.dev + 9, seq,
-                                      S.mailbox.dev, seq));
-            pending.in = nullptr;
+        u64 seq = 0;
+        BFS_TRY(launch_round_tree(S, r, fold, stream, &seq));
+        if (seq != 0) {
             BFS_TRY(await_root(seq));
-            if (__atomic_load_n(S.mailbox.host + 9, __ATOMIC_ACQUIRE) == seq) {
+            if (fr.path == TreePath::Coset && __atomic_load_n(S.mailbox.host + 9, __ATOMIC_ACQUIRE) == seq) {
                 // a tuple with an element that stores fewer than three coefficients: the zipped-row interpreter hashes the tree again
                 // (the codeword is in HBM by now) -- every other codeword than one lifted from the base field never comes here
                 BFS_TRY(coset_tree_rows(fr.cw, fr.stride, fr.leaves, k, fr.nodes, fr.root, stream));
             }
-        } else if (fused) {
-            // small codeword: fold (of the previous round) + leaves + subtrees in one launch, root through the mailbox
-            const u64 seq = ++S.mailbox.seq;
-            BFS_TRY(fri_round_fused_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
-            pending.in = nullptr;
-            BFS_TRY(await_root(seq));
-        } else if (r == 0 && S.round0_nodes) {
-            fr.nodes = (u64*)S.round0_nodes;          // the STARK prover has just committed to this very codeword (brainfuck_stark.py:301 / fri.py:108)
-            memcpy(fr.root, S.round0_root, 64);
-        } else if (fr.length >= 2) {
-            const u64 seq = ++S.mailbox.seq;
-            if (pending.in != nullptr) {               // the leaf kernel folds the previous round's codeword on the way
-                BFS_TRY(merkle_build_xfe_fold_launch(pending, (u64*)fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));
-                pending.in = nullptr;
-            } else {
-                BFS_TRY(merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream, S.mailbox.dev, seq));  // fri.py:108
-            }
-            BFS_TRY(await_root(seq));
-        } else {
-            BFS_TRY(merkle_build_xfe_launch(fr.cw, fr.stride, fr.length, fr.nodes, stream));
+        } else if (fr.path == TreePath::SingleElement) {
             if (r >= 1) begin_lookahead();
             BFS_HIP(hipMemcpyAsync(fr.root, fr.nodes + 8, 64, hipMemcpyDeviceToHost, stream));
             BFS_HIP(hipStreamSynchronize(stream));
@@ -301,19 +355,10 @@ int fri_commit(FriSession& S, rp::Transcript& ps, const u64* d_cw, u64 stride, u
                     1e3 * (t_launched - t_round), 1e3 * (t_absorbed - t_launched), 1e3 * (t_root - t_absorbed), 1e3 * (now_ms() - t_root));
         if (r == R - 1) break;                                                // fri.py:116-117
         if (!speculating && !have_seed) ps.fiat_shamir(ps.objects.size(), seed, 32);   // fri.py:120
-        Xfe alpha = rp::sample_xfe(seed, 32);
-        FriRound& nx = S.rounds[r + 1];
-        FriFoldArgs fold{};
+        // the next round folds while it builds its tree
         fold.in = fr.cw; fold.in_stride = fr.stride;
         fold.winv_lo = winv_lo; fold.winv_hi = winv_hi; fold.lo_bits = lo_bits; fold.round_shift = k * r;
-        fri_fold_constants(fold, k, fr.length, alpha, g, w);
-        const u64 half = fold.half;                       // = nx.length
-        if (half >= 2 && (half <= FRI_FUSED_MAX || half > FRI_FOLD_IN_LEAVES_MIN)) {
-            // the next round folds while it builds its tree (fri_round_quad_kernel, or merkle_leaves_xfe_fold_kernel for large rounds)
-            pending = fold;
-        } else {
-            BFS_TRY(fri_fold_launch(fold, (u64*)nx.cw, nx.stride, stream));
-        }
+        fri_fold_constants(fold, k, fr.length, rp::sample_xfe(seed, 32), g, w);
         for (u32 j = 0; j < k; ++j) { g = gl_sqr(g); w = gl_sqr(w); }  // fri.py:130-131, once per step (the kernels square omega through round_shift)
     }
     g_fri_timing[0] = now_ms() - t_begin;   // rounds: trees, roots, challenges, folds
@@ -395,14 +440,6 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
     BFS_TRY(sample_indices(seed, S.rounds[1].length, S.rounds[R - 1].length, t, top));  // fri.py:186-187
     for (u32 s = 0; s < t; ++s) h_top[s] = top[s];
 
-    // plan every opening first (fri.py:191-197), then fetch everything with one gather
-    std::vector<std::vector<u64>> layer_idx;  // c indices per layer
-    std::vector<u64> idx = top;
-    for (u32 i = 0; i + 1 < R; ++i) {  // len(trees) - 1 = R - 2 layers use query(), the last one query_last()
-        for (auto& x : idx) x %= S.rounds[i + 1].length;      // = len(round i) / folding factor
-        layer_idx.push_back(idx);
-    }
-
     g_fri_timing[2] = now_ms() - t_begin;   // Fiat-Shamir + index sampling
     typedef FriSession::Key Key;
     const u32 fan = 1u << S.log2_folding;         // elements of round i that one element of round i + 1 depends on
@@ -413,7 +450,33 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
         S.elements.reserve(S.elements.vals.size() + (size_t)(fan + 1) * t * R + 8);
         S.nodes.reserve((size_t)(fan + 1) * t * depth_sum / 2 + 64);
     }
-    std::vector<GatherReq> reqs;                 // what to fetch
+    // every opening, once, in the reference's push order (fri.py:147-156, 166-174): per layer the t tuples -- the fan elements of round i
+    // and, unless a leaf is a whole coset, the one of round i + 1 they fold to -- then per test the authentication paths.  The gather
+    // requests below and the pushes at the end both come from this list.  (R - 2 layers are query(), the last one query_last(): the
+    // last codeword is in the proof, so nothing of it gets a path)
+    struct Opening {
+        enum Kind : u32 { Element, TupleEnd /* an element that closes its tuple */, Path } kind;
+        u32 round;
+        u64 index;
+    };
+    std::vector<Opening> plan;
+    plan.reserve((size_t)2 * (fan + 1) * t * (R - 1));
+    for (u32 i = 0; i + 1 < R; ++i) {
+        const u64 q = S.rounds[i + 1].length;      // = len(round i) / folding factor
+        for (u32 s = 0; s < t; ++s) {
+            const u64 c = top[s] % q;
+            for (u32 m = 0; m < fan; ++m) plan.push_back({Opening::Element, i, c + m * q});
+            if (!coset) plan.push_back({Opening::Element, i + 1, c});
+            plan.back().kind = Opening::TupleEnd;
+        }
+        for (u32 s = 0; s < t; ++s) {
+            const u64 c = top[s] % q;
+            if (coset) { plan.push_back({Opening::Path, i, c}); continue; }
+            for (u32 m = 0; m < fan; ++m) plan.push_back({Opening::Path, i, c + m * q});
+            if (i + 2 < R) plan.push_back({Opening::Path, i + 1, c});
+        }
+    }
+    std::vector<GatherReq> reqs;                // what to fetch
     std::vector<std::pair<int, Key>> order;      // what the fetched words are: (0 = element | 1 = tree node, key)
     reqs.reserve(4096); order.reserve(4096);
     u64 nwords = 0;
@@ -437,33 +500,15 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
             nwords += 8;
         }
     };
-    for (u32 i = 0; i < (u32)layer_idx.size(); ++i) {
-        const bool lastq = (i + 1 == layer_idx.size());
-        const u32 cur = lastq ? R - 2 : i;
-        const u64 q = S.rounds[cur + 1].length;
-        for (u32 s = 0; s < t; ++s) {
-            u64 c = layer_idx[i][s];
-            for (u32 m = 0; m < fan; ++m) need_element(cur, c + m * q);
-            if (coset) { need_path(cur, c); continue; }
-            need_element(cur + 1, c);
-            for (u32 m = 0; m < fan; ++m) need_path(cur, c + m * q);
-            if (!lastq) need_path(cur + 1, c);
-        }
+    for (const Opening& o : plan) {
+        if (o.kind == Opening::Path) need_path(o.round, o.index);
+        else need_element(o.round, o.index);
     }
     g_fri_timing[3] = now_ms() - t_begin - g_fri_timing[2];   // planning the openings
     const double t_gather = now_ms();
     const u64* words = nullptr;
     PinnedLease req_area, res_area;
-    if (!reqs.empty()) {
-        BFS_TRY(req_area.get(reqs.size() * sizeof(GatherReq)));
-        BFS_TRY(res_area.get(nwords * sizeof(u64)));
-        memcpy(req_area.host, reqs.data(), reqs.size() * sizeof(GatherReq));
-        u32 grid = (u32)((reqs.size() + 255) / 256);
-        hipLaunchKernelGGL(gather_requests_kernel, dim3(grid), dim3(256), 0, stream, (const GatherReq*)req_area.dev, (u32)reqs.size(), (u64*)res_area.dev);
-        BFS_HIP(hipGetLastError());
-        BFS_HIP(hipStreamSynchronize(stream));
-        words = (const u64*)res_area.host;
-    }
+    if (!reqs.empty()) BFS_TRY(gather_run(reqs, nwords, stream, req_area, res_area, &words));
     g_fri_timing[4] = now_ms() - t_gather;   // gather kernel + synchronisation
     const double t_build = now_ms();
     size_t pos = 0;
@@ -484,24 +529,12 @@ int fri_query(FriSession& S, rp::Transcript& ps, u32 t, u64* h_top, hipStream_t 
         return rp::mk_list(std::move(items));
     };
     // push in the reference's order: per layer, t leaf triples then the authentication paths (fri.py:147-156, 166-174)
-    for (u32 i = 0; i < (u32)layer_idx.size(); ++i) {
-        const bool lastq = (i + 1 == layer_idx.size());
-        const u32 cur = lastq ? R - 2 : i;
-        const u64 q = S.rounds[cur + 1].length;
-        for (u32 s = 0; s < t; ++s) {
-            u64 c = layer_idx[i][s];
-            std::vector<rp::Ref> items;
-            items.reserve(fan + 1);
-            for (u32 m = 0; m < fan; ++m) items.push_back(S.elements[Key(cur, c + m * q)]);
-            if (!coset) items.push_back(S.elements[Key(cur + 1, c)]);
-            ps.objects.push_back(rp::mk_tuple(std::move(items)));
-        }
-        for (u32 s = 0; s < t; ++s) {
-            u64 c = layer_idx[i][s];
-            if (coset) { ps.objects.push_back(path_obj(cur, c)); continue; }
-            for (u32 m = 0; m < fan; ++m) ps.objects.push_back(path_obj(cur, c + m * q));
-            if (!lastq) ps.objects.push_back(path_obj(cur + 1, c));
-        }
+    std::vector<rp::Ref> items;
+    items.reserve(fan + 1);
+    for (const Opening& o : plan) {
+        if (o.kind == Opening::Path) { ps.objects.push_back(path_obj(o.round, o.index)); continue; }
+        items.push_back(S.elements[Key(o.round, o.index)]);
+        if (o.kind == Opening::TupleEnd) { ps.objects.push_back(rp::mk_tuple(items)); items.clear(); }
     }
     g_fri_timing[5] = now_ms() - t_build;   // building the transcript objects
     return BFS_OK;
@@ -549,27 +582,32 @@ int bfs_fri_session_set_grinding(void* session, uint32_t bits, uint64_t window) 
     return BFS_OK;
 }
 
-int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
-                  uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream) {
-    return bfs_fri_prove_folded(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, 1, num_colinearity_tests, h_top_level_indices, stream);
-}
-
-int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
-                         uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
-                         void* stream) {
-    return bfs_fri_prove_cosets(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, log2_folding, 0, num_colinearity_tests,
-                                h_top_level_indices, stream);
-}
-
-int bfs_fri_prove_cosets(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
-                         uint32_t expansion_factor, uint32_t log2_folding, int coset_leaves, uint32_t num_colinearity_tests,
-                         uint64_t* h_top_level_indices, void* stream) {
+static int fri_prove_run(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega, uint32_t expansion_factor,
+                         uint32_t log2_folding, int coset_leaves, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream) {
     FriSession S;
     S.use_workspace = true;
     BFS_TRY(bfs_fri_session_set_folding(&S, log2_folding));
     BFS_TRY(bfs_fri_session_set_coset_leaves(&S, coset_leaves));
     BFS_TRY(fri_commit(S, *(rp::Transcript*)ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, (hipStream_t)stream));
     return fri_query(S, *(rp::Transcript*)ps, num_colinearity_tests, h_top_level_indices, (hipStream_t)stream);
+}
+
+int bfs_fri_prove(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                  uint32_t expansion_factor, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices, void* stream) {
+    return fri_prove_run(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, 1, 0, num_colinearity_tests, h_top_level_indices, stream);
+}
+
+int bfs_fri_prove_folded(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, uint32_t num_colinearity_tests, uint64_t* h_top_level_indices,
+                         void* stream) {
+    return fri_prove_run(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, log2_folding, 0, num_colinearity_tests, h_top_level_indices, stream);
+}
+
+int bfs_fri_prove_cosets(void* ps, const uint64_t* d_codeword, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                         uint32_t expansion_factor, uint32_t log2_folding, int coset_leaves, uint32_t num_colinearity_tests,
+                         uint64_t* h_top_level_indices, void* stream) {
+    return fri_prove_run(ps, d_codeword, limb_stride, log_n, offset, omega, expansion_factor, log2_folding, coset_leaves, num_colinearity_tests,
+                         h_top_level_indices, stream);
 }
 
 // The openings of BrainfuckStark.prove (brainfuck_stark.py:315-333) written into the transcript without a Python object in between:
@@ -639,14 +677,8 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
         want_path(2, uniq_idx[a]);
     }
     PinnedLease req_area, res_area;
-    BFS_TRY(req_area.get(reqs.size() * sizeof(GatherReq)));
-    BFS_TRY(res_area.get(nwords * sizeof(u64)));
-    memcpy(req_area.host, reqs.data(), reqs.size() * sizeof(GatherReq));
-    hipLaunchKernelGGL(gather_requests_kernel, dim3((u32)((reqs.size() + 255) / 256)), dim3(256), 0, stream, (const GatherReq*)req_area.dev, (u32)reqs.size(),
-                       (u64*)res_area.dev);
-    BFS_HIP(hipGetLastError());
-    BFS_HIP(hipStreamSynchronize(stream));
-    const u64* words = (const u64*)res_area.host;
+    const u64* words = nullptr;
+    BFS_TRY(gather_run(reqs, nwords, stream, req_area, res_area, &words));
     // ---- objects
     std::vector<rp::Ref> node_obj(node_list.size());
     for (size_t k = 0; k < node_list.size(); ++k) node_obj[k] = rp::mk_bytes(words + node_off[k], 64);
@@ -719,31 +751,27 @@ int bfs_gather(const bfs_gather_request* requests, uint32_t count, uint64_t* h_o
         nwords += requests[i].nwords;
     }
     PinnedLease req_area, res_area;
-    BFS_TRY(req_area.get(reqs.size() * sizeof(GatherReq)));
-    BFS_TRY(res_area.get(nwords * sizeof(u64)));
-    memcpy(req_area.host, reqs.data(), reqs.size() * sizeof(GatherReq));
-    hipLaunchKernelGGL(gather_requests_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, (const GatherReq*)req_area.dev, count, (u64*)res_area.dev);
-    BFS_HIP(hipGetLastError());
-    BFS_HIP(hipStreamSynchronize(stream));
-    memcpy(h_out, res_area.host, nwords * sizeof(u64));
+    const u64* words = nullptr;
+    BFS_TRY(gather_run(reqs, nwords, stream, req_area, res_area, &words));
+    memcpy(h_out, words, nwords * sizeof(u64));
+    return BFS_OK;
+}
+
+// leaves: 0 for a tree over single elements (as many leaves as the codeword is long), else the leaves of a coset tree
+static int session_round0_tree(FriSession* S, const uint8_t* d_nodes, uint64_t leaves, const uint8_t h_root[64]) {
+    S->round0_nodes = (const u64*)d_nodes;
+    S->round0_leaves = leaves;
+    memcpy(S->round0_root, h_root, 64);
     return BFS_OK;
 }
 
 int bfs_fri_session_round0_tree(void* session, const uint8_t* d_nodes, const uint8_t h_root[64]) {
-    FriSession* S = (FriSession*)session;
-    S->round0_nodes = (const u64*)d_nodes;
-    S->round0_leaves = 0;
-    memcpy(S->round0_root, h_root, 64);
-    return BFS_OK;
+    return session_round0_tree((FriSession*)session, d_nodes, 0, h_root);
 }
 
 int bfs_fri_session_round0_coset_tree(void* session, const uint8_t* d_nodes, uint64_t num_leaves, const uint8_t h_root[64]) {
-    FriSession* S = (FriSession*)session;
     if (num_leaves == 0 || (num_leaves & (num_leaves - 1))) { set_error("bfs_fri_session_round0_coset_tree: %llu leaves", (unsigned long long)num_leaves); return BFS_ERR_BAD_ARG; }
-    S->round0_nodes = (const u64*)d_nodes;
-    S->round0_leaves = num_leaves;
-    memcpy(S->round0_root, h_root, 64);
-    return BFS_OK;
+    return session_round0_tree((FriSession*)session, d_nodes, num_leaves, h_root);
 }
 
 int bfs_fri_session_alias(void* session, void* ps, uint32_t round, uint64_t index, uint64_t element_handle) {
@@ -776,28 +804,10 @@ uint64_t bfs_fri_session_round_leaves(void* session, uint32_t r) {
     return r < S->rounds.size() ? S->rounds[r].leaves : 0;
 }
 
-int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, const uint64_t alpha[3],
-                 uint64_t offset, uint64_t omega, void* stream) {
+// what bfs_xfe_fold and bfs_xfe_fold_multi share once each has checked its own arguments: the order of omega, the constants, the launch
+static int xfe_fold_run(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, uint32_t log2_folding,
+                        const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream) {
     const u64 N = 1ull << log_n;
-    if (log_n == 0) { set_error("cannot fold a codeword of length 1"); return BFS_ERR_BAD_ARG; }
-    if (gl_pow(omega, N) != 1 || gl_pow(omega, N / 2) == 1) { set_error("error in commit: omega does not have the right order!"); return BFS_ERR_NOT_ROOT; }
-    const u64 *lo = nullptr, *hi = nullptr;
-    u32 lo_bits = 0;
-    BFS_TRY(ntt_power_tables(gl_inv(omega), log_n, &lo, &hi, &lo_bits));
-    Xfe a{{alpha[0] % GL_P, alpha[1] % GL_P, alpha[2] % GL_P}};
-    FriFoldArgs f{};
-    f.in = d_in; f.in_stride = in_stride;
-    f.winv_lo = lo; f.winv_hi = hi; f.lo_bits = lo_bits; f.round_shift = 0;
-    fri_fold_constants(f, 1, N, a, offset % GL_P, omega);
-    return fri_fold_launch(f, d_out, out_stride, (hipStream_t)stream);
-}
-
-int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, uint32_t log2_folding,
-                       const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream) {
-    const u64 N = 1ull << log_n;
-    if (log2_folding < 1 || log2_folding > 3) { set_error("bfs_xfe_fold_multi: log2_folding must be 1, 2 or 3 (got %u)", log2_folding); return BFS_ERR_BAD_ARG; }
-    if (log_n < log2_folding || log_n > 32) { set_error("cannot fold a codeword of length 2^%u by %u", log_n, 1u << log2_folding); return BFS_ERR_BAD_ARG; }
-    if (in_stride < N || out_stride < (N >> log2_folding)) { set_error("bfs_xfe_fold_multi: a limb stride is shorter than its codeword"); return BFS_ERR_BAD_ARG; }
     if (gl_pow(omega, N) != 1 || gl_pow(omega, N / 2) == 1) { set_error("error in commit: omega does not have the right order!"); return BFS_ERR_NOT_ROOT; }
     const u64 *lo = nullptr, *hi = nullptr;
     u32 lo_bits = 0;
@@ -808,6 +818,21 @@ int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out
     f.winv_lo = lo; f.winv_hi = hi; f.lo_bits = lo_bits; f.round_shift = 0;
     fri_fold_constants(f, log2_folding, N, a, offset % GL_P, omega);
     return fri_fold_launch(f, d_out, out_stride, (hipStream_t)stream);
+}
+
+int bfs_xfe_fold(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, const uint64_t alpha[3],
+                 uint64_t offset, uint64_t omega, void* stream) {
+    if (log_n == 0) { set_error("cannot fold a codeword of length 1"); return BFS_ERR_BAD_ARG; }
+    return xfe_fold_run(d_in, in_stride, d_out, out_stride, log_n, 1, alpha, offset, omega, stream);
+}
+
+int bfs_xfe_fold_multi(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_n, uint32_t log2_folding,
+                       const uint64_t alpha[3], uint64_t offset, uint64_t omega, void* stream) {
+    const u64 N = 1ull << log_n;
+    if (log2_folding < 1 || log2_folding > 3) { set_error("bfs_xfe_fold_multi: log2_folding must be 1, 2 or 3 (got %u)", log2_folding); return BFS_ERR_BAD_ARG; }
+    if (log_n < log2_folding || log_n > 32) { set_error("cannot fold a codeword of length 2^%u by %u", log_n, 1u << log2_folding); return BFS_ERR_BAD_ARG; }
+    if (in_stride < N || out_stride < (N >> log2_folding)) { set_error("bfs_xfe_fold_multi: a limb stride is shorter than its codeword"); return BFS_ERR_BAD_ARG; }
+    return xfe_fold_run(d_in, in_stride, d_out, out_stride, log_n, log2_folding, alpha, offset, omega, stream);
 }
 
 }  // extern "C"

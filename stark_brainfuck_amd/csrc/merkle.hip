@@ -1,7 +1,8 @@
 // merkle.hip -- BLAKE2b-512 Merkle trees on gfx950.  Replaces Merkle.__init__ of the reference
 // (/root/reference/code/merkle.py:8-41): leaf hashing `blake2b(pickle.dumps(leaf))` (:29-32) and the level-by-level
 // parent hashing (:35-41).  One thread hashes one leaf (preimage synthesised in LDS, <= 4 compressions) or one
-// parent (one compression); the top 9 levels run in a single workgroup.
+// parent (one compression); the top 9 levels run in a single workgroup.  The latency-oriented kernels put four lanes on a hash; their
+// shared device blocks exist once: xfe_leaf_quad (the four-lane leaf) and quad_parent (one step of the level loops that run in LDS).
 #include "blake2b_quad.hpp"
 #include "merkle_core.hpp"
 #include <vector>
@@ -28,18 +29,23 @@ __device__ __forceinline__ void xfe_leaves_wave(u64 c0, u64 c1, u64 c2, bool act
     if (__ballot(k == 1) != 0) { if (k == 1) merkle_leaf_xfe_stream<1>(c0, c1, c2, stage + lane, LEAF_THREADS, h, midstates); }
 }
 
-__global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_xfe_kernel(const u64* limbs, u64 limb_stride, u64 n, u64* leaf_digests, const u64* midstates) {
-    __shared__ u64 stage[LEAF_STAGE_WORDS];
-    const u64 i = (u64)blockIdx.x * LEAF_THREADS + threadIdx.x;
-    const bool active = i < n;
-    u64 c0 = 0, c1 = 0, c2 = 0;
-    if (active) { c0 = limbs[i]; c1 = limbs[limb_stride + i]; c2 = limbs[2 * limb_stride + i]; }
+// the body of the two scalar leaf kernels below, which differ only in where the three limbs come from: hash, then store leaf i's digest
+__device__ __forceinline__ void xfe_leaves_wave_store(u64 c0, u64 c1, u64 c2, bool active, u64* stage, u64* leaf_digests, u64 i, const u64* midstates) {
     u64 d[8];
     xfe_leaves_wave(c0, c1, c2, active, stage, d, midstates);
     if (!active) return;
     u64* out = leaf_digests + i * 8;
 #pragma unroll
     for (int j = 0; j < 8; ++j) out[j] = d[j];
+}
+
+__global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_xfe_kernel(const u64* limbs, u64 limb_stride, u64 n, u64* leaf_digests, const u64* midstates) {
+    __shared__ u64 stage[LEAF_STAGE_WORDS];
+    const u64 i = (u64)blockIdx.x * LEAF_THREADS + threadIdx.x;
+    const bool active = i < n;
+    u64 c0 = 0, c1 = 0, c2 = 0;
+    if (active) { c0 = limbs[i]; c1 = limbs[limb_stride + i]; c2 = limbs[2 * limb_stride + i]; }
+    xfe_leaves_wave_store(c0, c1, c2, active, stage, leaf_digests, i, midstates);
 }
 
 // the same for a FRI round whose codeword does not exist yet: every thread first PRODUCES its element (the split-and-fold step of the
@@ -60,12 +66,7 @@ __global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_xfe_fold_kernel(Fr
         cw[cw_stride + i] = c1;
         cw[2 * cw_stride + i] = c2;
     }
-    u64 d[8];
-    xfe_leaves_wave(c0, c1, c2, active, stage, d, midstates);
-    if (!active) return;
-    u64* out = leaf_digests + i * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[j] = d[j];
+    xfe_leaves_wave_store(c0, c1, c2, active, stage, leaf_digests, i, midstates);
 }
 
 __global__ void __launch_bounds__(LEAF_THREADS) merkle_leaves_bfe_kernel(const u64* values, u64 n, u64* leaf_digests) {
@@ -164,6 +165,51 @@ __global__ void __launch_bounds__(256) merkle_parents_quad_kernel(u64* nodes, u6
 #endif
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// one step of the "levels in LDS, one quad per parent" loops below, in two halves so that the addresses of the second are worked out
+// behind the hash (ahead of it they cost two registers).  quad_parent: the quad hashes the two children at m (16 words, of which
+// `bytes` bytes count); quad_parent_store: lane j of it puts its two digest words into the LDS level at `dst` (8 words) and into the
+// tree at `g`.  hl, hh stay with the caller: a root goes to the mailbox as well.
+__device__ __forceinline__ void quad_parent(const QuadLane& ql, const u64* m, u64 bytes, u64& hl, u64& hh) {
+    blake2b_init_quad(ql, hl, hh);
+    blake2b_compress_quad(ql, hl, hh, m, bytes, true);
+}
+__device__ __forceinline__ void quad_parent_store(u32 j, u64 hl, u64 hh, u64* dst, u64* g) {
+    dst[j] = hl;
+    dst[4 + j] = hh;
+    g[j] = hl;
+    g[4 + j] = hh;
+}
+
+constexpr int QUAD_LEAF_WORDS = 48;                  // 3 blocks of 16 words per leaf (bytes 128..409)
+
+// the four-lane leaf: blake2b(pickle.dumps(element c0, c1, c2)) by one quad, lane j of it ending with digest words j and 4 + j.  Block 0
+// is a midstate; lane 0 assembles the rest of the preimage in m (QUAD_LEAF_WORDS words of LDS), the four lanes hash it.
+__device__ __forceinline__ void xfe_leaf_quad(u64 c0, u64 c1, u64 c2, u64* m, const QuadLane& ql, u32 j, const u64* midstates, u64& hl, u64& hh) {
+    const u32 k = xfe_leaf_k(c0, c1, c2);
+    if (k == 0) {
+        hl = midstates[(size_t)2 * LEAF_MS_LEN * 8 + j];
+        hh = midstates[(size_t)2 * LEAF_MS_LEN * 8 + 4 + j];
+    } else {
+        const u32 body = xfe_leaf_body_len(k, c0, c1, c2), total = body + 11;
+        const u32 nblk = (total + 127) / 128;
+        const u64* ms = midstates + ((size_t)(k == 1 ? 0 : 1) * LEAF_MS_LEN + body) * 8;
+        hl = ms[j];
+        hh = ms[4 + j];
+        if (j == 0) {
+            LeafWriter w;
+            w.init(m, 1);
+            encode_xfe_leaf_tail(w, k, c0, c1, c2);
+            for (u32 x = w.wpos; x < (nblk - 1) * 16; ++x) m[x] = 0;   // zero padding of the final block
+        }
+        for (u32 b = 1; b < nblk; ++b) {
+            const bool last = b + 1 == nblk;
+            blake2b_compress_quad(ql, hl, hh, m + 16 * (b - 1), last ? (u64)total : (u64)(b + 1) * 128, last);
+        }
+    }
+}
+#endif
+
 // top of the tree (levels of width <= 256 down to the root) in one 1024-thread workgroup, one quad per parent,
 // ping-pong level buffers in LDS
 __global__ void __launch_bounds__(1024) merkle_top_quad_kernel(u64* nodes, u32 width, u64 present_children, u64* root_out, u64 seq) {
@@ -187,13 +233,8 @@ __global__ void __launch_bounds__(1024) merkle_top_quad_kernel(u64* nodes, u32 w
                 for (int wd = 0; wd < 4; ++wd) { const int idx = 4 * j + wd; if (idx >= 8 * pr) m[idx] = 0; }
             }
             u64 hl, hh;
-            blake2b_init_quad(ql, hl, hh);
-            blake2b_compress_quad(ql, hl, hh, m, (u64)(64 * pr + 32 * (2 - pr)), true);
-            dst[q * 8 + j] = hl;
-            dst[q * 8 + 4 + j] = hh;
-            u64* g = nodes + ((u64)w + q) * 8;
-            g[j] = hl;
-            g[4 + j] = hh;
+            quad_parent(ql, m, (u64)(64 * pr + 32 * (2 - pr)), hl, hh);
+            quad_parent_store(j, hl, hh, dst + q * 8, nodes + ((u64)w + q) * 8);
             if (w == 1 && root_out != nullptr) {
                 __hip_atomic_store(root_out + j, hl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(root_out + 4 + j, hh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -229,13 +270,8 @@ __global__ void __launch_bounds__(1024) merkle_subtree_quad_kernel(u64* nodes, u
     for (u32 w = 256; w >= 1; w >>= 1, level >>= 1) {
         if (q < w) {
             u64 hl, hh;
-            blake2b_init_quad(ql, hl, hh);
-            blake2b_compress_quad(ql, hl, hh, src + q * 16, 128, true);
-            dst[q * 8 + j] = hl;
-            dst[q * 8 + 4 + j] = hh;
-            u64* g = nodes + (level + (u64)blockIdx.x * w + q) * 8;
-            g[j] = hl;
-            g[4 + j] = hh;
+            quad_parent(ql, src + q * 16, 128, hl, hh);
+            quad_parent_store(j, hl, hh, dst + q * 8, nodes + (level + (u64)blockIdx.x * w + q) * 8);
         }
         __syncthreads();
         u64* tmp = src; src = dst; dst = tmp;
@@ -247,36 +283,15 @@ __global__ void __launch_bounds__(1024) merkle_subtree_quad_kernel(u64* nodes, u
 // the four lanes hash it
 __global__ void __launch_bounds__(256) merkle_leaves_xfe_quad_kernel(const u64* limbs, u64 limb_stride, u64 n, u64* leaf_digests, const u64* midstates) {
 #if defined(__HIP_DEVICE_COMPILE__)   // DPP builtins exist only in the device pass
-    constexpr int WORDS = 48;                        // 3 blocks of 16 words per leaf (bytes 128..409)
-    __shared__ u64 stage[64 * WORDS];
+    __shared__ u64 stage[64 * QUAD_LEAF_WORDS];
     const u32 q = threadIdx.x >> 2, j = threadIdx.x & 3;
     const u64 i = (u64)blockIdx.x * 64 + q;
     const QuadLane ql = quad_lane(threadIdx.x);
     if (i >= n) return;
-    u64* m = stage + q * WORDS;
+    u64* m = stage + q * QUAD_LEAF_WORDS;
     const u64 c0 = limbs[i], c1 = limbs[limb_stride + i], c2 = limbs[2 * limb_stride + i];
-    const u32 k = xfe_leaf_k(c0, c1, c2);
     u64 hl, hh;
-    if (k == 0) {
-        hl = midstates[(size_t)2 * LEAF_MS_LEN * 8 + j];
-        hh = midstates[(size_t)2 * LEAF_MS_LEN * 8 + 4 + j];
-    } else {
-        const u32 body = xfe_leaf_body_len(k, c0, c1, c2), total = body + 11;
-        const u32 nblk = (total + 127) / 128;
-        const u64* ms = midstates + ((size_t)(k == 1 ? 0 : 1) * LEAF_MS_LEN + body) * 8;
-        hl = ms[j];
-        hh = ms[4 + j];
-        if (j == 0) {
-            LeafWriter w;
-            w.init(m, 1);
-            encode_xfe_leaf_tail(w, k, c0, c1, c2);
-            for (u32 x = w.wpos; x < (nblk - 1) * 16; ++x) m[x] = 0;   // zero padding of the final block
-        }
-        for (u32 b = 1; b < nblk; ++b) {
-            const bool last = b + 1 == nblk;
-            blake2b_compress_quad(ql, hl, hh, m + 16 * (b - 1), last ? (u64)total : (u64)(b + 1) * 128, last);
-        }
-    }
+    xfe_leaf_quad(c0, c1, c2, m, ql, j, midstates, hl, hh);
     leaf_digests[i * 8 + j] = hl;
     leaf_digests[i * 8 + 4 + j] = hh;
 #endif
@@ -299,8 +314,7 @@ template <int K>      // the fold that produces the codeword is by 2^K
 __global__ void __launch_bounds__(4 * FRI_WG_LEAVES) fri_round_quad_kernel(FriFoldArgs f, u64* cw, u64 cw_stride, u64 n, u64* nodes, const u64* midstates,
                                                               u64* root_out, u64 seq) {
 #if defined(__HIP_DEVICE_COMPILE__)   // DPP builtins exist only in the device pass
-    constexpr int WORDS = 48;                        // 3 blocks of 16 words per leaf (bytes 128..409)
-    __shared__ u64 stage[FRI_WG_LEAVES * WORDS];
+    __shared__ u64 stage[FRI_WG_LEAVES * QUAD_LEAF_WORDS];
     __shared__ u64 bufA[FRI_WG_LEAVES * 8];
     __shared__ u64 bufB[FRI_WG_LEAVES * 4];
     __shared__ u64 limbs[3 * FRI_WG_LEAVES];
@@ -323,30 +337,10 @@ __global__ void __launch_bounds__(4 * FRI_WG_LEAVES) fri_round_quad_kernel(FriFo
     __syncthreads();
     // leaf digests: one quad per leaf (as merkle_leaves_xfe_quad_kernel)
     if (q < local) {
-        u64* m = stage + q * WORDS;
+        u64* m = stage + q * QUAD_LEAF_WORDS;
         const u64 c0 = limbs[q], c1 = limbs[FRI_WG_LEAVES + q], c2 = limbs[2 * FRI_WG_LEAVES + q];
-        const u32 k = xfe_leaf_k(c0, c1, c2);
         u64 hl, hh;
-        if (k == 0) {
-            hl = midstates[(size_t)2 * LEAF_MS_LEN * 8 + j];
-            hh = midstates[(size_t)2 * LEAF_MS_LEN * 8 + 4 + j];
-        } else {
-            const u32 body = xfe_leaf_body_len(k, c0, c1, c2), total = body + 11;
-            const u32 nblk = (total + 127) / 128;
-            const u64* ms = midstates + ((size_t)(k == 1 ? 0 : 1) * LEAF_MS_LEN + body) * 8;
-            hl = ms[j];
-            hh = ms[4 + j];
-            if (j == 0) {
-                LeafWriter w;
-                w.init(m, 1);
-                encode_xfe_leaf_tail(w, k, c0, c1, c2);
-                for (u32 x = w.wpos; x < (nblk - 1) * 16; ++x) m[x] = 0;   // zero padding of the final block
-            }
-            for (u32 b = 1; b < nblk; ++b) {
-                const bool last = b + 1 == nblk;
-                blake2b_compress_quad(ql, hl, hh, m + 16 * (b - 1), last ? (u64)total : (u64)(b + 1) * 128, last);
-            }
-        }
+        xfe_leaf_quad(c0, c1, c2, m, ql, j, midstates, hl, hh);
         u64* g = nodes + (n + first + q) * 8;        // leaf i sits at heap index npo2 + i, npo2 = n
         g[j] = hl; g[4 + j] = hh;
         bufA[q * 8 + j] = hl; bufA[q * 8 + 4 + j] = hh;
@@ -360,11 +354,8 @@ __global__ void __launch_bounds__(4 * FRI_WG_LEAVES) fri_round_quad_kernel(FriFo
     for (u32 w = local >> 1; w >= 1; w >>= 1) {
         if (q < w) {
             u64 hl, hh;
-            blake2b_init_quad(ql, hl, hh);
-            blake2b_compress_quad(ql, hl, hh, src + q * 16, 128, true);
-            dst[q * 8 + j] = hl; dst[q * 8 + 4 + j] = hh;
-            u64* g = nodes + (groups * w + (u64)blockIdx.x * w + q) * 8;   // this level has groups * w nodes, first at that heap index
-            g[j] = hl; g[4 + j] = hh;
+            quad_parent(ql, src + q * 16, 128, hl, hh);
+            quad_parent_store(j, hl, hh, dst + q * 8, nodes + (groups * w + (u64)blockIdx.x * w + q) * 8);   // this level has groups * w nodes, first at that heap index
             if (w == 1 && whole_tree && root_out != nullptr) {
                 __hip_atomic_store(root_out + j, hl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(root_out + 4 + j, hh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -424,8 +415,7 @@ int merkle_build_xfe_launch(const u64* d_limbs, u64 limb_stride, u64 n, u64* d_n
     if (n == 0) return BFS_OK;
     const u64* d_ms = nullptr;
     BFS_TRY(get_leaf_midstates(&d_ms));
-    u32 depth = 0;
-    while ((1ull << depth) < n) ++depth;
+    const u32 depth = tree_depth(n);
     const u64 npo2 = 1ull << depth;
     if (n <= QUAD_LEAVES_MAX)
         hipLaunchKernelGGL(merkle_leaves_xfe_quad_kernel, dim3((u32)((n + 63) / 64)), dim3(256), 0, stream, d_limbs, limb_stride, n, d_nodes + npo2 * 8, d_ms);
@@ -444,17 +434,13 @@ int fri_round_fused_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u6
     BFS_TRY(get_leaf_midstates(&d_ms));
     const u32 groups = (u32)(n <= FRI_WG_LEAVES ? 1 : n / FRI_WG_LEAVES);
     const dim3 grid(groups), block(4 * FRI_WG_LEAVES);
-    switch (fold.in == nullptr ? 1u : fold.log2_folding) {
-    case 1: hipLaunchKernelGGL(fri_round_quad_kernel<1>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
-    case 2: hipLaunchKernelGGL(fri_round_quad_kernel<2>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
-    case 3: hipLaunchKernelGGL(fri_round_quad_kernel<3>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq); break;
-    default: set_error("internal: fold by 2^%u", fold.log2_folding); return BFS_ERR_BAD_ARG;
-    }
-    BFS_HIP(hipGetLastError());
+    BFS_TRY(with_fold_factor(fold.in == nullptr ? 1u : fold.log2_folding, [&](auto k) -> int {
+        hipLaunchKernelGGL(fri_round_quad_kernel<decltype(k)::value>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes, d_ms, root_out, seq);
+        BFS_HIP(hipGetLastError());
+        return BFS_OK;
+    }));
     if (groups == 1) return BFS_OK;
-    u32 depth = 0;
-    while ((1ull << depth) < groups) ++depth;
-    return merkle_inner_launch(d_nodes, depth, groups, stream, root_out, seq);     // the level of the subtree roots plays the leaf level
+    return merkle_inner_launch(d_nodes, tree_depth(groups), groups, stream, root_out, seq);     // the level of the subtree roots plays the leaf level
 }
 
 // Merkle(codeword) of a FRI round with more than FRI_FUSED_MAX elements, the fold that produces the codeword done by the leaf kernel
@@ -462,24 +448,20 @@ int merkle_build_xfe_fold_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stri
     if (fold.in == nullptr || n <= QUAD_LEAVES_MAX) { set_error("internal: fused fold + leaves on %llu elements", (unsigned long long)n); return BFS_ERR_BAD_ARG; }
     const u64* d_ms = nullptr;
     BFS_TRY(get_leaf_midstates(&d_ms));
-    u32 depth = 0;
-    while ((1ull << depth) < n) ++depth;
+    const u32 depth = tree_depth(n);
     const u64 npo2 = 1ull << depth;
     const dim3 grid((u32)((n + LEAF_THREADS - 1) / LEAF_THREADS)), block(LEAF_THREADS);
-    switch (fold.log2_folding) {
-    case 1: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<1>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
-    case 2: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<2>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
-    case 3: hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<3>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms); break;
-    default: set_error("internal: fold by 2^%u", fold.log2_folding); return BFS_ERR_BAD_ARG;
-    }
-    BFS_HIP(hipGetLastError());
+    BFS_TRY(with_fold_factor(fold.log2_folding, [&](auto k) -> int {
+        hipLaunchKernelGGL(merkle_leaves_xfe_fold_kernel<decltype(k)::value>, grid, block, 0, stream, fold, d_cw, cw_stride, n, d_nodes + npo2 * 8, d_ms);
+        BFS_HIP(hipGetLastError());
+        return BFS_OK;
+    }));
     return merkle_inner_launch(d_nodes, depth, n, stream, root_out, seq);
 }
 
 int merkle_build_bfe_launch(const u64* d_values, u64 n, u64* d_nodes, hipStream_t stream) {
     if (n == 0) return BFS_OK;
-    u32 depth = 0;
-    while ((1ull << depth) < n) ++depth;
+    const u32 depth = tree_depth(n);
     const u64 npo2 = 1ull << depth;
     hipLaunchKernelGGL(merkle_leaves_bfe_kernel, dim3((u32)((n + LEAF_THREADS - 1) / LEAF_THREADS)), dim3(LEAF_THREADS), 0, stream,
                        d_values, n, d_nodes + npo2 * 8);
@@ -489,8 +471,7 @@ int merkle_build_bfe_launch(const u64* d_values, u64 n, u64* d_nodes, hipStream_
 
 int merkle_build_bytes_launch(const u64* d_data, const u64* d_offsets, const u32* d_lengths, u64 n, u64* d_nodes, hipStream_t stream) {
     if (n == 0) return BFS_OK;
-    u32 depth = 0;
-    while ((1ull << depth) < n) ++depth;
+    const u32 depth = tree_depth(n);
     const u64 npo2 = 1ull << depth;
     hipLaunchKernelGGL(blake2b_batch_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, stream, d_data, d_offsets, d_lengths, n, d_nodes + npo2 * 8);
     BFS_HIP(hipGetLastError());

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ntt_plan.hpp"
 
 namespace bfs {
@@ -127,6 +129,22 @@ BFS_HD Xfe fri_fold_point(const FriFoldArgs& f, u64 i) {
         if (j + 1 < K) w = gl_sqr(w);
     }
     return v[0];
+}
+// a runtime log2_folding in 1..3 as the compile-time K of the kernels: returns fn(std::integral_constant<int, K>()), the launch of the instance
+template <class Fn>
+inline int with_fold_factor(u32 log2_folding, Fn&& fn) {
+    switch (log2_folding) {
+    case 1: return fn(std::integral_constant<int, 1>());
+    case 2: return fn(std::integral_constant<int, 2>());
+    case 3: return fn(std::integral_constant<int, 3>());
+    default: set_error("internal: fold by 2^%u", log2_folding); return BFS_ERR_BAD_ARG;
+    }
+}
+// levels above the leaves of a tree over n leaves: its leaf level has 2^tree_depth(n) slots
+inline u32 tree_depth(u64 n) {
+    u32 depth = 0;
+    while ((1ull << depth) < n) ++depth;
+    return depth;
 }
 constexpr u64 FRI_FUSED_MAX = 16384;     // up to 256 workgroups of 64 leaves (their roots: one top kernel)
 int merkle_build_xfe_fold_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out, u64 seq);

@@ -272,29 +272,24 @@ class Fri:
 
     def query(self, current_tree, next_tree, c_indices, proof_stream):
         """fri.py:141-158; folding by a: the a elements c + j * q of the current codeword instead of the two c, c + half"""
+        return self._query_layer(current_tree, next_tree.leafs, next_tree, c_indices, proof_stream)
+
+    def query_last(self, current_tree, last_codeword, c_indices, proof_stream):
+        """fri.py:160-176: the next codeword is in the stream already, so nothing of it gets a path"""
+        return self._query_layer(current_tree, last_codeword, None, c_indices, proof_stream)
+
+    def _query_layer(self, current_tree, next_values, next_tree, c_indices, proof_stream):
         if self.coset_leaves:
-            return self._query_cosets(current_tree, c_indices, proof_stream)      # (nothing of the next tree is opened)
+            return self._query_cosets(current_tree, c_indices, proof_stream)      # (nothing of the next codeword is opened)
         a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
         opened = [[i + j * q for i in c_indices] for j in range(a)]          # (a = 2: a_indices, b_indices)
         for s in range(self.num_colinearity_tests):
-            proof_stream.push(tuple(current_tree.leafs[opened[j][s]] for j in range(a)) + (next_tree.leafs[c_indices[s]],))
+            proof_stream.push(tuple(current_tree.leafs[opened[j][s]] for j in range(a)) + (next_values[c_indices[s]],))
         for s in range(self.num_colinearity_tests):
             for j in range(a):
                 proof_stream.push(current_tree.open(opened[j][s]))
-            proof_stream.push(next_tree.open(c_indices[s]))
-        return [i for column in opened for i in column]
-
-    def query_last(self, current_tree, last_codeword, c_indices, proof_stream):
-        """fri.py:160-176"""
-        if self.coset_leaves:
-            return self._query_cosets(current_tree, c_indices, proof_stream)
-        a, q = self.folding_factor, len(current_tree.leafs) // self.folding_factor
-        opened = [[i + j * q for i in c_indices] for j in range(a)]
-        for s in range(self.num_colinearity_tests):
-            proof_stream.push(tuple(current_tree.leafs[opened[j][s]] for j in range(a)) + (last_codeword[c_indices[s]],))
-        for s in range(self.num_colinearity_tests):
-            for j in range(a):
-                proof_stream.push(current_tree.open(opened[j][s]))
+            if next_tree is not None:
+                proof_stream.push(next_tree.open(c_indices[s]))
         return [i for column in opened for i in column]
 
     def _query_cosets(self, current_tree, c_indices, proof_stream):
@@ -344,7 +339,7 @@ class Fri:
             return False
         n_last = len(last_codeword)
         degree = (n_last // self.expansion_factor) - 1
-        k, a = self._log2_folding, self.folding_factor
+        k = self._log2_folding
         last_omega_v = pow(omega_v, 1 << (k * (rounds - 1)), P)
         assert pow(last_omega_v, n_last, P) == 1, "omega does not have right order"
         top = _interpolant_degree(last_omega_v, [tuple(e.limbs()) for e in last_codeword])
@@ -357,143 +352,95 @@ class Fri:
                 print("proof of work check failure")
                 return False
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), N >> k, N >> (k * (rounds - 1)), t)
-        if self.coset_leaves:
-            return self._verify_coset_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
-        if a != 2:
-            return self._verify_folded_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
-        for r in range(rounds - 1):
-            half = N >> (r + 1)
-            c_indices = [i % half for i in top_level_indices]
-            a_indices, b_indices = list(c_indices), [i + half for i in c_indices]
-            alpha = tuple(alphas[r].limbs())
-            aa, bb, cc = [], [], []
-            for s in range(t):
-                ay, by, cy = proof_stream.pull()
-                aa.append(ay); bb.append(by); cc.append(cy)
-                ax, bx = offset_v * pow(omega_v, a_indices[s], P) % P, offset_v * pow(omega_v, b_indices[s], P) % P
-                ya, yb, yc = tuple(ay.limbs()), tuple(by.limbs()), tuple(cy.limbs())
-                on_a_line = _on_a_line(ax, ya, bx, yb, alpha, yc)
-                if on_a_line is None:          # coinciding abscissae: let the general routine decide (and fail the way the reference's does)
-                    from .algebra import BaseField, BaseFieldElement
-                    lift, base = self.field.lift, BaseField.main()
-                    on_a_line = colinear([(lift(BaseFieldElement(ax, base)), ay), (lift(BaseFieldElement(bx, base)), by), (alphas[r], cy)])
-                if not on_a_line:
-                    print("colinearity check failure")
-                    return False
-            for i in range(t):
-                if not Merkle.verify(roots[r], a_indices[i], proof_stream.pull(), aa[i]):
-                    print("merkle authentication path verification fails for aa")
-                    return False
-                if not Merkle.verify(roots[r], b_indices[i], proof_stream.pull(), bb[i]):
-                    print("merkle authentication path verification fails for bb")
-                    return False
-                if r + 1 != rounds - 1:
-                    if not Merkle.verify(roots[r + 1], c_indices[i], proof_stream.pull(), cc[i]):
-                        print("merkle authentication path verification fails for cc")
-                        return False
-            if r + 1 == rounds - 1:
-                for i in range(t):
-                    if cc[i] != last_codeword[c_indices[i]]:
-                        print("leafs in last round do not correspond to last codeword")
-                        return False
-            omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
-        return True
+        return self._verify_layers(proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v)
 
-    def _verify_folded_layers(self, proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v):
-        """the layers of `verify` when a round folds by a = 4 or 8: per test the a opened values C_r[c + j * q] are folded pairwise, k
-        times (fri.py:127-128 on integer residues, with alpha^(2^step), offset and omega squared between the steps), and the result must
-        be the opened C_{r+1}[c]; then a paths into tree r and -- except on the last layer, whose next codeword is in the proof -- one
-        into tree r + 1."""
-        from .air import P, xadd, xmul, xscale, xsub
-        rounds, t, N, k, a = self.num_rounds(), self.num_colinearity_tests, self.domain.length, self._log2_folding, self.folding_factor
-        half_inv = pow(2, P - 2, P)
-        for r in range(rounds - 1):
-            q = N >> (k * (r + 1))
-            c_indices = [i % q for i in top_level_indices]
-            opened, nexts = [], []
-            for s in range(t):
-                values = proof_stream.pull()
-                if not isinstance(values, tuple) or len(values) != a + 1:
-                    print("colinearity check failure")
-                    return False
-                opened.append(values[:a]); nexts.append(values[a])
-                v = [tuple(e.limbs()) for e in values[:a]]
-                alpha, g, w = tuple(alphas[r].limbs()), offset_v, omega_v
-                for step in range(k):
-                    h = len(v) // 2
-                    folded = []
-                    for m in range(h):
-                        x_inv = pow(g * pow(w, c_indices[s] + m * q, P) % P, P - 2, P)
-                        beta = xscale(alpha, half_inv * x_inv % P)
-                        folded.append(xadd(xscale(xadd(v[m], v[m + h]), half_inv), xmul(beta, xsub(v[m], v[m + h]))))
-                    v, alpha, g, w = folded, xmul(alpha, alpha), g * g % P, w * w % P
-                if v[0] != tuple(values[a].limbs()):
-                    print("colinearity check failure")
-                    return False
-            for i in range(t):
-                for j in range(a):
-                    if not Merkle.verify(roots[r], c_indices[i] + j * q, proof_stream.pull(), opened[i][j]):
-                        print("merkle authentication path verification fails for opened value %d" % j)
-                        return False
-                if r + 1 != rounds - 1:
-                    if not Merkle.verify(roots[r + 1], c_indices[i], proof_stream.pull(), nexts[i]):
-                        print("merkle authentication path verification fails for cc")
-                        return False
-            if r + 1 == rounds - 1:
-                for i in range(t):
-                    if nexts[i] != last_codeword[c_indices[i]]:
-                        print("leafs in last round do not correspond to last codeword")
-                        return False
-            for _ in range(k):
-                omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
-        return True
-
-    def _verify_coset_layers(self, proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v):
-        """the layers of `verify` when every round commits one leaf per folding coset: per layer r the t opened cosets -- tuples of the a
-        values C_r[c + j * q], c = index mod q, q = len(C_r) / a -- then their t paths (log2 q digests each) into tree r.  The value a
-        coset folds to (the arithmetic of _verify_folded_layers; one step when a = 2) is not in the stream: it must be element number
-        c_{r-1} // q of the coset the same test opens on this layer, and on the last layer last_codeword[c]."""
+    def _verify_layers(self, proof_stream, roots, alphas, last_codeword, top_level_indices, omega_v, offset_v):
+        """the layers of `verify`, one loop for every mode.  With q = len(C_r) / a and c = index mod q, test s opens on layer r
+          per element: the tuple (C_r[c], C_r[c + q], .., C_r[c + (a - 1) q], C_{r+1}[c]), then a paths into tree r and -- except on the
+            last layer, whose next codeword is in the proof -- one into tree r + 1;
+          coset leaves: the tuple of the a values alone, then ONE path of log2 q digests into tree r.  What the tuple folds to is not in
+            the stream: it must be element number c_{r-1} // q of the tuple the same test opens on the next layer (`expected`), and
+            last_codeword[c] on the last layer -- compared before the paths are pulled; the per-element protocols compare after.
+        `_judge` decides a tuple."""
         from .air import P
         rounds, t, N, k, a = self.num_rounds(), self.num_colinearity_tests, self.domain.length, self._log2_folding, self.folding_factor
+        coset = self.coset_leaves
+        labels = ["the opened coset"] if coset else ["aa", "bb"] if a == 2 else ["opened value %d" % j for j in range(a)]
         expected = None                                   # per test: (position in this layer's tuple, the value the previous layer folded to)
         for r in range(rounds - 1):
             q = N >> (k * (r + 1))
+            last_layer = r + 1 == rounds - 1
             c_indices = [i % q for i in top_level_indices]
-            opened, folded = [], []
+            opened, nexts = [], []                        # per test: the a elements; what they fold to (coset: a triple, else the opened element)
             for s in range(t):
-                values = proof_stream.pull()
-                if not isinstance(values, tuple) or len(values) != a or not all(hasattr(e, "limbs") for e in values):
+                judged = self._judge(proof_stream.pull(), alphas[r], offset_v, omega_v, c_indices[s], q, expected[s] if expected else None)
+                if judged is None:
                     print("colinearity check failure")
                     return False
-                v = [tuple(e.limbs()) for e in values]
-                if expected is not None and v[expected[s][0]] != expected[s][1]:
-                    print("colinearity check failure")
-                    return False
-                opened.append(values)
-                folded.append(_fold_coset(v, tuple(alphas[r].limbs()), offset_v, omega_v, c_indices[s], q, k))
-            if r + 1 == rounds - 1:
+                opened.append(judged[0]); nexts.append(judged[1])
+
+            def matches_last_codeword():
                 for s in range(t):
-                    if folded[s] != tuple(last_codeword[c_indices[s]].limbs()):
+                    want = last_codeword[c_indices[s]]
+                    if nexts[s] != (tuple(want.limbs()) if coset else want):
                         print("leafs in last round do not correspond to last codeword")
                         return False
+                return True
+            if coset and last_layer and not matches_last_codeword():
+                return False
             for s in range(t):
-                path = proof_stream.pull()
-                if not isinstance(path, list) or len(path) != q.bit_length() - 1 or not all(isinstance(node, (bytes, bytearray)) for node in path):
-                    print("merkle authentication path verification fails for the opened coset")
-                    return False
-                if not Merkle.verify(roots[r], c_indices[s], path, opened[s]):
-                    print("merkle authentication path verification fails for the opened coset")
-                    return False
+                if coset:
+                    paths = [(roots[r], c_indices[s], opened[s])]
+                else:
+                    paths = [(roots[r], c_indices[s] + j * q, opened[s][j]) for j in range(a)]
+                    if not last_layer:
+                        paths.append((roots[r + 1], c_indices[s], nexts[s]))
+                for (tree_root, index, leaf), label in zip(paths, labels + ["cc"]):
+                    path = proof_stream.pull()
+                    well_formed = not coset or (isinstance(path, list) and len(path) == q.bit_length() - 1
+                                                and all(isinstance(node, (bytes, bytearray)) for node in path))
+                    if not well_formed or not Merkle.verify(tree_root, index, path, leaf):
+                        print("merkle authentication path verification fails for " + label)
+                        return False
+            if not coset and last_layer and not matches_last_codeword():
+                return False
             q_next = q >> k
-            expected = [(c_indices[s] // q_next, folded[s]) for s in range(t)] if q_next else None
+            expected = [(c_indices[s] // q_next, nexts[s]) for s in range(t)] if coset and q_next else None
             for _ in range(k):
                 omega_v, offset_v = omega_v * omega_v % P, offset_v * offset_v % P
         return True
+
+    def _judge(self, values, alpha_element, g, w, c, q, expected):
+        """one opened tuple of a layer: (the a elements, what they fold to), or None when the tuple fails.  Folding by 2 per element keeps
+        the reference's question -- are the three points on a line of degree exactly one (`_on_a_line`; a plain fold comparison would
+        accept a constant) -- every other mode compares with `_fold_coset`; `expected`: see _verify_layers."""
+        from .air import P
+        k, a, alpha = self._log2_folding, self.folding_factor, tuple(alpha_element.limbs())
+        if not self.coset_leaves and a == 2:
+            ay, by, cy = values
+            ax, bx = g * pow(w, c, P) % P, g * pow(w, c + q, P) % P
+            on_a_line = _on_a_line(ax, tuple(ay.limbs()), bx, tuple(by.limbs()), alpha, tuple(cy.limbs()))
+            if on_a_line is None:          # coinciding abscissae: let the general routine decide (and fail the way the reference's does)
+                from .algebra import BaseField, BaseFieldElement
+                lift, base = self.field.lift, BaseField.main()
+                on_a_line = colinear([(lift(BaseFieldElement(ax, base)), ay), (lift(BaseFieldElement(bx, base)), by), (alpha_element, cy)])
+            return ((ay, by), cy) if on_a_line else None
+        if not isinstance(values, tuple) or len(values) != (a if self.coset_leaves else a + 1):
+            return None
+        if self.coset_leaves and not all(hasattr(e, "limbs") for e in values):
+            return None
+        v = [tuple(e.limbs()) for e in values[:a]]
+        if expected is not None and v[expected[0]] != expected[1]:
+            return None
+        folded = _fold_coset(v, alpha, g, w, c, q, k)
+        if self.coset_leaves:
+            return values, folded
+        return (values[:a], values[a]) if folded == tuple(values[a].limbs()) else None
 
 
 def _fold_coset(values, alpha, g, w, c, q, k):
     """the a = 2^k values C[c + j q] (integer triples) folded k times: fri.py:127-128 on integer residues, with alpha^(2^step), offset g
-    and generator w squared between the steps -- the arithmetic of Fri._verify_folded_layers"""
+    and generator w squared between the steps -- the only copy of the fold arithmetic on the host"""
     from .air import P, xadd, xmul, xscale, xsub
     half_inv = pow(2, P - 2, P)
     v = list(values)

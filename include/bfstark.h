@@ -108,7 +108,7 @@ int bfs_gl_ntt(const uint64_t* d_in, uint64_t n_in, uint64_t in_stride, uint64_t
                void* stream);
 
 /*
- * bfs_ntt_tune (no reference counterpart; optional): for a LARGE out-of-place transform (>= 256 MiB, all n inputs read, several
+ * bfs_ntt_tune (no reference counterpart; optional; csrc/ntt_route.cpp): for a LARGE out-of-place transform (>= 256 MiB, all n inputs read, several
  * passes) that the caller is going to repeat on the same (d_in, d_out) pair -- a benchmark step, a prover's pooled buffers --, choose by
  * measurement where the first pass writes: straight into the output or through one of three library buffers of the output's size
  * (how fast the first, transposing pass streams depends on the physical placement of the PAIR of buffers: 405-510 us for the same

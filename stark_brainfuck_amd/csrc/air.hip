@@ -15,8 +15,6 @@
 
 namespace bfs {
 
-int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* lo_bits);
-
 // ---- randomized interpolation ------------------------------------------------------------------------------------
 // The reference interpolates each trace column over {omicron^i} plus one extra point (omega, random value r) with a
 // generic subproduct-tree routine (ntt.py:82-161).  The interpolant is unique, so it equals

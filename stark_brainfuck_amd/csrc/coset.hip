@@ -12,8 +12,6 @@
 
 namespace bfs {
 
-int merkle_inner_launch(u64* d_nodes, u32 depth, u64 n_leaves, hipStream_t stream, u64* root_out, u64 seq);
-
 constexpr u32 COSET_THREADS = 64;     // one wavefront per workgroup: 16.5 KiB of LDS, nine workgroups per CU
 
 // Thread c < q: leaf c.  K > 0: cw does not exist yet -- element c + m q of it is fri_fold_point<K>(f, c + m q), written to cw on the way

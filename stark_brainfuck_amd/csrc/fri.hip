@@ -20,13 +20,6 @@
 
 namespace bfs {
 
-int merkle_build_xfe_launch(const u64* d_limbs, u64 limb_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0);
-int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* lo_bits);
-// coset.hip: the tree with one leaf per folding coset
-int coset_tree_launch(const FriFoldArgs* fold, u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, hipStream_t stream, u64* not_mine,
-                      u64 token, u64* root_out, u64 seq);
-int coset_tree_rows(const u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, unsigned char h_root[64], hipStream_t stream);
-
 // the fold on its own (fri.py:127-128, K times: fri_fold_point in runtime.hpp): out[i], i < f.half, from the 2^K inputs in[i + m * f.half]
 // winv_*: two-level powers of the ROUND-0 omega^-1 (exponent i << round_shift)
 // (launched with 256 threads; saying so gives the K = 3 body, which holds 8 extension elements, the registers it needs: without the

@@ -376,7 +376,7 @@ constexpr u64 SUBTREE_PARENTS_MAX = 65536;    // levels of at most this many par
 constexpr u64 QUAD_LEAVES_MAX = 8192;
 
 // build all inner nodes above a leaf level of npo2 = 2^depth slots of which n_leaves hold digests
-int merkle_inner_launch(u64* d_nodes, u32 depth, u64 n_leaves, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0) {
+int merkle_inner_launch(u64* d_nodes, u32 depth, u64 n_leaves, hipStream_t stream, u64* root_out, u64 seq) {
     if (depth == 0) return BFS_OK;  // single leaf: root = leaf digest (merkle.py:43 nodes[1])
     u64 present = n_leaves;
     for (u32 lvl = depth; lvl-- > 0;) {

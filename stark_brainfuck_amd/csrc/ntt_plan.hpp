@@ -1,5 +1,5 @@
-// ntt_plan.hpp -- host-side planning for bfs_gl_ntt(): pass split, tile shapes, twiddle tables.
-// Pure C++ (no HIP calls) so that the planner is also exercised by the host emulation test.
+// ntt_plan.hpp -- host-side planning for bfs_gl_ntt(): pass split, tile shapes, twiddle tables, and the schedule of passes over buffers.
+// Pure C++ (no HIP calls): ntt.hip launches what these functions decide and the host emulation test walks the same decisions.
 // Validation mirrors the reference's asserts: /root/reference/code/ntt.py:5-6 (power of two),
 // :13-14 (w^n == 1), :15-16 (w^(n/2) != 1).
 #pragma once
@@ -229,7 +229,100 @@ inline void ntt_build_coset_tables(const NttPlan& p, u64 shift, CosetHostTables&
 //                run along the columns (coalesced loads): the swizzled layout of lds_addr
 //   single-pass plans (one column): +2 words every 256 rows
 
-// fill the per-pass kernel arguments (pointers are whatever address space the caller runs in)
+// ---- the pass schedule: what ntt.hip's ntt_launch launches and what the host emulation (tests/emu/emu_ntt.cpp) walks ----
+
+// do the spans of a batch of `count`-element inputs and of n-element outputs share an address?
+inline bool ntt_buffers_overlap(const u64* in, u64 count, u64 in_stride, const u64* out, u64 n, u64 out_stride, u32 batch) {
+    const u64* in_end = in + (u64)(batch - 1) * in_stride + count;
+    const u64* out_end = out + (u64)(batch - 1) * out_stride + n;
+    return in < out_end && out < in_end;
+}
+
+// The plan a call runs.  Zero-padded transforms whose coefficients fill at most 1/16 of the domain (every trace column's low-degree
+// extension) take the expansion plan, which starts at the second digit and saves a pass -- unless input and output overlap (its first
+// real pass reads the input while it writes the output) or the caller does not allow it.  false: no plan for this log_n.
+inline bool ntt_choose_plan(u32 log_n, u64 n_in, u64 root, bool overlap, bool allow_expand, NttPlan& p) {
+    NttPlan plain;
+    if (!ntt_make_plan(log_n, root, plain)) return false;
+    if (!(allow_expand && !overlap && ntt_make_expand_plan(log_n, n_in, root, plain, p))) p = plain;
+    return true;
+}
+
+// Where the passes run.  Pass 0 transposes (it cannot run in place); every later pass rewrites the slots it read.  Separate input and
+// output: in -> out, then in place on out.  `via_mid` (input and output overlap, or a measured route: ntt_route.cpp): pass 0 writes an
+// intermediate buffer of batch x n elements and pass 1 reads it -- its tiles touch one 2^(S_0+S_1)-element block each, so reading one
+// buffer and writing another costs it nothing (measured, profiles/r04/ab_ws_probe.txt) --, passes 2.. in place on the output.  An
+// expansion plan has no pass 0 and never goes through the intermediate buffer (ntt_choose_plan: its buffers are separate).
+enum { NTT_BUF_IN = 0, NTT_BUF_OUT = 1, NTT_BUF_MID = 2 };
+struct NttStep {
+    u32 pass;            // index into the plan's digits
+    u32 mode;            // PASS_SINGLE / FIRST / COLUMN / EXPAND
+    u32 S;               // digit width
+    u32 grid_x;          // tiles per transform
+    u32 src, dst;        // NTT_BUF_*
+    u64 count;           // coefficients the step reads per transform: n_in for the first step, n after it
+};
+struct NttSchedule {
+    u32 nsteps = 0;      // 0: n <= 8, the direct small kernel
+    NttStep step[4];
+};
+inline NttSchedule ntt_make_schedule(const NttPlan& p, u64 n_in, bool via_mid) {
+    NttSchedule s;
+    const u64 n = 1ull << p.log_n;
+    const bool mid = via_mid && !p.expand && p.npass > 1;
+    for (u32 t = p.expand ? 1 : 0; t < p.npass; ++t) {
+        NttStep& st = s.step[s.nsteps];
+        const bool first = s.nsteps++ == 0;
+        st.pass = t;
+        st.mode = p.npass == 1 ? PASS_SINGLE : t == 0 ? PASS_FIRST : (p.expand && t == 1) ? PASS_EXPAND : PASS_COLUMN;
+        st.S = p.pass_bits[t];
+        st.grid_x = (u32)((n >> st.S) >> p.logC[t]);
+        st.src = first ? NTT_BUF_IN : (mid && t == 1) ? NTT_BUF_MID : NTT_BUF_OUT;
+        st.dst = (mid && t == 0) ? NTT_BUF_MID : NTT_BUF_OUT;
+        st.count = first ? n_in : n;
+    }
+    return s;
+}
+
+// A run-time (mode, S) as the compile-time shape of the tile kernels: returns fn(TileShape<B1, B2, B3, LOGC, MODE>()), the launch (or
+// the emulation) of that instance; BFS_ERR_BAD_ARG when there is none.  Multi-pass plans use 4096-element tiles (logC = 12 - S,
+// S = 5..8: two register stages); single-pass plans one column of 2^S rows (S = 4..12, up to three stages).  These are ALL the
+// instances of the tile kernels the library contains.
+template <int B1, int B2, int B3, int LOGC, int MODE>
+struct TileShape {};
+template <int MODE, class Fn>
+inline int ntt_with_multi_pass_shape(u32 S, Fn&& fn) {
+    switch (S) {
+        case 5: return fn(TileShape<4, 1, 0, 7, MODE>());
+        case 6: return fn(TileShape<4, 2, 0, 6, MODE>());
+        case 7: return fn(TileShape<4, 3, 0, 5, MODE>());
+        case 8: return fn(TileShape<4, 4, 0, 4, MODE>());
+    }
+    return BFS_ERR_BAD_ARG;
+}
+template <class Fn>
+inline int ntt_with_tile_shape(u32 mode, u32 S, Fn&& fn) {
+    switch (mode) {
+        case PASS_FIRST: return ntt_with_multi_pass_shape<PASS_FIRST>(S, fn);
+        case PASS_COLUMN: return ntt_with_multi_pass_shape<PASS_COLUMN>(S, fn);
+        case PASS_EXPAND: return ntt_with_multi_pass_shape<PASS_EXPAND>(S, fn);
+        case PASS_SINGLE:
+            switch (S) {
+                case 4: return fn(TileShape<4, 0, 0, 0, PASS_SINGLE>());
+                case 5: return fn(TileShape<4, 1, 0, 0, PASS_SINGLE>());
+                case 6: return fn(TileShape<4, 2, 0, 0, PASS_SINGLE>());
+                case 7: return fn(TileShape<4, 3, 0, 0, PASS_SINGLE>());
+                case 8: return fn(TileShape<4, 4, 0, 0, PASS_SINGLE>());
+                case 9: return fn(TileShape<4, 4, 1, 0, PASS_SINGLE>());
+                case 10: return fn(TileShape<4, 4, 2, 0, PASS_SINGLE>());
+                case 11: return fn(TileShape<4, 4, 3, 0, PASS_SINGLE>());
+                case 12: return fn(TileShape<4, 4, 4, 0, PASS_SINGLE>());
+            }
+    }
+    return BFS_ERR_BAD_ARG;
+}
+
+// fill the kernel arguments of pass t, which reads n_in coefficients per transform (pointers are whatever address space the caller runs in)
 inline PassArgs ntt_pass_args(const NttPlan& p, u32 t, const u64* in, u64* out, u64 in_stride, u64 out_stride,
                               u64 n_in, const NttTables& tb, bool has_coset, u64 shift, u64 post_scale) {
     PassArgs a{};
@@ -254,25 +347,22 @@ inline PassArgs ntt_pass_args(const NttPlan& p, u32 t, const u64* in, u64* out, 
     }
     a.uinv = p.uinv;
     a.sched = p.sched;
-    if (p.expand && t == 1) {
-        // the first real pass of an expansion plan reads the coefficients: n_in of them, of which the first n_main are the main part
+    // the coset shift rides on the pass that reads the coefficients: pass 0, or the first real pass of an expansion plan
+    const bool expand = p.expand && t == 1;
+    a.has_coset = ((t == 0 || expand) && has_coset) ? 1 : 0;
+    const u32 sh1 = S - (S < 4 ? S : 4);
+    if (expand) {
+        // n_in coefficients, of which the first n_main are the main part
         a.main_bits = p.main_bits;
         a.extras = p.extras;
         a.n_main = n_in < (1ull << p.main_bits) ? n_in : (1ull << p.main_bits);
-        a.has_coset = has_coset ? 1 : 0;
-        if (has_coset) {
-            const u32 sh1 = S - (S < 4 ? S : 4);
+        if (a.has_coset) {
             a.coset_delta = gl_pow(shift, 1ull << (sh1 + a.tw_shift));
             a.extra_scale = gl_pow(shift, 1ull << p.main_bits);
         }
-        a.post_scale = last ? post_scale : 1;
-        a.tb = tb;
-        a.tw1 = last ? tb.t_in_last : tb.t_in;
-        a.tw2 = tb.t_in;
-        a.unit0 = (a.tw1 == tb.t_in || post_scale == 1) ? 1 : 0;
-        return a;
+    } else if (a.has_coset) {
+        a.coset_delta = gl_pow(shift, p.npass > 1 ? ((1ull << (p.log_n - S)) << sh1) : (1ull << sh1));
     }
-    a.has_coset = (t == 0 && has_coset) ? 1 : 0;
     a.post_scale = last ? post_scale : 1;
     a.tb = tb;
     // the inner twiddle tables: n^-1 of intt rides on the LAST inner twiddle of the last pass (a single-stage last pass multiplies at its store)
@@ -280,12 +370,6 @@ inline PassArgs ntt_pass_args(const NttPlan& p, u32 t, const u64* in, u64* out, 
     a.tw1 = (last && stages == 2) ? tb.t_in_last : tb.t_in;
     a.tw2 = (last && stages == 3) ? tb.t_in_last : tb.t_in;
     a.unit0 = (a.tw1 == tb.t_in || post_scale == 1) ? 1 : 0;
-    if (a.has_coset) {
-        u32 b1 = S < 4 ? S : 4;
-        u32 sh1 = S - b1;
-        u64 stride = p.npass > 1 ? ((1ull << (p.log_n - S)) << sh1) : (1ull << sh1);
-        a.coset_delta = gl_pow(shift, stride);
-    }
     return a;
 }
 

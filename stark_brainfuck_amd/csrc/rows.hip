@@ -29,8 +29,6 @@
 
 namespace bfs {
 
-int merkle_inner_launch(u64* d_nodes, u32 depth, u64 n_leaves, hipStream_t stream, u64* root_out, u64 seq);
-
 constexpr int ROW_MAX_COLS = 32;
 
 // host-side description of a template: constant byte runs (in a word pool) and the places where a row's integers go

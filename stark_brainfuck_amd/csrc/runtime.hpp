@@ -151,12 +151,63 @@ int merkle_build_xfe_fold_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stri
 int fri_round_fused_launch(const FriFoldArgs& fold, u64* d_cw, u64 cw_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out, u64 seq);
 
 // ---- internal entry points (device pointers, current device) ----
+// ntt.hip.  One bfs_gl_ntt call of at most 65535 transforms, as the pass runner and the route code see it (log_n is the plan's)
+struct NttCall {
+    const u64* in;
+    u64 n_in, in_stride;
+    u64* out;
+    u64 out_stride;
+    u32 batch;
+    u64 root, shift, post_scale;
+    u32 streaming;                                    // non-temporal data accesses (ntt_core.hpp)
+    hipStream_t stream;
+};
+constexpr u64 NTT_STREAMING_BYTES = 128ull << 20;     // one 2^24-point column (128 MiB) still runs out of the Infinity Cache, two do not
+int ntt_launch(const u64* d_in, u64 n_in, u64 in_stride, u64* d_out, u64 out_stride, u32 log_n, u32 batch, u64 root,
+               u64 shift, u64 post_scale, hipStream_t stream);
+// steps first..last of the call's schedule (ntt_plan.hpp: ntt_make_schedule); mid: the intermediate buffer of passes 0 and 1, or null
+int ntt_run_steps(const NttCall& c, const NttPlan& p, u64* mid, u32 first, u32 last);
+// two-level power tables of `root` (order 2^log_n): root^e = lo[e & mask] * hi[e >> lo_bits]
+int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* lo_bits);
+// the environment switches of the transform, each read once per process
+constexpr int NTT_ROUTE_CANDIDATES = 3;
+constexpr int NTT_ROUTE_DIRECT = -1;                  // a route: direct, or k >= 0 through candidate buffer k
+enum class NttRouteMode { Remembered, Auto, Forced };
+struct NttEnv {
+    NttRouteMode route_mode;      // BFS_NTT_WS_PROBE unset: routes come from bfs_ntt_tune only; "auto" / "1": bfs_gl_ntt tunes a pair itself the third
+    int forced_route;             //   time it sees it; "0" / "direct" / "buffer0..2": Forced, this route for every large transform and tune a no-op
+    bool probe_log;               // BFS_NTT_WS_PROBE_LOG=1: the route measurements go to stderr
+    int force_streaming;          // BFS_NTT_STREAMING=0 / 1 forces the choice (A/B, tools/ab_ntt.sh); -1: by size
+    bool allow_expand;            // BFS_NTT_EXPAND=0: zero-padded transforms take the plain plan too
+    bool plan_log;                // BFS_NTT_PLAN_LOG: one stderr line per tiled call
+};
+const NttEnv& ntt_env();
+
+// ntt_route.cpp: where pass 0 of a large out-of-place transform writes
+constexpr int NTT_ROUTE_SLOT0 = 16;                   // workspace slots 16.. hold the candidate buffers
+int ntt_route(const NttCall& c, const NttPlan& p, int* route);
 int ntt_route_probe_info(float* us, int* route, unsigned long long* probes);
 int ntt_tune(const u64* d_in, u64 in_stride, u64* d_out, u64 out_stride, u32 log_n, u32 batch, u64 root, hipStream_t stream, int* route_out);
 size_t ntt_route_forget_range(const void* lo, size_t bytes, bool may_free);
 void ntt_route_trim();
-int ntt_launch(const u64* d_in, u64 n_in, u64 in_stride, u64* d_out, u64 out_stride, u32 log_n, u32 batch, u64 root,
-               u64 shift, u64 post_scale, hipStream_t stream);
+
+// pointwise.hip
+int mul_pointwise_launch(const u64* a, const u64* b, u64* out, u64 n, hipStream_t stream);
+int batch_inverse_launch(const u64* in, u64* out, u64 n, hipStream_t stream);
+int scale_launch(const u64* in, u64* out, u64 n, u64 stride, u32 batch, u64 factor, hipStream_t stream);
+int xfe_mul_pointwise_launch(const u64* a, u64 a_stride, const u64* b, u64 b_stride, u64* out, u64 out_stride, u64 n, hipStream_t stream);
+int xfe_batch_inverse_launch(const u64* in, u64 in_stride, u64* out, u64 out_stride, u64 n, hipStream_t stream);
+
+// merkle.hip
+int merkle_inner_launch(u64* d_nodes, u32 depth, u64 n_leaves, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0);
+int merkle_build_xfe_launch(const u64* d_limbs, u64 limb_stride, u64 n, u64* d_nodes, hipStream_t stream, u64* root_out = nullptr, u64 seq = 0);
+int merkle_build_bfe_launch(const u64* d_values, u64 n, u64* d_nodes, hipStream_t stream);
+int merkle_build_bytes_launch(const u64* d_data, const u64* d_offsets, const u32* d_lengths, u64 n, u64* d_nodes, hipStream_t stream);
+
+// coset.hip: the tree with one leaf per folding coset
+int coset_tree_launch(const FriFoldArgs* fold, u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, hipStream_t stream, u64* not_mine,
+                      u64 token, u64* root_out, u64 seq);
+int coset_tree_rows(const u64* d_cw, u64 cw_stride, u64 q, u32 log2_coset, u64* d_nodes, unsigned char h_root[64], hipStream_t stream);
 
 // pow.hip: the smallest nonce in [first, first + count) whose hash with `seed` starts with `bits` zero bits (pow_core.hpp); bounded
 // launches in ascending order, the stream synchronised after each.  POW_DEFAULT_WINDOW: the nonces of one search step of a FRI

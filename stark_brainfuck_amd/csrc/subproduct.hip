@@ -22,10 +22,6 @@
 
 #include "runtime.hpp"
 
-namespace bfs {
-int batch_inverse_launch(const u64* in, u64* out, u64 n, hipStream_t stream);
-}
-
 using namespace bfs;
 
 namespace {

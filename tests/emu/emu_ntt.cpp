@@ -11,7 +11,7 @@
 using namespace bfs;
 
 template <int B1, int B2, int B3, int LOGC, int MODE>
-static void run_pass(const PassArgs& a, u32 grid_x, u32 batch) {
+static int run_pass(TileShape<B1, B2, B3, LOGC, MODE>, const PassArgs& a, u32 grid_x, u32 batch) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
     std::vector<u64> smem(Cfg::LDS_WORDS + 2);
     // dense stage-1 -> stage-2 twiddle table, as the kernel builds it in LDS
@@ -32,32 +32,7 @@ static void run_pass(const PassArgs& a, u32 grid_x, u32 batch) {
             if (B2 > 0) for (u32 t = 0; t < (u32)Cfg::W; ++t) ntt_stage2<B1, B2, B3, LOGC, MODE>(a, smem.data(), t, bx, by, srow);
             if (B3 > 0) for (u32 t = 0; t < (u32)Cfg::W; ++t) ntt_stage3<B1, B2, B3, LOGC, MODE>(a, smem.data(), t, bx, by, srow);
         }
-}
-
-template <int MODE>
-static void dispatch_multi(const PassArgs& a, u32 S, u32 grid_x, u32 batch) {
-    switch (S) {
-        case 5: run_pass<4, 1, 0, 7, MODE>(a, grid_x, batch); break;
-        case 6: run_pass<4, 2, 0, 6, MODE>(a, grid_x, batch); break;
-        case 7: run_pass<4, 3, 0, 5, MODE>(a, grid_x, batch); break;
-        case 8: run_pass<4, 4, 0, 4, MODE>(a, grid_x, batch); break;
-        default: abort();
-    }
-}
-
-static void dispatch_single(const PassArgs& a, u32 S, u32 batch) {
-    switch (S) {
-        case 4: run_pass<4, 0, 0, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 5: run_pass<4, 1, 0, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 6: run_pass<4, 2, 0, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 7: run_pass<4, 3, 0, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 8: run_pass<4, 4, 0, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 9: run_pass<4, 4, 1, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 10: run_pass<4, 4, 2, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 11: run_pass<4, 4, 3, 0, PASS_SINGLE>(a, 1, batch); break;
-        case 12: run_pass<4, 4, 4, 0, PASS_SINGLE>(a, 1, batch); break;
-        default: abort();
-    }
+    return 0;
 }
 
 static int emu_allow_expand = 1;
@@ -79,14 +54,18 @@ extern "C" int emu_gl_ntt(const u64* in, u64 n_in, u64 in_stride, u64* out, u64 
     if (rc) return rc;
     const u64 n = 1ull << log_n;
     if (n_in > n) return BFS_ERR_TOO_MANY_COEFFS;
+    // the product's decisions (ntt.hip: ntt_launch makes the same three calls): overlapping in / out of a multi-pass plan go through an
+    // intermediate buffer in passes 0 and 1, and `force_ws` lets a test take that route with separate buffers too
+    const bool overlap = log_n > NTT_TILE_LOG && n_in != 0 && (ntt_buffers_overlap(in, n_in, in_stride, out, n, out_stride, batch) || emu_force_ws);
     NttPlan p;
-    if (!ntt_make_plan(log_n, root, p)) return BFS_ERR_BAD_ARG;
+    if (!ntt_choose_plan(log_n, n_in, root, overlap, emu_allow_expand != 0, p)) return BFS_ERR_BAD_ARG;
     if (p.npass == 0) {
         SmallArgs a{in, out, in_stride, out_stride, n_in, log_n, root, shift, post_scale};
         for (u32 b = 0; b < batch; ++b)
             for (u32 k = 0; k < n; ++k) ntt_small_body(a, k, b);
         return 0;
     }
+    emu_expand_plans += p.expand;
     NttHostTables ht;
     ntt_build_tables(p, root, post_scale, ht);
     CosetHostTables ct;
@@ -94,57 +73,37 @@ extern "C" int emu_gl_ntt(const u64* in, u64 n_in, u64 in_stride, u64* out, u64 
     if (coset) ntt_build_coset_tables(p, shift, ct);
     NttTables tb{ht.w_lo.data(), ht.w_hi.data(), p.lo_bits, p.t_in_log, ht.t_in.data(), ht.t_in_last.data(),
                  coset ? ct.s_lo.data() : nullptr, coset ? ct.s_hi.data() : nullptr, nullptr, nullptr};
-    // the product's buffer flow (ntt.hip: ntt_launch): pass 0 in -> out, later passes in place on out; overlapping in / out go through
-    // an intermediate buffer in passes 0 and 1.  `force_ws` lets a test take that route with separate buffers too.
-    const u64* in_end = in + (u64)(batch - 1) * in_stride + n_in;
-    const u64* out_end = out + (u64)(batch - 1) * out_stride + n;
-    const bool overlap = p.npass > 1 && n_in != 0 && ((in < out_end && out < in_end) || emu_force_ws);
-    // the expansion plan of a zero-padded transform (ntt.hip: ntt_launch takes it under the same condition)
-    NttPlan xp;
-    if (emu_allow_expand && !overlap && ntt_make_expand_plan(log_n, n_in, root, p, xp)) {
-        ++emu_expand_plans;
-        for (u32 t = 1; t < xp.npass; ++t) {
-            const u32 S = xp.pass_bits[t];
-            const u32 grid_x = (u32)((n >> S) >> xp.logC[t]);
-            tb.row = nullptr; tb.srow = nullptr;
-            if (t == 1) {
-                PassArgs a = ntt_pass_args(xp, t, in, out, in_stride, out_stride, n_in, tb, coset, shift, post_scale);
-                dispatch_multi<PASS_EXPAND>(a, S, grid_x, batch);
-            } else {
-                PassArgs a = ntt_pass_args(xp, t, out, out, out_stride, out_stride, n, tb, coset, shift, post_scale);
-                dispatch_multi<PASS_COLUMN>(a, S, grid_x, batch);
-            }
-        }
-        return 0;
-    }
-    std::vector<u64> ws;
-    if (overlap) ws.resize((size_t)n * batch);
-    std::vector<std::vector<u64>> rows(p.npass), srows(p.npass);
-    for (u32 t = 0; t < p.npass; ++t) {
-        const u64* src = out;
-        u64* dst = out;
-        u64 src_stride = out_stride, dst_stride = out_stride;
-        if (t == 0) {
-            src = in; src_stride = in_stride;
-            if (overlap) { dst = ws.data(); dst_stride = n; }
-        } else if (t == 1 && overlap) {
-            src = ws.data(); src_stride = n;
-        }
-        tb.row = nullptr;
-        tb.srow = nullptr;
-        {
-            NttRowSpec load, store;
-            ntt_row_specs(p, t, root, load, store);
-            if (load.omega) { ntt_product_table(load.omega, load.a_bits, load.b_bits, rows[t]); tb.row = rows[t].data(); }
-            if (store.omega) { ntt_product_table(store.omega, store.a_bits, store.b_bits, srows[t]); tb.srow = srows[t].data(); }
-        }
-        PassArgs a = ntt_pass_args(p, t, src, dst, src_stride, dst_stride, t == 0 ? n_in : n, tb, coset, shift, post_scale);
-        u32 grid_x = (u32)((n >> p.pass_bits[t]) >> p.logC[t]);
-        if (p.npass == 1) dispatch_single(a, p.pass_bits[0], batch);
-        else if (t == 0) dispatch_multi<PASS_FIRST>(a, p.pass_bits[t], grid_x, batch);
-        else dispatch_multi<PASS_COLUMN>(a, p.pass_bits[t], grid_x, batch);
+    std::vector<u64> mid;
+    if (overlap) mid.resize((size_t)n * batch);
+    const NttSchedule s = ntt_make_schedule(p, n_in, overlap);
+    const struct { u64* ptr; u64 stride; } buf[3] = {{const_cast<u64*>(in), in_stride}, {out, out_stride}, {mid.data(), n}};
+    for (u32 k = 0; k < s.nsteps; ++k) {
+        const NttStep& st = s.step[k];
+        std::vector<u64> row, srow;
+        NttRowSpec load, store;
+        ntt_row_specs(p, st.pass, root, load, store);
+        tb.row = nullptr; tb.srow = nullptr;
+        if (load.omega) { ntt_product_table(load.omega, load.a_bits, load.b_bits, row); tb.row = row.data(); }
+        if (store.omega) { ntt_product_table(store.omega, store.a_bits, store.b_bits, srow); tb.srow = srow.data(); }
+        const PassArgs a = ntt_pass_args(p, st.pass, buf[st.src].ptr, buf[st.dst].ptr, buf[st.src].stride, buf[st.dst].stride, st.count, tb, shift != 1, shift, post_scale);
+        if (ntt_with_tile_shape(st.mode, st.S, [&](auto shape) { return run_pass(shape, a, st.grid_x, batch); })) abort();
     }
     return 0;
+}
+
+// the step list a call would run (no arithmetic): row k of `steps` = {pass, mode, S, logC, grid_x, src, dst, count} of step k, src / dst
+// 0 input, 1 output, 2 intermediate; *virtual_bits = the digit an expansion plan skips (0: plain plan).  Returns the number of steps, -1: no plan
+extern "C" int emu_schedule(u32 log_n, u64 n_in, u64 root, int via_mid, int allow_expand, u64* steps, u32* virtual_bits) {
+    NttPlan p;
+    if (!ntt_choose_plan(log_n, n_in, root, via_mid != 0, allow_expand != 0, p)) return -1;
+    const NttSchedule s = ntt_make_schedule(p, n_in, via_mid != 0);
+    *virtual_bits = p.expand ? p.pass_bits[0] : 0;
+    for (u32 k = 0; k < s.nsteps; ++k) {
+        const NttStep& st = s.step[k];
+        const u64 row[8] = {st.pass, st.mode, st.S, p.logC[st.pass], st.grid_x, st.src, st.dst, st.count};
+        memcpy(steps + 8 * k, row, sizeof(row));
+    }
+    return (int)s.nsteps;
 }
 
 extern "C" int emu_plan(u32 log_n, u64 root, u32* npass, u32* bits, u32* logc, u32* uinv) {

@@ -235,6 +235,48 @@ def test_planner(emu, oracle):
         assert (u * uinv.value) % 16 == 1
 
 
+def test_schedule_of_every_plan(emu, oracle):
+    """ntt_choose_plan + ntt_make_schedule (ntt_plan.hpp), the step list that ntt_launch launches and emu_gl_ntt walks: for every size,
+    fill, with and without the intermediate buffer and the expansion plan, the buffers chain from the input to the output, only the
+    in-place column passes read what they write, the intermediate buffer sits between passes 0 and 1 of a plain multi-pass plan and
+    nowhere else, the digits add up to log n and every step's grid covers the transform once."""
+    COLUMN, SINGLE, FIRST, EXPAND = 0, 1, 2, 3
+    IN, OUT, MID = 0, 1, 2
+    emu.emu_schedule.argtypes = [ctypes.c_uint32, u64, u64, ctypes.c_int, ctypes.c_int, vp, vp]
+    expanded = 0
+    for logn in range(4, 33):
+        n = 1 << logn
+        root = oracle.primitive_nth_root(n)
+        for n_in in sorted({n, n // 16 + 1, n // 64, 1}):
+            for via_mid in (0, 1):
+                for allow in (0, 1):
+                    raw = (u64 * 32)()
+                    virtual = ctypes.c_uint32()
+                    count = emu.emu_schedule(logn, n_in, root, via_mid, allow, raw, ctypes.byref(virtual))
+                    case = (logn, n_in, via_mid, allow)
+                    assert 1 <= count <= 4, case
+                    steps = [dict(zip(("pass", "mode", "S", "logC", "grid_x", "src", "dst", "count"), raw[8 * k:8 * k + 8])) for k in range(count)]
+                    assert steps[0]["src"] == IN and steps[0]["count"] == n_in, case
+                    assert steps[-1]["dst"] == OUT, case
+                    for a, b in zip(steps, steps[1:]):
+                        assert b["src"] == a["dst"] and b["count"] == n and b["pass"] == a["pass"] + 1, case
+                    for st in steps:
+                        assert (st["src"] == st["dst"]) <= (st["mode"] == COLUMN), case
+                        assert st["grid_x"] << (st["S"] + st["logC"]) == n, case
+                    mids = [(k, side) for k, st in enumerate(steps) for side in ("src", "dst") if st[side] == MID]
+                    assert mids == ([(0, "dst"), (1, "src")] if via_mid and logn > 12 else []), case
+                    assert sum(st["S"] for st in steps) + virtual.value == logn, case
+                    modes = [st["mode"] for st in steps]
+                    if virtual.value:
+                        assert allow and not via_mid and steps[0]["pass"] == 1, case
+                        assert modes == [EXPAND] + [COLUMN] * (count - 1), case
+                        expanded += 1
+                    else:
+                        assert steps[0]["pass"] == 0, case
+                        assert modes == ([SINGLE] if logn <= 12 else [FIRST] + [COLUMN] * (count - 1)), case
+    assert expanded > 0
+
+
 def test_leaf_encoder_matches_reference_pickles(emu):
     g = load_golden("pickle.json")
     for r in g["xfe_leaves"]:

@@ -15,13 +15,17 @@ Where the time goes in the reference, and where it goes here:
 Padding, Fiat-Shamir sampling, transcript assembly and the object-identity bookkeeping of opened rows stay on the host.
 """
 import ctypes
+import gc
+import os
+import time
+from hashlib import blake2b
+from types import SimpleNamespace
 
 import numpy as np
-from hashlib import blake2b
 from os import urandom          # module-level on purpose: tests patch `brainfuck_stark.urandom` for determinism
 from .randomness import source as random_source
 
-from . import _lib, air
+from . import _lib, air, arrays, salted_merkle as salted_mod, table as table_mod
 from .algebra import BaseField, BaseFieldElement
 from .arrays import XArray
 from .device import GatherBatch, current_stream, gather, synchronize
@@ -32,7 +36,7 @@ from .instruction_table import InstructionTable
 from .io_table import InputTable, OutputTable
 from .ip import ProofStream
 from .memory_table import MemoryTable
-from .merkle import Merkle
+from .merkle import Merkle, leaf_pickle_source
 from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
@@ -47,6 +51,139 @@ _u64 = ctypes.c_uint64
 
 class _MalformedProof(Exception):
     """an object in the proof is not what its position requires (verify() answers False)"""
+
+
+def _canonical_limbs(e):
+    """value of an element read from the proof, as canonical residues: the prover chooses the representation (any Python int
+    unpickles), the reference reduces in every operation (algebra.py:89-99) and so sees v mod p -- and so must every
+    consumer here: bfs_air_evaluate's host arithmetic assumes canonical operands and ctypes truncates above 2^64.  An extension
+    element with more than three coefficients is not an element: the proof is refused."""
+    if hasattr(e, "limbs"):
+        c = e.limbs()
+        if len(c) != 3:
+            raise _MalformedProof("extension element with %d coefficients" % len(c))
+        return (c[0] % air.P, c[1] % air.P, c[2] % air.P)
+    return (e.value % air.P, 0, 0)
+
+
+def _triples(raw, count):
+    """`count` extension elements out of a flat array of u64 limbs, as int triples"""
+    return [(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]) for i in range(count)]
+
+
+def _seed_or_stream(draw, nbytes):
+    """a block of random bytes as (seed, None) in production -- 32 bytes of the system's (or the ranks' shared) randomness, which the
+    device expands -- or as (None, bytes) when a test replaced urandom: the `nbytes` the reference draws, from the reference's byte stream"""
+    if draw is os.urandom or getattr(draw, "expand_on_device", False):
+        return draw(32), None
+    return None, draw(nbytes)
+
+
+class _TermLayout:
+    """The order of the terms of the non-linear combination (:245-293), which is also the order of the columns in the zipped rows:
+    tables in the order of `tables`, all base columns, then all extension columns, then every table's quotients (boundary /
+    transition / terminal), then one quotient per permutation argument.  Term s has the weights 1 + 2s and 2 + 2s (weight 0 is the
+    randomizer codeword's); column s is element 1 + s of an opened row (element 0 is the randomizer codeword's)."""
+
+    def __init__(self, tables, permutation_arguments, max_degree):
+        self.tables, self.max_degree = tables, max_degree
+        self.num_base = sum(self.width(t, 0) for t in tables)
+        self.num_columns = self.num_base + sum(self.width(t, 1) for t in tables)
+        self.base, self.ext, self.quot = [], [], []          # per table: its slice of the terms
+        base_at, ext_at, quot_at = 0, self.num_base, self.num_columns
+        for t in tables:
+            bw, xw, nq = self.width(t, 0), self.width(t, 1), t.num_quotients()
+            self.base.append(slice(base_at, base_at + bw))
+            self.ext.append(slice(ext_at, ext_at + xw))
+            self.quot.append(slice(quot_at, quot_at + nq))
+            base_at, ext_at, quot_at = base_at + bw, ext_at + xw, quot_at + nq
+        self.first_argument = quot_at                        # the term of permutation argument j is first_argument + j
+        self.weight_count = 1 + 2 * (quot_at + len(permutation_arguments))          # the randomizer codeword's, then two per term
+
+    @staticmethod
+    def width(table, ext):
+        return table.full_width - table.base_width if ext else table.base_width
+
+    def column_degree_bounds(self):
+        """the interpolant's degree bound per base column, then per extension column (heights are final once the tables are padded)"""
+        return [t.interpolant_degree() for ext in (0, 1) for t in self.tables for _ in range(self.width(t, ext))]
+
+    def shifts(self, quotient_bounds):
+        """per term, the power of x that lifts it to the common degree bound: the columns, then the quotients"""
+        return [self.max_degree - b for b in self.column_degree_bounds() + list(quotient_bounds)]
+
+    def unit_distances(self, n):
+        """the distances from an opened index to the rows opened with it.  The iteration order of this very expression is part of the
+        proof format: the rows are pushed in it, and native prover and verifier are handed the list as it comes out."""
+        return list(set(table.unit_distance(n) for table in self.tables))
+
+    def device_columns(self, n, ext):
+        """every base (ext = 0) or extension (ext = 1) column codeword in HBM, in term order: (table, column, address, limbs).  A
+        table's columns lie `limbs * n` words apart."""
+        out = []
+        for t in self.tables:
+            buf, limbs = (t.ext_codewords, 3) if ext else (t.base_codewords, 1)
+            out += [(t, c, buf.ptr + 8 * limbs * c * n, limbs) for c in range(self.width(t, ext))]
+        return out
+
+    def row_requests(self, n, ext, i):
+        """gather requests (address, words, stride) for row i of those columns: one per table, from its first column on"""
+        return [(address + 8 * i, limbs * self.width(t, ext), n) for t, c, address, limbs in self.device_columns(n, ext) if c == 0]
+
+
+class _RowBuilder:
+    """Opened rows of the two zipped trees as the objects the reference pickles (only opened rows are ever read back).  The trees keep
+    its methods in their lazy leaf lists, so it outlives prove(): it must not hold the prover, or a prover object kept with its trees
+    (keep_intermediates) becomes a reference cycle and its HBM waits for a full garbage collection."""
+
+    def __init__(self, layout, n, randomizer_codeword, field, xfield):
+        self.layout, self.n, self.randomizer_codeword, self.field, self.xfield = layout, n, randomizer_codeword, field, xfield
+        self.fetched_base, self.fetched_ext = {}, {}      # row -> words, filled by the batched gather of the openings
+        self.fastlist = arrays._fastlist                  # the same objects, made in C (cpyext/fastlist.c): 16 elements in 3 us instead of 16
+        self.internal = xfield.modulus.coefficients[0].field
+        self.moduli = self.shared = self.plain_columns = None
+
+    def share(self, moduli):
+        """moduli: per extension column, None or the period with which its elements share coefficient objects (Table.ext_sharing_moduli)"""
+        self.moduli = moduli
+        self.shared = [dict() for _ in moduli]            # per column: i mod modulus -> the coefficient objects of that class
+        self.plain_columns = [c for c in range(len(moduli)) if moduli[c] is None]
+
+    def requests(self, ext, i):
+        """gather requests for row i of the base tree (ext = 0: the randomizer codeword, then the base columns) or the extension tree"""
+        rc = self.randomizer_codeword
+        return ([] if ext else [(rc.ptr + 8 * i, 3, rc.stride)]) + self.layout.row_requests(self.n, ext, i)
+
+    def base_row(self, i):
+        words = self.fetched_base[i] if i in self.fetched_base else gather(self.requests(0, i))
+        if self.fastlist is not None:
+            tail = self.fastlist.unpack_base(np.ascontiguousarray(words[3:], dtype=np.uint64), BaseFieldElement, self.field)
+        else:
+            tail = [BaseFieldElement(int(v), self.field) for v in words[3:]]
+        return tuple([self.xfield.from_limbs([int(v) for v in words[:3]])] + tail)
+
+    def ext_row(self, i):
+        xf, moduli, columns = self.xfield, self.moduli, self.layout.num_columns - self.layout.num_base
+        words = self.fetched_ext[i] if i in self.fetched_ext else gather(self.requests(1, i))
+        row, made = [], {}          # made: column -> element, for those made in C
+        if self.fastlist is not None and self.plain_columns:
+            # the elements without shared coefficient objects, all at once: limb planes (3, k) -> k ExtensionFieldElements
+            soa = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).reshape(columns, 3)[self.plain_columns].T)
+            made = dict(zip(self.plain_columns, self.fastlist.unpack_ext(soa, ExtensionFieldElement, Polynomial, BaseFieldElement, xf, self.internal)))
+        for c in range(columns):
+            limbs = [int(v) for v in words[3 * c:3 * c + 3]]
+            if c in made:
+                row.append(made[c])
+            elif moduli[c] is None:
+                row.append(xf.from_limbs(limbs))
+            else:
+                while limbs and limbs[-1] == 0:
+                    limbs.pop()
+                objs = self.shared[c].setdefault(i % moduli[c], [BaseFieldElement(v, self.internal) for v in limbs])
+                e = ExtensionFieldElement(Polynomial(objs), xf)
+                e.shares_coefficients = True
+                row.append(e)
+        return tuple(row)
 
 
 class BrainfuckStark:
@@ -99,6 +236,7 @@ class BrainfuckStark:
         generator = BrainfuckStark.field.generator()
         omega = BrainfuckStark.field.primitive_nth_root(fri_domain_length)
         self.fri = Fri(generator, omega, fri_domain_length, self.expansion_factor, self.num_colinearity_checks, self.xfield)
+        self._layout = _TermLayout(self.tables, self.permutation_arguments, self.max_degree)
 
     def get_terminals(self):
         """the five terminals as int triples (:103-109)"""
@@ -111,7 +249,6 @@ class BrainfuckStark:
         """:104-112: weight i = ExtensionField.sample(blake2b(randomness + bytes(i)).digest()), i.e. the three 21-byte big-endian
         chunks of the digest mod p (extension_field.py:100-111; the 64th byte is not used).  One integer conversion per digest."""
         if number > 4:             # natively (bfs_sample_weights): 157 digests and 471 reductions are ~150 us of a 4 ms proof in Python
-            import ctypes
             lib = _lib.load()
             raw = (ctypes.c_uint64 * (3 * number))()
             randomness = bytes(randomness)
@@ -167,51 +304,49 @@ class BrainfuckStark:
         world_size, rank, group, device = self._cooperation
         return RowShardedSaltedMerkle(columns, n, make_row, world_size, rank, group=group, device=device)
 
-    def _openings_python(self, proof_stream, base_tree, extension_tree, combination, combination_tree, base_requests, ext_requests,
-                         fetched_base, fetched_ext, indices, unit_distances, n, xf):
+    def _openings_python(self, p):
         """the openings (:315-333) through Python objects: used when the transcript cannot take them natively (a foreign proof
         stream class, the row-sharded trees of a cooperative proof)"""
+        proof_stream, base_tree, extension_tree, combination_tree, n = p.proof_stream, p.base_tree, p.extension_tree, p.combination_tree, p.n
+        distances = [0] + p.unit_distances
         # everything the openings read from HBM -- rows, salts, authentication paths, combination leaves -- in one round trip
-        rows = list(dict.fromkeys((index + distance) % n for index in indices for distance in [0] + unit_distances))
+        rows = list(dict.fromkeys((index + distance) % n for index in p.indices for distance in distances))
         batch = GatherBatch()
-        row_tickets = {i: ([batch.add(*r) for r in base_requests(i)], [batch.add(*r) for r in ext_requests(i)]) for i in rows}
-        leaf_tickets = {index: batch.add(combination.ptr + 8 * index, 3, combination.stride) for index in dict.fromkeys(indices)}
+        row_tickets = {i: ([batch.add(*r) for r in p.rows.requests(0, i)], [batch.add(*r) for r in p.rows.requests(1, i)]) for i in rows}
+        leaf_tickets = {index: batch.add(p.combination.ptr + 8 * index, 3, p.combination.stride) for index in dict.fromkeys(p.indices)}
         stores = [base_tree.prefetch_salts(rows, batch), extension_tree.prefetch_salts(rows, batch),
                   base_tree.prefetch_paths(rows, batch), extension_tree.prefetch_paths(rows, batch),
-                  combination_tree.prefetch_paths(indices, batch)]
+                  combination_tree.prefetch_paths(p.indices, batch)]
         batch.run()
         for store in stores:
             store()
         for i, (tb, te) in row_tickets.items():
-            fetched_base[i] = np.concatenate([batch.words(t) for t in tb])
-            fetched_ext[i] = np.concatenate([batch.words(t) for t in te])
-        for index in indices:
-            for distance in [0] + unit_distances:
+            p.rows.fetched_base[i] = np.concatenate([batch.words(t) for t in tb])
+            p.rows.fetched_ext[i] = np.concatenate([batch.words(t) for t in te])
+        for index in p.indices:
+            for distance in distances:
                 idx = (index + distance) % n
                 proof_stream.push(base_tree.leafs[idx][0])
                 proof_stream.push(base_tree.open(idx))
                 proof_stream.push(extension_tree.leafs[idx][0])
                 proof_stream.push(extension_tree.open(idx))
         known = {}
-        for index in indices:
+        for index in p.indices:
             if index not in known:                   # the same index twice is the same leaf object twice
-                known[index] = xf.from_limbs([int(v) for v in batch.words(leaf_tickets[index])])
-            leaf = known[index]
-            proof_stream.push(leaf)
+                known[index] = self.xfield.from_limbs([int(v) for v in batch.words(leaf_tickets[index])])
+            proof_stream.push(known[index])
             proof_stream.push(combination_tree.open(index))
-
         return known
 
-    def _openings_native(self, proof_stream, base_tree, extension_tree, combination, combination_tree, base_row, ext_row, moduli,
-                         indices, unit_distances, n, f2, xf, lib, stream):
+    def _openings_native(self, p):
         """the same through bfs_stark_push_openings: rows, salts, paths and leaves go from HBM into the native transcript in one
         call, and become Python objects only if somebody looks at proof_stream.objects (ip.ProofStream._adopt_lazy).  Returns
         {index: handle of the combination leaf} for Fri.prove, or None when this route is not available."""
-        if self._cooperation is not None or type(base_tree) is not ZippedSaltedMerkle or type(extension_tree) is not ZippedSaltedMerkle:
+        base_tree, extension_tree, combination, combination_tree, xf = p.base_tree, p.extension_tree, p.combination, p.combination_tree, self.xfield
+        if (self._cooperation is not None or type(base_tree) is not ZippedSaltedMerkle or type(extension_tree) is not ZippedSaltedMerkle
+                or combination_tree._nodes_host is not None or combination_tree.num_leafs != p.n):
             return None
-        if combination_tree._nodes_host is not None or combination_tree.num_leafs != n:
-            return None
-        transcript = BrainfuckStark._native_transcript(proof_stream, xf)
+        transcript = BrainfuckStark._native_transcript(p.proof_stream, xf)
         if transcript is None:
             return None
 
@@ -225,18 +360,19 @@ class BrainfuckStark:
             if getattr(tree, "_salt_cache", None) is not None:
                 return ctypes.c_void_p(tree._salt_base), 1
             return ctypes.c_void_p(ctypes.addressof(tree._salt_host)), 0
-        base_arr, ext_arr = requests(base_row), requests(ext_row)
+        base_arr, ext_arr = requests(p.rows.requests(0, 0)), requests(p.rows.requests(1, 0))
+        moduli, indices = p.rows.moduli, p.indices
         mods = (_u64 * max(len(moduli), 1))(*[0 if m is None else int(m) for m in moduli])
         idx = (_u64 * len(indices))(*indices)
-        dist = (_u64 * (1 + len(unit_distances)))(0, *unit_distances)
+        dist = (_u64 * (1 + len(p.unit_distances)))(0, *p.unit_distances)
         out = (_u64 * len(indices))()
         (bs, bs_dev), (es, es_dev) = salts(base_tree), salts(extension_tree)
         before = transcript.num_objects()
-        _lib.check(lib.bfs_stark_push_openings(transcript.handle, base_arr, len(base_row), transcript._field_id(f2), ext_arr, len(ext_row), mods,
-                                               len(moduli), n, base_tree._nodes.ptr, bs, bs_dev, extension_tree._nodes.ptr, es, es_dev,
-                                               combination.ptr, combination.stride, combination_tree._nodes.ptr, idx, len(indices), dist, len(dist),
-                                               out, stream))
-        proof_stream._adopt_lazy(transcript, before, transcript.num_objects(), xf)
+        _lib.check(_lib.load().bfs_stark_push_openings(
+            transcript.handle, base_arr, len(base_arr), transcript._field_id(BrainfuckStark.field), ext_arr, len(ext_arr), mods, len(moduli), p.n,
+            base_tree._nodes.ptr, bs, bs_dev, extension_tree._nodes.ptr, es, es_dev, combination.ptr, combination.stride,
+            combination_tree._nodes.ptr, idx, len(indices), dist, len(dist), out, p.stream))
+        p.proof_stream._adopt_lazy(transcript, before, transcript.num_objects(), xf)
         return {index: int(handle) for index, handle in zip(indices, out)}
 
     @staticmethod
@@ -273,7 +409,6 @@ class BrainfuckStark:
         # The trace matrices keep ~10^5 element objects alive; every full garbage collection during (or right after) the proof
         # would walk all of them (measured: 20 ms pauses on a 17 ms proof).  gc.freeze() parks everything that exists now in a
         # permanent generation for the duration of the call; objects made by the proof itself are collected as usual.
-        import gc
         from . import debug_checks
         # DEBUG (the reference's switch, brainfuck_stark.py:251-290, table.py:170-176 / 219-234 / 264-284) or BFS_DEBUG=1: every
         # quotient and every term of the combination is interpolated and its degree asserted (debug_checks.py).  The checks need the
@@ -328,12 +463,69 @@ class BrainfuckStark:
             return None
         return values
 
+    def _native_randomness(self, n):
+        """every random draw of prove(), in its order, from the sources the Python path reads (tests replace them module by module), as
+        the structure bfs_stark_commit takes.  Returns (structure, buffers it points at): keep the second alive as long as the first."""
+        rnd = _lib.StarkRandomness()
+        keep = []                                                               # buffers the structure points at (ADDRESSES go into it:
+        # ctypes.cast(buffer, c_void_p) puts the buffer into its own _objects dictionary -- a reference cycle, and a 24 n-byte salt
+        # buffer per commitment then lives until the cyclic collector happens to run: a soak grew by 5 MB per proof that way)
+        draw = random_source(urandom)
+        count = self.max_degree + 1
+        seed, blob = _seed_or_stream(draw, 3 * 9 * count)        # the randomizer polynomial (:162-165): `count` draws of 27 bytes
+        if seed is not None:
+            keep.append(ctypes.create_string_buffer(seed, 32))
+            rnd.randomizer_seed = ctypes.addressof(keep[-1])
+        else:
+            keep.append(np.ascontiguousarray(sample_ext_many(blob, count, 9), dtype=np.uint64))
+            rnd.randomizer_limbs = keep[-1].ctypes.data
+        tdraw = random_source(table_mod.urandom)
+
+        def draws(source, count):
+            """`count` draws of 24 bytes (table.py:125-127), as integers; the operating system's generator is asked once for all of them"""
+            if source is os.urandom:
+                blob = source(24 * count)
+                return [int.from_bytes(blob[24 * i:24 * i + 24], "big") for i in range(count)]
+            return [int.from_bytes(source(24), "big") for _ in range(count)]
+        base_rand = [v % P_GOLDILOCKS for v in draws(tdraw, sum(t.base_width for t in self.tables[:3] if t.height))]
+        keep.append((_u64 * max(len(base_rand), 1))(*base_rand))
+        rnd.base_randomizers = ctypes.addressof(keep[-1])
+
+        def salts(field_seed, field_data):
+            seed, data = _seed_or_stream(random_source(salted_mod.urandom), 24 * n)
+            keep.append(ctypes.create_string_buffer(seed or data, len(seed or data)))
+            setattr(rnd, field_data if seed is None else field_seed, ctypes.addressof(keep[-1]))
+        salts("base_salt_seed", "base_salts")
+        initials = [sample_ext(draw(3 * 8)) for _ in self.permutation_arguments]
+        rnd.initials = (_u64 * 6)(*[v for i in initials for v in i])
+        mask64 = (1 << 64) - 1              # ExtensionField.sample of 24 bytes: three big-endian 8-byte chunks mod p (extension_field.py:100-111)
+        ext_rand = [c % P_GOLDILOCKS for v in draws(tdraw, sum(t.full_width - t.base_width for t in self.tables[:3] if t.height))
+                    for c in (v >> 128, (v >> 64) & mask64, v & mask64)]
+        keep.append((_u64 * max(len(ext_rand), 1))(*ext_rand))
+        rnd.ext_randomizers = ctypes.addressof(keep[-1])
+        salts("ext_salt_seed", "ext_salts")
+        return rnd, keep
+
+    def _adopt_commit_reply(self, out_ch, out_scan, out_io, ci):
+        """what bfs_stark_commit answered -- 11 challenges, the 7 terminals of its scans with 2 spare, the 2 IO tables' -- onto the
+        tables, as the Python path's extension leaves them (ci: the processor's current-instruction column); returns (challenges,
+        terminals, terminal objects)"""
+        challenges = tuple(_triples(out_ch, 11))
+        scan, io = _triples(out_scan, 9), _triples(out_io, 2)
+        pt, it, mt = self.processor_table, self.instruction_table, self.memory_table
+        (pt.instruction_permutation_terminal, pt.memory_permutation_terminal, pt.input_evaluation_terminal,
+         pt.output_evaluation_terminal) = scan[0:4]
+        it.permutation_terminal, it.evaluation_terminal = scan[4], scan[5]
+        mt.permutation_terminal = scan[6]
+        self.input_table.evaluation_terminal, self.output_table.evaluation_terminal = io
+        pt.evaluation_terminal_identities = (pt._identity(None, scan[2], challenges[8], np.nonzero(ci == ord(","))[0] + 1),
+                                             pt._identity(None, scan[3], challenges[9], np.nonzero(ci == ord("."))[0]))
+        terminals = self.get_terminals()
+        return challenges, terminals, self._terminal_objects(terminals)
+
     def _prove_native(self, program, matrices, proof_stream):
         """prove() through bfs_stark_commit / bfs_stark_finish.  Returns the proof bytes, or None when this route does not apply (the
         caller then takes the Python path): plain-list matrices, a foreign proof stream, a cooperative proof, test hooks."""
-        import os
-        from . import salted_merkle as salted_mod, table as table_mod
-        from .table import sample_base
         if os.environ.get("BFS_NATIVE_PROVE", "1") == "0" or not self.native_stages:
             return None
         if (self._cooperation is not None or self.keep_intermediates or self.stage_timing or self.check_air or self._row_windows is not None
@@ -352,7 +544,6 @@ class BrainfuckStark:
         transcript = BrainfuckStark._native_transcript(proof_stream, xf, refuse_loaded=True)
         if transcript is None:
             return None
-        import time
         t_begin = time.perf_counter()
         for table, matrix in zip(self.tables, ordered):
             table.matrix = matrix
@@ -362,50 +553,7 @@ class BrainfuckStark:
         for table, v in zip(self.tables[:3], values[:3]):
             if v.shape[0] + table._padding_length(v.shape[0]) != table.height:
                 return None                                                     # (the Python path raises where the reference would)
-        # ---- every random draw of prove(), in its order, from the sources the Python path reads (tests replace them module by module)
-        rnd = _lib.StarkRandomness()
-        keep = []                                                               # buffers the structure points at (ADDRESSES go into it:
-        # ctypes.cast(buffer, c_void_p) puts the buffer into its own _objects dictionary -- a reference cycle, and a 24 n-byte salt
-        # buffer per commitment then lives until the cyclic collector happens to run: a soak grew by 5 MB per proof that way)
-        draw = random_source(urandom)
-        count = self.max_degree + 1
-        if draw is os.urandom or getattr(draw, "expand_on_device", False):
-            keep.append(ctypes.create_string_buffer(draw(32), 32))
-            rnd.randomizer_seed = ctypes.addressof(keep[-1])
-        else:
-            keep.append(np.ascontiguousarray(sample_ext_many(draw(3 * 9 * count), count, 9), dtype=np.uint64))
-            rnd.randomizer_limbs = keep[-1].ctypes.data
-        tdraw = random_source(table_mod.urandom)
-
-        def draws(source, count):
-            """`count` draws of 24 bytes (table.py:125-127), as integers; the operating system's generator is asked once for all of them"""
-            if source is os.urandom:
-                blob = source(24 * count)
-                return [int.from_bytes(blob[24 * i:24 * i + 24], "big") for i in range(count)]
-            return [int.from_bytes(source(24), "big") for _ in range(count)]
-        base_rand = [v % P_GOLDILOCKS for v in draws(tdraw, sum(t.base_width for t in self.tables[:3] if t.height))]
-        keep.append((_u64 * max(len(base_rand), 1))(*base_rand))
-        rnd.base_randomizers = ctypes.addressof(keep[-1])
-
-        def salts(field_seed, field_data):
-            sdraw = random_source(salted_mod.urandom)
-            if sdraw is os.urandom or getattr(sdraw, "expand_on_device", False):
-                keep.append(ctypes.create_string_buffer(sdraw(32), 32))
-                setattr(rnd, field_seed, ctypes.addressof(keep[-1]))
-            else:
-                data = sdraw(24 * n)
-                keep.append(ctypes.create_string_buffer(data, len(data)))
-                setattr(rnd, field_data, ctypes.addressof(keep[-1]))
-        salts("base_salt_seed", "base_salts")
-        initials = [sample_ext(draw(3 * 8)) for _ in self.permutation_arguments]
-        rnd.initials = (_u64 * 6)(*[v for i in initials for v in i])
-        mask64 = (1 << 64) - 1              # ExtensionField.sample of 24 bytes: three big-endian 8-byte chunks mod p (extension_field.py:100-111)
-        ext_rand = [c % P_GOLDILOCKS for v in draws(tdraw, sum(t.full_width - t.base_width for t in self.tables[:3] if t.height))
-                    for c in (v >> 128, (v >> 64) & mask64, v & mask64)]
-        keep.append((_u64 * max(len(ext_rand), 1))(*ext_rand))
-        rnd.ext_randomizers = ctypes.addressof(keep[-1])
-        salts("ext_salt_seed", "ext_salts")
-
+        rnd, keep = self._native_randomness(n)          # (`keep` lives until this call returns)
         params = _lib.StarkParams(n.bit_length() - 1, self.expansion_factor, self.num_colinearity_checks, self.security_level,
                                   self.fri.domain.offset.value, self.fri.domain.omega.value, self.max_degree,
                                   (_u64 * 3)(*[t.height for t in self.tables[:3]]))
@@ -421,33 +569,18 @@ class BrainfuckStark:
                                             ms_a, stream))
             t_commit = time.perf_counter()
             # ---- while the GPU extends the extension columns: terminals, their objects, degree bounds
-            challenges = tuple((out_ch[3 * i], out_ch[3 * i + 1], out_ch[3 * i + 2]) for i in range(11))
-            scan = [(out_scan[3 * i], out_scan[3 * i + 1], out_scan[3 * i + 2]) for i in range(9)]
-            pt, it, mt = self.processor_table, self.instruction_table, self.memory_table
-            (pt.instruction_permutation_terminal, pt.memory_permutation_terminal, pt.input_evaluation_terminal,
-             pt.output_evaluation_terminal) = scan[0:4]
-            it.permutation_terminal, it.evaluation_terminal = scan[4], scan[5]
-            mt.permutation_terminal = scan[6]
-            self.input_table.evaluation_terminal = (out_io[0], out_io[1], out_io[2])
-            self.output_table.evaluation_terminal = (out_io[3], out_io[4], out_io[5])
-            ci = values[0][:, 2]
-            pt.evaluation_terminal_identities = (pt._identity(None, scan[2], challenges[8], np.nonzero(ci == ord(","))[0] + 1),
-                                                 pt._identity(None, scan[3], challenges[9], np.nonzero(ci == ord("."))[0]))
-            terminals = self.get_terminals()
-            terminal_objects = self._terminal_objects(terminals)
+            challenges, terminals, terminal_objects = self._adopt_commit_reply(out_ch, out_scan, out_io, values[0][:, 2])
             transcript.scan(terminal_objects)
             handles = (_u64 * 5)(*[transcript.to_native(t) for t in terminal_objects])
-            bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.base_width)]
-            bounds += [t.interpolant_degree() for t in self.tables for _ in range(t.full_width - t.base_width)]
-            quotient_degree_bounds = self._quotient_degree_bounds_cached(challenges, terminals)
-            bounds += quotient_degree_bounds
-            unit_distances = list(set(table.unit_distance(n) for table in self.tables))
+            quotient_degree_bounds = self._quotient_degree_bounds(challenges, terminals, cached=True)
+            shifts = self._layout.shifts(quotient_degree_bounds)
+            unit_distances = self._layout.unit_distances(n)
             dist = (_u64 * (1 + len(unit_distances)))(0, *unit_distances)
             out_idx, out_top = (_u64 * max(self.security_level, 1))(), (_u64 * max(self.num_colinearity_checks, 1))()
             wseed = ctypes.create_string_buffer(32)
             t_host = time.perf_counter()
             _lib.check(lib.bfs_stark_finish(session, transcript.handle, handles, (_u64 * 15)(*[v for t in terminals for v in t]),
-                                            (_u64 * len(bounds))(*[self.max_degree - b for b in bounds]), len(bounds), transcript._field_id(BrainfuckStark.field), dist, len(dist),
+                                            (_u64 * len(shifts))(*shifts), len(shifts), transcript._field_id(BrainfuckStark.field), dist, len(dist),
                                             out_idx, wseed, out_top, ms_b, stream))
         except Exception:
             proof_stream._cached = None          # native code may have appended objects the Python list does not have
@@ -466,36 +599,30 @@ class BrainfuckStark:
 
     _bounds_cache = {}
 
-    def _quotient_degree_bounds_verifier(self, challenges, terminals):
-        """the same for verify(): the challenges are Fiat-Shamir outputs, the terminals are the PROVER's, chosen after it has seen the
+    def _quotient_degree_bounds(self, challenges, terminals, exact_terminals=False, cached=False):
+        """all quotient degree bounds of a proof (:203-221): Table.all_quotient_degree_bounds of every table, then the permutation arguments.
+        exact_terminals, for verify(): the challenges are Fiat-Shamir outputs, the terminals are the PROVER's, chosen after it has seen the
         challenges.  A terminal made from them (the product of two challenges, say) can cancel a monomial of a terminal constraint while
         looking as sampled as any other value; the reference expands symbolically every time and would then shift that quotient by a
-        different amount than the generic bounds say (round-5 advice).  So the terminal constraints -- the only ones the terminals enter
-        -- take the exact expansion here (nine small constraints, ~50 us); boundary and transition bounds depend on the challenges
-        alone and keep their per-shape memory."""
-        out = [b for table in self.tables for b in table.all_quotient_degree_bounds(challenges, terminals, exact_terminals=True)]
-        out += [pa.quotient_degree_bound() for pa in self.permutation_arguments]
-        return out
-
-    def _quotient_degree_bounds_cached(self, challenges, terminals):
-        """all quotient degree bounds of a proof (:203-221) -- Table.all_quotient_degree_bounds of every table, then the permutation
-        arguments -- remembered per SHAPE of the inputs.  Which monomials of the composed constraints survive depends on the numeric
-        challenges, terminals and parameters only through cancellations (stark_brainfuck_amd/table.py: _degree_bounds); values that
-        look sampled (more than 32 significant bits) behave generically except with negligible probability, small ones (zero, the
-        `iota^0 = 1` of an IO table without padding, a crafted test value) are part of the key as they are.  The per-table code draws the
-        same line but falls back to the exact symbolic expansion whenever ANY value is small -- every proof of a program without input
-        does, 160 us of host time between the two native calls."""
-        values = list(challenges) + list(terminals) + [p for t in self.tables for p in t.air_params(challenges)]
-        sampled = [v for v in values if v[0] >> 32 or v[1] or v[2]]
-        if len(set(sampled)) == len(sampled):
-            key = (tuple(t.height for t in self.tables), tuple(t.length for t in self.tables[3:]),
-                   tuple("s" if (v[0] >> 32 or v[1] or v[2]) else tuple(v) for v in values))
-            hit = BrainfuckStark._bounds_cache.get(key)
-            if hit is not None:
-                return list(hit)
-        else:
-            key = None
-        out = [b for table in self.tables for b in table.all_quotient_degree_bounds(challenges, terminals)]
+        different amount than the generic bounds say.  So the terminal constraints -- the only ones the terminals enter -- take the exact
+        expansion there (nine small constraints, ~50 us); boundary and transition bounds depend on the challenges alone.
+        cached, for the native prover: remembered per SHAPE of the inputs.  Which monomials of the composed constraints survive depends
+        on the numeric challenges, terminals and parameters only through cancellations (table.py: _degree_bounds); values that look
+        sampled (more than 32 significant bits) behave generically except with negligible probability, small ones (zero, the `iota^0 = 1`
+        of an IO table without padding, a crafted test value) are part of the key as they are.  The per-table code draws the same line but
+        falls back to the exact expansion whenever ANY value is small -- every proof of a program without input does, 160 us of host time."""
+        key = None
+        if cached:
+            assert not exact_terminals
+            values = list(challenges) + list(terminals) + [p for t in self.tables for p in t.air_params(challenges)]
+            sampled = [v for v in values if v[0] >> 32 or v[1] or v[2]]
+            if len(set(sampled)) == len(sampled):
+                key = (tuple(t.height for t in self.tables), tuple(t.length for t in self.tables[3:]),
+                       tuple("s" if (v[0] >> 32 or v[1] or v[2]) else tuple(v) for v in values))
+                hit = BrainfuckStark._bounds_cache.get(key)
+                if hit is not None:
+                    return list(hit)
+        out = [b for table in self.tables for b in table.all_quotient_degree_bounds(challenges, terminals, exact_terminals=exact_terminals)]
         out += [pa.quotient_degree_bound() for pa in self.permutation_arguments]
         if key is not None:
             if len(BrainfuckStark._bounds_cache) > 1024:
@@ -525,278 +652,196 @@ class BrainfuckStark:
             terminal_objects[3] = terminal_objects[2]
         return terminal_objects
 
+    # ---- the Python stage driver: one method per stage, named after the `timing` key the stage ends on, over one per-proof record `p`
     def _prove(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None):
         assert len(processor_matrix) + len(program) == len(instruction_matrix)
         proof = self._prove_native(program, (processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix), proof_stream)
         if proof is not None:
             return proof
-        lib, stream = _lib.load(), current_stream()
-        xf, n = self.xfield, self.fri.domain.length
-        log_n = n.bit_length() - 1
-        domain = self.fri.domain
-        import time
-        self.timing = {}
-        mark = [time.perf_counter()]
-        sync_stages = self.stage_timing
-        def lap(name):
+        self.timing, sync_stages, stream, mark = {}, self.stage_timing, current_stream(), time.perf_counter()
+        # the per-proof record (nothing in it refers to this object): the matrices in the order of self.tables and what else is given; the stages
+        # add draw, randomizer_polynomial, randomizer_codeword, prepared_extension, rows (the _RowBuilder), base_tree, challenges, terminals,
+        # extension_tree, weights_seed, combination, combination_tree, indices, unit_distances, known (the opened combination leaves), proof
+        p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
+                            domain=self.fri.domain, n=self.fri.domain.length, stream=stream, quotient_degree_bounds=None, quotient_buffers=[])
+        for name, stage in (("pad", self._stage_pad),           # (includes the randomizer's GPU time where it outlasts the padding)
+                            ("randomizer", None), ("base_lde", self._stage_base_lde), ("base_tree", self._stage_base_tree),
+                            ("extend", self._stage_extend), ("ext_lde", self._stage_ext_lde), ("ext_tree", self._stage_ext_tree),
+                            ("quotients", self._stage_quotients), ("combination", self._stage_combination),
+                            ("combination_tree", self._stage_combination_tree), ("openings", self._stage_openings),
+                            ("fri", self._stage_fri), ("serialize", self._stage_serialize)):
+            if stage is not None:
+                stage(p)
             if sync_stages:
                 synchronize(stream)
             now = time.perf_counter()
-            self.timing[name] = self.timing.get(name, 0.0) + now - mark[0]
-            mark[0] = now
+            self.timing[name], mark = now - mark, now
+        return p.proof
 
-        # randomizer polynomial and codeword (:162-167) -- queued FIRST: padding (:143-148) is host work that draws no randomness, so the
-        # GPU expands and transforms the randomizer while the host pads (the order of the random draws is the reference's either way)
-        count = self.max_degree + 1
-        import os
-        draw = random_source(urandom)    # the module's urandom, or this context's shared stream (randomness.override)
-        if draw is os.urandom or getattr(draw, "expand_on_device", False):
-            # production: coefficients expanded on the GPU from 32 bytes of the system's (or the ranks' shared) randomness
-            randomizer_polynomial = XArray.empty(count, xf)
-            _lib.check(lib.bfs_xfe_sample_fill(draw(32), randomizer_polynomial.ptr, count, count, stream))
-        else:                            # a test replaced urandom: the reference's byte stream, `count` draws of 27 bytes
-            randomizer_polynomial = XArray.from_numpy(sample_ext_many(draw(3 * 9 * count), count, 9), xf)
-        randomizer_codeword = domain.xevaluate(randomizer_polynomial, xf, as_array=True)
-
-        for table, matrix in zip(self.tables, (processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix)):
+    def _stage_pad(self, p):
+        """randomizer polynomial and codeword (:162-167) -- queued FIRST: padding (:143-148) is host work that draws no randomness, so the
+        GPU expands and transforms the randomizer while the host pads (the order of the random draws is the reference's either way)"""
+        xf, count = self.xfield, self.max_degree + 1
+        p.draw = random_source(urandom)    # the module's urandom, read now, or this context's shared stream (randomness.override)
+        seed, blob = _seed_or_stream(p.draw, 3 * 9 * count)      # `count` draws of 27 bytes
+        if seed is not None:
+            p.randomizer_polynomial = XArray.empty(count, xf)
+            _lib.check(_lib.load().bfs_xfe_sample_fill(seed, p.randomizer_polynomial.ptr, count, count, p.stream))
+        else:
+            p.randomizer_polynomial = XArray.from_numpy(sample_ext_many(blob, count, 9), xf)
+        p.randomizer_codeword = p.domain.xevaluate(p.randomizer_polynomial, xf, as_array=True)
+        for table, matrix in zip(self.tables, p.matrices):
             table.matrix = matrix
         for table in (self.processor_table, self.memory_table, self.instruction_table, self.input_table, self.output_table):
             table.pad()                                                                      # :143-148
-        if proof_stream is None:
-            proof_stream = ProofStream()
-        lap("pad")           # (includes the randomizer's GPU time where it outlasts the padding)
-        lap("randomizer")
-        # base codewords of all tables, one commitment to the zipped rows (:169-179)
-        lde_tables(self.tables, domain)
-        base_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.base_width)]
-        prepared_extension = prepare_extension(self.tables)      # host work (row masks) behind the transform that has just been queued
-        lap("base_lde")
-        f2 = BrainfuckStark.field
+        if p.proof_stream is None:
+            p.proof_stream = ProofStream()
 
-        fetched_base, fetched_ext = {}, {}      # row -> words, filled by the batched gather of the openings
+    def _stage_base_lde(self, p):          # base codewords of all tables (:169-172)
+        lde_tables(self.tables, p.domain)
+        p.prepared_extension = prepare_extension(self.tables)      # host work (row masks) behind the transform that has just been queued
 
-        # the closures below outlive this call inside the trees' lazy leaf lists: they must not hold `self`, or a prover object
-        # kept with its trees (keep_intermediates) becomes a reference cycle and its HBM waits for a full garbage collection
-        tables = self.tables
+    def _stage_base_tree(self, p):          # one commitment to the zipped rows of randomizer and base codewords (:174-179)
+        p.rows = _RowBuilder(self._layout, p.n, p.randomizer_codeword, BrainfuckStark.field, self.xfield)
+        columns = [(p.randomizer_codeword.ptr, True, 0)] + [(address, False, 0) for _, _, address, _ in self._layout.device_columns(p.n, 0)]
+        p.base_tree = self._zipped_tree(columns, p.n, p.rows.base_row)
+        p.proof_stream.push(p.base_tree.root())
 
-        def base_requests(i):
-            return [(randomizer_codeword.ptr + 8 * i, 3, randomizer_codeword.stride)] + [(t.base_codewords.ptr + 8 * i, t.base_width, n) for t in tables]
-
-        from .arrays import _fastlist
-        internal_field = xf.modulus.coefficients[0].field
-
-        def base_row(i):         # only opened rows are ever read back
-            words = fetched_base[i] if i in fetched_base else gather(base_requests(i))
-            if _fastlist is not None:     # the same objects, made in C (cpyext/fastlist.c): 16 elements in 3 us instead of 16
-                tail = _fastlist.unpack_base(np.ascontiguousarray(words[3:], dtype=np.uint64), BaseFieldElement, f2)
-                return tuple([xf.from_limbs([int(v) for v in words[:3]])] + tail)
-            return tuple([xf.from_limbs([int(v) for v in words[:3]])] + [BaseFieldElement(int(v), f2) for v in words[3:]])
-        base_columns = [(randomizer_codeword.ptr, True, 0)]
-        for t in self.tables:
-            base_columns += [(t.base_codewords.ptr + 8 * c * n, False, 0) for c in range(t.base_width)]
-        base_tree = self._zipped_tree(base_columns, n, base_row)
-        proof_stream.push(base_tree.root())
-        lap("base_tree")
-
-        # challenges, initials, table extension, terminals (:181-192)
-        challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.prover_fiat_shamir()))
-        initials = [sample_ext(draw(3 * 8)) for _ in self.permutation_arguments]
-        extend_tables_device(self.tables, challenges, initials, prepared=prepared_extension)   # prefix scans on the trace columns lde() left in HBM
-        terminals = self.get_terminals()
+    def _stage_extend(self, p):          # challenges, initials, table extension, terminals (:181-192)
+        p.challenges = tuple(BrainfuckStark._sample_weights(11, p.proof_stream.prover_fiat_shamir()))
+        initials = [sample_ext(p.draw(3 * 8)) for _ in self.permutation_arguments]
+        extend_tables_device(self.tables, p.challenges, initials, prepared=p.prepared_extension)   # prefix scans on the trace columns lde() left in HBM
+        p.terminals = self.get_terminals()
         if self.check_air:              # the trace against the AIR it is about to be proven for, on the columns in HBM
-            violations = [v for t in self.tables if t.length for v in t.air_violations(challenges, terminals)]
+            violations = [v for t in self.tables if t.length for v in t.air_violations(p.challenges, p.terminals)]
             if violations:
                 raise AirViolationError(violations)
-        lap("extend")
 
-        # extension codewords and their commitment (:194-201)
-        lde_tables(self.tables, domain, extension=True)
-        extension_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.full_width - t.base_width)]
-        early_quotient_bounds = None
+    def _stage_ext_lde(self, p):          # extension codewords (:194-195)
+        lde_tables(self.tables, p.domain, extension=True)
         if not self.keep_intermediates:
             # the quotient degree bounds (:203-221) are host work on challenges and terminals: done here, while the GPU runs the coset
             # transform of the extension columns that lde_tables has just queued
-            early_quotient_bounds = [b for table in self.tables for b in table.all_quotient_degree_bounds(challenges, terminals)]
-            early_quotient_bounds += [pa.quotient_degree_bound() for pa in self.permutation_arguments]
-        lap("ext_lde")
-        num_ext_columns = sum(t.full_width - t.base_width for t in self.tables)
-        moduli = [m for t in self.tables for m in t.ext_sharing_moduli(n)]
-        internal = xf.modulus.coefficients[0].field
-        shared = [dict() for _ in moduli]          # per column: i mod modulus -> the coefficient objects of that class
+            p.quotient_degree_bounds = self._quotient_degree_bounds(p.challenges, p.terminals)
 
-        def ext_requests(i):
-            return [(t.ext_codewords.ptr + 8 * i, 3 * (t.full_width - t.base_width), n) for t in tables]
+    def _stage_ext_tree(self, p):          # the commitment to the zipped rows of the extension codewords (:197-201)
+        p.rows.share([m for t in self.tables for m in t.ext_sharing_moduli(p.n)])
+        columns = [(address, True, 0) for _, _, address, _ in self._layout.device_columns(p.n, 1)]
+        p.extension_tree = self._zipped_tree(columns, p.n, p.rows.ext_row)
+        p.proof_stream.push(p.extension_tree.root())
 
-        plain_columns = [c for c in range(num_ext_columns) if moduli[c] is None]
+    def _stage_quotients(self, p):
+        """quotients (:203-221).  keep_intermediates (tests): the quotient codewords are written out and summed by bfs_combination, as the
+        reference does; otherwise they only ever exist in registers (bfs_air_combine).  Same field elements either way."""
+        if not self.keep_intermediates:
+            return
+        domain = p.domain
+        p.quotient_buffers = [(table.all_quotients(domain, None, p.challenges, p.terminals), table.num_quotients()) for table in self.tables]
+        p.quotient_buffers += [(pa.quotient(domain), 1) for pa in self.permutation_arguments]
+        p.quotient_degree_bounds = self._quotient_degree_bounds(p.challenges, p.terminals)
+        from . import debug_checks
+        if debug_checks.enabled():
+            debug_checks.check_prover(self, p.quotient_buffers, self._layout.column_degree_bounds(), p.quotient_degree_bounds)
 
-        def ext_row(i):
-            words = fetched_ext[i] if i in fetched_ext else gather(ext_requests(i))
-            row = []
-            made = None
-            if _fastlist is not None and plain_columns:
-                # the elements without shared coefficient objects, all at once: limb planes (3, k) -> k ExtensionFieldElements
-                soa = np.ascontiguousarray(np.asarray(words, dtype=np.uint64).reshape(num_ext_columns, 3)[plain_columns].T)
-                made = dict(zip(plain_columns, _fastlist.unpack_ext(soa, ExtensionFieldElement, Polynomial, BaseFieldElement, xf, internal_field)))
-            for c in range(num_ext_columns):
-                if made is not None and c in made:
-                    row.append(made[c])
-                    continue
-                limbs = [int(v) for v in words[3 * c:3 * c + 3]]
-                if moduli[c] is None:
-                    row.append(xf.from_limbs(limbs))
-                    continue
-                while limbs and limbs[-1] == 0:
-                    limbs.pop()
-                objs = shared[c].setdefault(i % moduli[c], [BaseFieldElement(v, internal) for v in limbs])
-                e = ExtensionFieldElement(Polynomial(objs), xf)
-                e.shares_coefficients = True
-                row.append(e)
-            return tuple(row)
-        ext_columns = []
-        for t in self.tables:
-            ext_columns += [(t.ext_codewords.ptr + 8 * 3 * c * n, True, 0) for c in range(t.full_width - t.base_width)]
-        extension_tree = self._zipped_tree(ext_columns, n, ext_row)
-        proof_stream.push(extension_tree.root())
-        lap("ext_tree")
-
-        # quotients (:203-221)
-        # keep_intermediates (tests): the quotient codewords are written out and summed by bfs_combination, as the reference
-        # does; otherwise they only ever exist in registers (bfs_air_combine below).  Same field elements either way.
-        quotient_buffers, quotient_degree_bounds = [], []
-        if early_quotient_bounds is not None:
-            quotient_degree_bounds = early_quotient_bounds
-        else:
-            for table in self.tables:
-                quotient_buffers.append((table.all_quotients(domain, None, challenges, terminals), table.num_quotients()))
-                quotient_degree_bounds += table.all_quotient_degree_bounds(challenges, terminals)
-            for pa in self.permutation_arguments:
-                quotient_buffers.append((pa.quotient(domain), 1))
-                quotient_degree_bounds.append(pa.quotient_degree_bound())
-            from . import debug_checks
-            if debug_checks.enabled():
-                # the reference checks each table's quotients inside all_quotients (before the terminals are pushed) ...
-                supports = [debug_checks.check_table_quotients(table, buf, n, domain.omega.value)
-                            for table, (buf, _) in zip(self.tables, quotient_buffers)]
-                supports += [debug_checks.support(buf.ptr, 3, count, n, domain.omega.value) for buf, count in quotient_buffers[len(self.tables):]]
-                # ... and the terms of the combination while it assembles them (after the weights are sampled; nothing in between
-                # depends on the outcome, so both sets run here)
-                debug_checks.check_terms(self, n, domain.omega.value, base_degree_bounds, extension_degree_bounds, supports, quotient_degree_bounds)
-
-        lap("quotients")
-        terminal_objects = self._terminal_objects(terminals)          # :223-224
-        for t in terminal_objects:
-            proof_stream.push(t)
-
-        # weights of the non-linear combination (:226-243)
-        num_base = sum(t.base_width for t in self.tables)
-        num_ext = sum(t.full_width - t.base_width for t in self.tables)
-        num_quot = len(quotient_degree_bounds)
-        weights_seed = proof_stream.prover_fiat_shamir()
-        weight_array = BrainfuckStark._sample_weights(1 + 2 * (num_base + num_ext + num_quot), weights_seed, as_array=True)
+    def _stage_combination(self, p):          # terminals (:223-224), weights (:226-243) and the non-linear combination (:245-298)
+        for t in self._terminal_objects(p.terminals):
+            p.proof_stream.push(t)
+        p.weights_seed = p.proof_stream.prover_fiat_shamir()
+        weight_array = BrainfuckStark._sample_weights(self._layout.weight_count, p.weights_seed, as_array=True)
         weight0 = tuple(int(v) for v in weight_array[0])
-
-        # terms in the order of the reference's `terms` list (:245-293): base, extension, quotient codewords; term s has the
-        # weights 1 + 2s, 2 + 2s and is shifted to the common degree bound.  One row of seven words per term (bfs_comb_weight).
-        bounds = base_degree_bounds + extension_degree_bounds + quotient_degree_bounds
-        assert 1 + 2 * len(bounds) == len(weight_array)
-        terms = np.empty((len(bounds), 7), dtype=np.uint64)
-        terms[:, 0:3] = weight_array[1::2]
-        terms[:, 3:6] = weight_array[2::2]
-        terms[:, 6] = [self.max_degree - bound for bound in bounds]
+        # terms in the order of the reference's `terms` list (_TermLayout); each is shifted to the common degree bound.  One row of seven
+        # words per term (bfs_comb_weight).
+        shifts = self._layout.shifts(p.quotient_degree_bounds)
+        assert 1 + 2 * len(shifts) == len(weight_array)
+        terms = np.empty((len(shifts), 7), dtype=np.uint64)
+        terms[:, 0:3], terms[:, 3:6], terms[:, 6] = weight_array[1::2], weight_array[2::2], shifts
         if self._shift_tweak is not None:
             terms[:, 6] = self._shift_tweak(terms[:, 6])
-
-        def term_of(s):
-            return tuple(int(v) for v in terms[s, 0:3]), tuple(int(v) for v in terms[s, 3:6]), int(terms[s, 6])
-        combination = XArray.empty(n, xf)
+        p.combination = XArray.empty(p.n, self.xfield)
         if self.keep_intermediates:
-            sources = []
-            for t in self.tables:
-                for c in range(t.base_width):
-                    sources.append((t.base_codewords.ptr + 8 * c * n, 0))
-            for t in self.tables:
-                for c in range(t.full_width - t.base_width):
-                    sources.append((t.ext_codewords.ptr + 8 * 3 * c * n, 1))
-            for buf, count in quotient_buffers:
-                for q in range(count):
-                    sources.append((buf.ptr + 8 * 3 * q * n, 1))
-            assert len(sources) == len(bounds)
-            srcs = (_lib.CombSource * len(sources))()
-            for s, (ptr, is_ext) in enumerate(sources):
-                wa, wb, shift = term_of(s)
-                srcs[s].ptr, srcs[s].is_ext, srcs[s].shift = ptr, is_ext, shift
-                srcs[s].wa = (_u64 * 3)(*wa)
-                srcs[s].wb = (_u64 * 3)(*wb)
-            _lib.check(lib.bfs_combination(srcs, len(sources), randomizer_codeword.ptr, (_u64 * 3)(*weight0), combination.ptr,
-                                           log_n, domain.offset.value, domain.omega.value, stream))
+            self._combine_written_out(p, terms, weight0)
         else:
-            # a cooperative proof (cooperate()): the stage is pointwise, every rank holds all codewords (a row's neighbour at
-            # unit_distance comes from the rank's own copy), so each rank does its own rows and the ranks all-gather the combination.
-            # _row_windows (tests): the same row-window entry points on one GPU, the domain cut into arbitrary pieces.
-            rows = None
-            if self._cooperation is not None:
-                from .shard import row_range
-                rows = row_range(n, self._cooperation[0], self._cooperation[1])
-            windows = [rows]
-            if rows is None and self._row_windows is not None:
-                windows = list(self._row_windows)
-                # run in the order given (every window initialises its own rows of the accumulator): any order of a tiling
-                ends = [first + count for first, count in sorted(windows)]
-                assert [first for first, _ in sorted(windows)] == [0] + ends[:-1] and ends[-1] == n, "the windows must tile the domain"
-            for window in windows:
-                inverse_buffer, inverses = zerofier_inverses(self.tables, domain, rows=window)      # all zerofier denominators, one inversion per point
-                base_at = ext_at = 0
-                quot_at = num_base + num_ext
-                for k, t in enumerate(self.tables):
-                    bw, xw, nq = t.base_width, t.full_width - t.base_width, t.num_quotients()
-                    mine = np.concatenate([terms[base_at:base_at + bw], terms[num_base + ext_at:num_base + ext_at + xw], terms[quot_at:quot_at + nq]])
-                    t.combine_into(domain, challenges, terminals, mine, combination,
-                                   randomizer=randomizer_codeword if k == 0 else None, randomizer_weight=weight0, inverses=inverses[t], rows=window)
-                    base_at, ext_at, quot_at = base_at + bw, ext_at + xw, quot_at + nq
-                for pa in self.permutation_arguments:
-                    pa.combine_into(domain, term_of(quot_at), combination, inv_x_minus_1=inverses[self.tables[0]][0], rows=window)
-                    quot_at += 1
-                assert quot_at == len(terms)
-                inverse_buffer.free()
-            if rows is not None:
-                from .shard import all_gather_rows
-                world_size, rank, group, device = self._cooperation
-                all_gather_rows(combination.ptr, n, 3, combination.stride, world_size, rank, group=group, device=device, stream=stream)
+            self._combine_fused(p, terms, weight0)
+            BrainfuckStark._release(p.randomizer_polynomial, *[buf for buf, _ in p.quotient_buffers])
+            p.quotient_buffers = []
 
-        if not self.keep_intermediates:
-            BrainfuckStark._release(randomizer_polynomial, *[buf for buf, _ in quotient_buffers])
-            quotient_buffers = []
-        lap("combination")
-        # commitment to the combination codeword, openings (:300-333)
-        combination_tree = Merkle(combination)
-        proof_stream.push(combination_tree.root())
-        lap("combination_tree")          # (GPU work: 2^22 extension leaves are 1.1 ms; the round-3 breakdown counted it under "openings")
-        indices = BrainfuckStark.sample_indices(self.security_level, proof_stream.prover_fiat_shamir(), n)
-        unit_distances = list(set(table.unit_distance(n) for table in self.tables))
-        known = self._openings_native(proof_stream, base_tree, extension_tree, combination, combination_tree, base_requests(0),
-                                      ext_requests(0), moduli, indices, unit_distances, n, f2, xf, lib, stream)
-        if known is None:
-            known = self._openings_python(proof_stream, base_tree, extension_tree, combination, combination_tree, base_requests,
-                                          ext_requests, fetched_base, fetched_ext, indices, unit_distances, n, xf)
+    @staticmethod
+    def _term(terms, s):
+        return tuple(int(v) for v in terms[s, 0:3]), tuple(int(v) for v in terms[s, 3:6]), int(terms[s, 6])
 
+    def _combine_written_out(self, p, terms, weight0):
+        """bfs_combination: one weighted sum over the column codewords and the quotient codewords that _stage_quotients wrote out"""
+        n, domain = p.n, p.domain
+        sources = [(address, ext) for ext in (0, 1) for _, _, address, _ in self._layout.device_columns(n, ext)]
+        sources += [(buf.ptr + 8 * 3 * q * n, 1) for buf, count in p.quotient_buffers for q in range(count)]
+        assert len(sources) == len(terms)
+        srcs = (_lib.CombSource * len(sources))()
+        for s, (ptr, is_ext) in enumerate(sources):
+            wa, wb, shift = self._term(terms, s)
+            srcs[s].ptr, srcs[s].is_ext, srcs[s].shift = ptr, is_ext, shift
+            srcs[s].wa, srcs[s].wb = (_u64 * 3)(*wa), (_u64 * 3)(*wb)
+        _lib.check(_lib.load().bfs_combination(srcs, len(sources), p.randomizer_codeword.ptr, (_u64 * 3)(*weight0), p.combination.ptr,
+                                               n.bit_length() - 1, domain.offset.value, domain.omega.value, p.stream))
+
+    def _combine_fused(self, p, terms, weight0):
+        """bfs_air_combine: every table's columns and quotients folded into the accumulator, the quotients never written out.
+        A cooperative proof (cooperate()): the stage is pointwise, every rank holds all codewords (a row's neighbour at unit_distance
+        comes from the rank's own copy), so each rank does its own rows and the ranks all-gather the combination.
+        _row_windows (tests): the same row-window entry points on one GPU, the domain cut into arbitrary pieces."""
+        n, domain, layout = p.n, p.domain, self._layout
+        rows = None
+        if self._cooperation is not None:
+            from .shard import row_range
+            rows = row_range(n, self._cooperation[0], self._cooperation[1])
+        windows = [rows]
+        if rows is None and self._row_windows is not None:
+            windows = list(self._row_windows)
+            # run in the order given (every window initialises its own rows of the accumulator): any order of a tiling
+            ends = [first + count for first, count in sorted(windows)]
+            assert [first for first, _ in sorted(windows)] == [0] + ends[:-1] and ends[-1] == n, "the windows must tile the domain"
+        for window in windows:
+            inverse_buffer, inverses = zerofier_inverses(self.tables, domain, rows=window)      # all zerofier denominators, one inversion per point
+            for k, t in enumerate(self.tables):
+                mine = np.concatenate([terms[layout.base[k]], terms[layout.ext[k]], terms[layout.quot[k]]])
+                t.combine_into(domain, p.challenges, p.terminals, mine, p.combination, randomizer=p.randomizer_codeword if k == 0 else None,
+                               randomizer_weight=weight0, inverses=inverses[t], rows=window)
+            for j, pa in enumerate(self.permutation_arguments):
+                pa.combine_into(domain, self._term(terms, layout.first_argument + j), p.combination, inv_x_minus_1=inverses[self.tables[0]][0],
+                                rows=window)
+            inverse_buffer.free()
+        if rows is not None:
+            from .shard import all_gather_rows
+            world_size, rank, group, device = self._cooperation
+            all_gather_rows(p.combination.ptr, n, 3, p.combination.stride, world_size, rank, group=group, device=device, stream=p.stream)
+
+    def _stage_combination_tree(self, p):
+        """commitment to the combination codeword (:300-302).  (GPU work: 2^22 extension leaves are 1.1 ms)"""
+        p.combination_tree = Merkle(p.combination)
+        p.proof_stream.push(p.combination_tree.root())
+
+    def _stage_openings(self, p):          # the opened rows and combination leaves (:304-333)
+        p.indices = BrainfuckStark.sample_indices(self.security_level, p.proof_stream.prover_fiat_shamir(), p.n)
+        p.unit_distances = self._layout.unit_distances(p.n)
+        p.known = self._openings_native(p)
+        if p.known is None:
+            p.known = self._openings_python(p)
         if not self.keep_intermediates:
-            BrainfuckStark._release(base_tree, extension_tree, randomizer_codeword, *self.tables)
-            base_tree = extension_tree = None
-        lap("openings")
-        # low-degree test of the combination codeword (:335-336)
-        self.fri.prove(combination, proof_stream, known_leafs=known, round0_tree=combination_tree)   # round 0 commits to this very tree
-        self._last = {"challenges": challenges, "terminals": terminals, "indices": indices, "weights_seed": weights_seed,
-                      "quotient_degree_bounds": quotient_degree_bounds}
+            BrainfuckStark._release(p.base_tree, p.extension_tree, p.randomizer_codeword, *self.tables)
+            p.base_tree = p.extension_tree = None
+
+    def _stage_fri(self, p):
+        """low-degree test of the combination codeword (:335-336); round 0 commits to the combination tree that was just built"""
+        self.fri.prove(p.combination, p.proof_stream, known_leafs=p.known, round0_tree=p.combination_tree)
+        self._last = {"challenges": p.challenges, "terminals": p.terminals, "indices": p.indices, "weights_seed": p.weights_seed,
+                      "quotient_degree_bounds": p.quotient_degree_bounds}
         if self.keep_intermediates:
-            self._last.update({"base_tree": base_tree, "extension_tree": extension_tree, "combination_tree": combination_tree,
-                               "quotient_buffers": quotient_buffers, "combination": combination,
-                               "randomizer_codeword": randomizer_codeword})
+            self._last.update({"base_tree": p.base_tree, "extension_tree": p.extension_tree, "combination_tree": p.combination_tree,
+                               "quotient_buffers": p.quotient_buffers, "combination": p.combination, "randomizer_codeword": p.randomizer_codeword})
         else:
-            BrainfuckStark._release(combination, combination_tree)
-        lap("fri")
-        proof = proof_stream.serialize()
-        lap("serialize")
-        return proof
+            BrainfuckStark._release(p.combination, p.combination_tree)
+
+    def _stage_serialize(self, p):
+        p.proof = p.proof_stream.serialize()
 
     # ------------------------------------------------------------------------------------------------------------
     def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):
@@ -859,8 +904,6 @@ class BrainfuckStark:
         """brainfuck_stark.py:343-579 -- host only, like the reference's verifier: Merkle paths of the opened rows, the
         non-linear combination recomputed from the opened rows (constraints evaluated through air.evaluate), FRI, and the
         terminals against the public input, output and program."""
-        from .air import X0, xadd, xmul, xscale
-        P = air.P
         if proof_stream is None and self.native_stages:
             verdict = self._verify_native(proof)
             if verdict is not None:
@@ -868,22 +911,21 @@ class BrainfuckStark:
         if proof_stream is None:
             proof_stream = ProofStream()
         proof_stream = proof_stream.deserialize(proof)
-        if hasattr(proof_stream, "pickle_of"):
-            # leaf preimages (pickle.dumps of an opened row / element) come from the native copy of the stream while this call runs
-            from .merkle import leaf_pickle_source
-            token = leaf_pickle_source.set(proof_stream.pickle_of)
-            try:
-                return self._verify_checked(proof_stream)
-            finally:
+        # leaf preimages (pickle.dumps of an opened row / element) come from the native copy of the stream while this call runs
+        token = leaf_pickle_source.set(proof_stream.pickle_of) if hasattr(proof_stream, "pickle_of") else None
+        try:
+            return self._verify_stream(proof_stream)
+        except _MalformedProof:
+            return False
+        finally:
+            if token is not None:
                 leaf_pickle_source.reset(token)
-        return self._verify_checked(proof_stream)
 
     def _verify_native(self, proof):
         """verify() on the native object graph of the proof (csrc/verifier.cpp: bfs_stark_verify_begin / _finish): the same checks in the same
         order as _verify_stream / Fri.verify below, without a Python object per pulled item.  Returns True / False, raises the reference's
         AssertionError -- or returns None when this route does not apply (the bytes are not something the native reader takes, or the stream
         holds an object the native checks do not model): the Python verifier below then decides, as the reference would."""
-        import os
         if os.environ.get("BFS_NATIVE_VERIFY", "1") == "0":
             return None
         from .ip import NativeTranscript
@@ -894,9 +936,8 @@ class BrainfuckStark:
         t = NativeTranscript.from_bytes(data)
         if t is None:
             return None
-        lib = _lib.load()
-        n = self.fri.domain.length
-        unit_distances = list(set(table.unit_distance(n) for table in self.tables))
+        lib, n = _lib.load(), self.fri.domain.length
+        unit_distances = self._layout.unit_distances(n)
         if len(unit_distances) > 8:
             return None
         words = (_u64 * max(len(self.program), 1))(*[w.value if hasattr(w, "value") else int(w) for w in self.program])
@@ -909,165 +950,123 @@ class BrainfuckStark:
         params.heights = (_u64 * 5)(*[t_.height for t_ in self.tables])
         params.lengths = (_u64 * 5)(*[t_.length for t_ in self.tables])
         params.omicrons = (_u64 * 5)(*[t_.omicron.value for t_ in self.tables])
-        params.num_distances = len(unit_distances)
-        params.distances = (_u64 * 8)(*(unit_distances + [0] * (8 - len(unit_distances))))
+        params.num_distances, params.distances = len(unit_distances), (_u64 * 8)(*(unit_distances + [0] * (8 - len(unit_distances))))
         params.program, params.program_len = ctypes.addressof(words), len(self.program)
         params.input, params.n_input = ctypes.addressof(ins), len(self.input_symbols)
         params.output, params.n_output = ctypes.addressof(outs), len(self.output_symbols)
         out_ch, out_tm, verdict = (_u64 * 33)(), (_u64 * 15)(), ctypes.c_int(3)
         _lib.check(lib.bfs_stark_verify_begin(t.handle, ctypes.byref(params), out_ch, out_tm, ctypes.byref(verdict)))
-        if verdict.value == 2:
-            raise AssertionError(lib.bfs_last_error().decode("utf-8", "replace"))
+
+        def outcome():          # 1: accepted, 2: the reference's assertion, 3: this route does not apply, else refused
+            if verdict.value == 2:
+                raise AssertionError(lib.bfs_last_error().decode("utf-8", "replace"))
+            return None if verdict.value == 3 else verdict.value == 1
         if verdict.value != 1:
-            return None if verdict.value == 3 else False
-        challenges = tuple((out_ch[3 * i], out_ch[3 * i + 1], out_ch[3 * i + 2]) for i in range(11))
-        terminals = [(out_tm[3 * i], out_tm[3 * i + 1], out_tm[3 * i + 2]) for i in range(5)]
-        bounds = [t_.interpolant_degree() for t_ in self.tables for _ in range(t_.base_width)]
-        bounds += [t_.interpolant_degree() for t_ in self.tables for _ in range(t_.full_width - t_.base_width)]
-        bounds += self._quotient_degree_bounds_verifier(challenges, terminals)
-        shifts = (_u64 * len(bounds))(*[self.max_degree - b for b in bounds])
-        _lib.check(lib.bfs_stark_verify_finish(t.handle, ctypes.byref(params), shifts, len(bounds), ctypes.byref(verdict)))
-        if verdict.value == 2:
-            raise AssertionError(lib.bfs_last_error().decode("utf-8", "replace"))
-        if verdict.value == 3:
-            return None
-        return verdict.value == 1
+            return outcome()
+        challenges, terminals = tuple(_triples(out_ch, 11)), _triples(out_tm, 5)
+        shifts = self._layout.shifts(self._quotient_degree_bounds(challenges, terminals, exact_terminals=True))
+        _lib.check(lib.bfs_stark_verify_finish(t.handle, ctypes.byref(params), (_u64 * len(shifts))(*shifts), len(shifts), ctypes.byref(verdict)))
+        return outcome()
 
-    def _verify_checked(self, proof_stream):
-        try:
-            return self._verify_stream(proof_stream)
-        except _MalformedProof:
-            return False
-
+    # ---- the Python verifier, in the order of the reference's verify(): head, opened rows, per index the combination, tail
     def _verify_stream(self, proof_stream):
-        from .air import X0, xadd, xmul, xscale
-        P = air.P
-        n = self.fri.domain.length
-        offset, omega = self.fri.domain.offset.value, self.fri.domain.omega.value
-
-        def limbs(e):
-            """value of an element read from the proof, as canonical residues: the prover chooses the representation (any Python int
-            unpickles), the reference reduces in every operation (algebra.py:89-99) and so sees v mod p -- and so must every
-            consumer here: bfs_air_evaluate's host arithmetic assumes canonical operands and ctypes truncates above 2^64
-            (round-4 advice).  An extension element with more than three coefficients is not an element: the proof is refused."""
-            if hasattr(e, "limbs"):
-                c = e.limbs()
-                if len(c) != 3:
-                    raise _MalformedProof("extension element with %d coefficients" % len(c))
-                return (c[0] % P, c[1] % P, c[2] % P)
-            return (e.value % P, 0, 0)
-
-        base_root = proof_stream.pull()
-        challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.verifier_fiat_shamir()))
-        extension_root = proof_stream.pull()
-        terminal_objects = [proof_stream.pull() for _ in range(5)]
-        terminals = [limbs(t) for t in terminal_objects]
-        # ... and as STORED, for the three evaluation arguments at the end: the reference compares the pulled object with a computed
-        # element through Polynomial.__eq__ / BaseFieldElement.__eq__, i.e. the coefficient values as they were pickled (round-5 advice)
-        stored_terminals = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
-        # io_table.py:54-56, which the reference reaches through num_quotients below (brainfuck_stark.py:394-395): a non-empty input
-        # (output) table against a terminal stored as all zeros raises there instead of ending in False; input table first.  NOT where
-        # the claim's own symbols evaluate to zero too (a single symbol 0: `-+.`): such claims are proven and verified here, while the
-        # reference's prover stops at that very assertion.
-        for io, ea in zip((self.input_table, self.output_table), self.evaluation_arguments):
-            if io.height != 0 and not any(stored_terminals[io.terminal_index]):
-                assert not any(ea.compute_terminal(challenges)), "evaluation terminal for non-empty IOTable is zero but shouldn't be!"
-
-        base_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.base_width)]
-        extension_degree_bounds = [t.interpolant_degree() for t in self.tables for _ in range(t.full_width - t.base_width)]
-        num_base = sum(t.base_width for t in self.tables)
-        num_ext = sum(t.full_width - t.base_width for t in self.tables)
-        num_quot = sum(t.num_quotients(challenges, terminals) for t in self.tables)
-        weights = BrainfuckStark._sample_weights(1 + 2 * (num_base + num_ext + num_quot + len(self.permutation_arguments)),
-                                                 proof_stream.verifier_fiat_shamir(), as_array=True)
-        weights = np.ascontiguousarray(weights, dtype=np.uint64)      # (number, 3); stays alive for weights_raw below
-        weights_raw = weights.ctypes.data_as(ctypes.POINTER(_u64))
-        combination_root = proof_stream.pull()
-        indices = BrainfuckStark.sample_indices(self.security_level, proof_stream.verifier_fiat_shamir(), n)
-        unit_distances = list(set(table.unit_distance(n) for table in self.tables))
-
-        rows = {}
-        for index in indices:
-            for distance in [0] + unit_distances:
-                idx = (index + distance) % n
-                element = proof_stream.pull()
-                salt, path = proof_stream.pull()
-                assert SaltedMerkle.verify(base_root, idx, salt, path, element), "salted base tree verify must succeed for base codewords"
-                row = [limbs(e) for e in element]
-                element = proof_stream.pull()
-                salt, path = proof_stream.pull()
-                assert SaltedMerkle.verify(extension_root, idx, salt, path, element), \
-                    "salted base tree verify must succeed for extension codewords"
-                rows[idx] = row + [limbs(e) for e in element]
-
-        quotient_bounds = {t: (t.boundary_quotient_degree_bounds(challenges), t.transition_quotient_degree_bounds(challenges),
-                               t.terminal_quotient_degree_bounds(challenges, terminals, exact=True)) for t in self.tables}      # (exact: see _quotient_degree_bounds_verifier)
-        for index in indices:
-            x = offset * pow(omega, index, P) % P
-
-            powers = {}                 # x^shift for the few distinct shifts of a proof (151 terms share ~20 degree bounds)
-
-            def shifted(value, bound):
-                f = powers.get(bound)
-                if f is None:
-                    f = powers[bound] = pow(x, self.max_degree - bound, P)
-                return xscale(value, f)
-            row = rows[index]
-            terms = [row[0]]
-            for i in range(num_base):
-                terms += [row[1 + i], shifted(row[1 + i], base_degree_bounds[i])]
-            ext_offset = 1 + num_base
-            for i in range(num_ext):
-                terms += [row[ext_offset + i], shifted(row[ext_offset + i], extension_degree_bounds[i])]
-
-            # the rows of every table: base columns, then its extension columns
-            points, next_points = [], []
-            b, e = 1, ext_offset
-            for table in self.tables:
-                xw = table.full_width - table.base_width
-                nrow = rows[(index + table.unit_distance(n)) % n]
-                points.append(row[b:b + table.base_width] + row[e:e + xw])
-                next_points.append(nrow[b:b + table.base_width] + nrow[e:e + xw])
-                b, e = b + table.base_width, e + xw
-
-            boundary_inverse = pow((x - 1) % P, P - 2, P)
-            for table, point, next_point in zip(self.tables, points, next_points):
-                bb, tb, zb = quotient_bounds[table]
-                omicron_inverse = pow(table.omicron.value, P - 2, P)
-                boundary_values, transition_values, terminal_values = table.evaluate_all_constraints(point, next_point, challenges, terminals)
-                for value, bound in zip(boundary_values, bb):
-                    q = xscale(value, boundary_inverse)
-                    terms += [q, shifted(q, bound)]
-                if table.height == 0:
-                    transition_factor = 0
-                else:
-                    transition_factor = (x - omicron_inverse) * pow((pow(x, table.height, P) - 1) % P, P - 2, P) % P
-                for value, bound in zip(transition_values, tb):
-                    q = xscale(value, transition_factor)
-                    terms += [q, shifted(q, bound)]
-                terminal_inverse = pow((x - omicron_inverse) % P, P - 2, P)
-                for value, bound in zip(terminal_values, zb):
-                    q = xscale(value, terminal_inverse)
-                    terms += [q, shifted(q, bound)]
-            for arg in self.permutation_arguments:
-                q = xscale(arg.evaluate_difference(points), boundary_inverse)
-                terms += [q, shifted(q, arg.quotient_degree_bound())]
-            assert len(terms) == len(weights), f"length of terms ({len(terms)}) must be equal to length of weights ({len(weights)})"
+        head = self._verify_head(proof_stream)
+        rows = self._verify_opened_rows(proof_stream, head)
+        shifts = self._layout.shifts(self._quotient_degree_bounds(head.challenges, head.terminals, exact_terminals=True))
+        weights_raw = head.weights.ctypes.data_as(ctypes.POINTER(_u64))
+        for index in head.indices:
+            terms = self._combination_terms(head, rows, index, shifts)
+            assert len(terms) == len(head.weights), f"length of terms ({len(terms)}) must be equal to length of weights ({len(head.weights)})"
             flat = (_u64 * (3 * len(terms)))(*[v for t in terms for v in t])          # bfs_xfe_inner_product: 303 products natively
             got = (_u64 * 3)()
             _lib.check(_lib.load().bfs_xfe_inner_product(weights_raw, flat, len(terms), got))
             inner_product = (got[0], got[1], got[2])
-
             combination_leaf = proof_stream.pull()
             combination_path = proof_stream.pull()
-            if not Merkle.verify(combination_root, index, combination_path, combination_leaf):
+            if not Merkle.verify(head.combination_root, index, combination_path, combination_leaf):
                 return False
             # brainfuck_stark.py:567 compares the leaf OBJECT with the inner product (coefficient values as stored, algebra.py:36):
             # a leaf whose coefficients are not canonical residues is unequal there, and here
             if not hasattr(combination_leaf, "limbs") or tuple(combination_leaf.limbs()) != inner_product:
                 return False
-
-        verdict = self.fri.verify(proof_stream, combination_root)
+        verdict = self.fri.verify(proof_stream, head.combination_root)
         for ea in self.evaluation_arguments:
-            verdict = verdict and tuple(ea.select_terminal(stored_terminals)) == tuple(ea.compute_terminal(challenges))
+            verdict = verdict and tuple(ea.select_terminal(head.stored_terminals)) == tuple(ea.compute_terminal(head.challenges))
         return bool(verdict)
+
+    def _verify_head(self, proof_stream):
+        """everything up to the opened rows: roots, challenges, terminals, weights, indices (:357-413)"""
+        head = SimpleNamespace(base_root=proof_stream.pull())
+        head.challenges = challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.verifier_fiat_shamir()))
+        head.extension_root = proof_stream.pull()
+        terminal_objects = [proof_stream.pull() for _ in range(5)]
+        head.terminals = [_canonical_limbs(t) for t in terminal_objects]
+        # ... and as STORED, for the three evaluation arguments at the end: the reference compares the pulled object with a computed
+        # element through Polynomial.__eq__ / BaseFieldElement.__eq__, i.e. the coefficient values as they were pickled
+        head.stored_terminals = stored = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
+        # io_table.py:54-56, which the reference reaches through num_quotients below (brainfuck_stark.py:394-395): a non-empty input
+        # (output) table against a terminal stored as all zeros raises there instead of ending in False; input table first.  NOT where
+        # the claim's own symbols evaluate to zero too (a single symbol 0: `-+.`): such claims are proven and verified here, while the
+        # reference's prover stops at that very assertion.
+        for io, ea in zip((self.input_table, self.output_table), self.evaluation_arguments):
+            if io.height != 0 and not any(stored[io.terminal_index]):
+                assert not any(ea.compute_terminal(challenges)), "evaluation terminal for non-empty IOTable is zero but shouldn't be!"
+        weights = BrainfuckStark._sample_weights(self._layout.weight_count, proof_stream.verifier_fiat_shamir(), as_array=True)
+        head.weights = np.ascontiguousarray(weights, dtype=np.uint64)      # (number, 3)
+        head.combination_root = proof_stream.pull()
+        head.indices = BrainfuckStark.sample_indices(self.security_level, proof_stream.verifier_fiat_shamir(), self.fri.domain.length)
+        return head
+
+    def _verify_opened_rows(self, proof_stream, head):
+        """{row index: canonical limbs of its randomizer, base and extension elements}, every opened row checked against its root (:415-433)"""
+        n, rows, unit_distances = self.fri.domain.length, {}, self._layout.unit_distances(self.fri.domain.length)
+        for index in head.indices:
+            for distance in [0] + unit_distances:
+                idx = (index + distance) % n
+                element = proof_stream.pull()
+                salt, path = proof_stream.pull()
+                assert SaltedMerkle.verify(head.base_root, idx, salt, path, element), "salted base tree verify must succeed for base codewords"
+                row = [_canonical_limbs(e) for e in element]
+                element = proof_stream.pull()
+                salt, path = proof_stream.pull()
+                assert SaltedMerkle.verify(head.extension_root, idx, salt, path, element), "salted base tree verify must succeed for extension codewords"
+                rows[idx] = row + [_canonical_limbs(e) for e in element]
+        return rows
+
+    def _combination_terms(self, head, rows, index, shifts):
+        """the terms of the non-linear combination at domain point `index` (:435-560), from the opened rows: the randomizer, then every
+        term of the layout followed by its shifted copy"""
+        P, xscale, layout = air.P, air.xscale, self._layout
+        n, challenges, terminals = self.fri.domain.length, head.challenges, head.terminals
+        x = self.fri.domain.offset.value * pow(self.fri.domain.omega.value, index, P) % P
+        powers = {}                 # x^shift for the few distinct shifts of a proof (151 terms share ~20 degree bounds)
+
+        def with_shifted(value, s):
+            f = powers.get(shifts[s])
+            if f is None:
+                f = powers[shifts[s]] = pow(x, shifts[s], P)
+            return [value, xscale(value, f)]
+        row = rows[index]
+        terms = [row[0]]
+        for s in range(layout.num_columns):
+            terms += with_shifted(row[1 + s], s)
+        # the rows of every table at this point and at the next one: base columns, then its extension columns
+        points, next_points = [], []
+        for k, table in enumerate(self.tables):
+            columns, next_columns = row[1:], rows[(index + table.unit_distance(n)) % n][1:]
+            points.append(columns[layout.base[k]] + columns[layout.ext[k]])
+            next_points.append(next_columns[layout.base[k]] + next_columns[layout.ext[k]])
+        boundary_inverse = pow((x - 1) % P, P - 2, P)
+        for k, table in enumerate(self.tables):
+            omicron_inverse = pow(table.omicron.value, P - 2, P)
+            transition_factor = 0 if table.height == 0 else (x - omicron_inverse) * pow((pow(x, table.height, P) - 1) % P, P - 2, P) % P
+            # one over the zerofier of the boundary, the transition and the terminal constraints
+            factors = (boundary_inverse, transition_factor, pow((x - omicron_inverse) % P, P - 2, P))
+            s = layout.quot[k].start
+            for values, factor in zip(table.evaluate_all_constraints(points[k], next_points[k], challenges, terminals), factors):
+                for value in values:
+                    terms += with_shifted(xscale(value, factor), s)
+                    s += 1
+        for j, arg in enumerate(self.permutation_arguments):
+            terms += with_shifted(xscale(arg.evaluate_difference(points), boundary_inverse), layout.first_argument + j)
+        return terms

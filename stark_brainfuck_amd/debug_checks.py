@@ -86,6 +86,18 @@ def check_table_quotients(table, buffer, n, omega):
     return nonzero
 
 
+def check_prover(stark, quotient_buffers, column_degree_bounds, quotient_degree_bounds):
+    """every degree check of the reference's prover on the quotient codewords in HBM (`quotient_buffers`: (buffer, count) per table, then per
+    permutation argument) and on the terms of the combination"""
+    n, omega, num_base = stark.fri.domain.length, stark.fri.domain.omega.value, sum(t.base_width for t in stark.tables)
+    # the reference checks each table's quotients inside all_quotients (before the terminals are pushed) ...
+    supports = [check_table_quotients(table, buf, n, omega) for table, (buf, _) in zip(stark.tables, quotient_buffers)]
+    supports += [support(buf.ptr, 3, count, n, omega) for buf, count in quotient_buffers[len(stark.tables):]]
+    # ... and the terms of the combination while it assembles them (after the weights are sampled; nothing in between depends on the
+    # outcome, so both sets run here)
+    check_terms(stark, n, omega, column_degree_bounds[:num_base], column_degree_bounds[num_base:], supports, quotient_degree_bounds)
+
+
 def check_terms(stark, n, omega, base_degree_bounds, extension_degree_bounds, quotient_supports, quotient_degree_bounds):
     """brainfuck_stark.py:251-290: the terms of the non-linear combination, in the reference's order"""
     max_degree = stark.max_degree

@@ -110,6 +110,35 @@ def test_production_path_writes_the_reference_proof(name, monkeypatch):
         assert "quotient_buffers" not in stark._last
 
 
+PYTHON_STAGE_KEYS = ["pad", "randomizer", "base_lde", "base_tree", "extend", "ext_lde", "ext_tree", "quotients", "combination",
+                     "combination_tree", "openings", "fri", "serialize"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_python_stage_driver_writes_the_reference_proof(name, monkeypatch):
+    """native_stages = False: every stage driven from Python, the quotients folded into the combination in registers (the path of
+    cooperative proofs, plain-list matrices, stage_timing and row windows) -- the reference's proof from the reference's randomness,
+    and `timing` holds the stages in the order bench.py's breakdown and the native driver report them"""
+    from stark_brainfuck_amd import brainfuck_stark, salted_merkle, table
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    from stark_brainfuck_amd.vm import VirtualMachine
+    g = json.load(open(os.path.join(GOLDEN, "stark_%s.json" % name)))
+    program = VirtualMachine.compile(g["program"])
+    running_time, input_symbols, output_symbols = VirtualMachine.run(program, input_data=list(g["input"]))
+    matrices = VirtualMachine.simulate(program, input_data=list(input_symbols))
+    stark = BrainfuckStark(running_time, len(matrices[1]), program, input_symbols, output_symbols)
+    stark.native_stages = False
+    stream = Stream(name.encode())
+    for mod in (brainfuck_stark, salted_merkle, table):
+        monkeypatch.setattr(mod, "urandom", stream)
+    proof = stark.prove(program, *matrices)
+    assert stream.pos == g["urandom_bytes"], "the prover consumed a different amount of randomness"
+    assert len(proof) == g["proof_len"] and hashlib.sha256(proof).hexdigest() == g["proof_sha256"]
+    assert list(stark.timing) == PYTHON_STAGE_KEYS
+    assert "quotient_buffers" not in stark._last
+
+
 @pytest.mark.gpu
 def test_a_refused_commit_leaves_the_threads_session_usable(monkeypatch):
     """bfs_stark_commit refuses a call from its arguments alone (BFS_ERR_BAD_ARG = 6: a height that does not match the matrix, then no

@@ -76,6 +76,35 @@ def test_quotient_degree_bounds(name):
         assert got == q["degree_bounds"], ta.name
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_term_layout_shifts_are_max_degree_minus_the_golden_bounds(name):
+    """the degree shifts handed to both native calls and used by both Python routes (the prover's term layout): max_degree minus the
+    interpolant bound of every base column, then of every extension column, then the reference's own quotient degree bounds in the
+    order the golden file lists them (per table, then the permutation arguments) -- with the bounds the native prover remembers per
+    shape and with the verifier's exact terminal bounds; and one weight for the randomizer plus two per term"""
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    from stark_brainfuck_amd.vm import VirtualMachine
+    g = golden(name)
+    program = VirtualMachine.compile(g["program"])
+    running_time, inputs, outputs = VirtualMachine.run(program, input_data=list(g["input"]))
+    stark = BrainfuckStark(running_time, g["matrix_shapes"]["memory"][0], program, inputs, outputs)
+    assert [t.height for t in stark.tables] == g["table_heights"]
+    challenges = tuple(tuple(c) for c in g["quotients"][0]["challenges"])
+    terminals = [tuple(t) for t in g["terminals"]]
+    interpolant = [height + randomizers - 1 for height, randomizers in zip(g["table_heights"], [1, 1, 1, 0, 0])]
+    base_widths = [g["matrix_shapes"][key][1] for key in ("processor", "instruction", "memory", "input", "output")]
+    ext_widths = [t.full_width - t.base_width for t in stark.tables]
+    assert 1 + sum(base_widths) == g["base_tree"]["width"] and sum(ext_widths) == g["extension_tree"]["width"]
+    bounds = [b for widths in (base_widths, ext_widths) for b, width in zip(interpolant, widths) for _ in range(width)]
+    bounds += [b for q in g["quotients"] for b in q["degree_bounds"]] + [q["degree_bound"] for q in g["perm_quotients"]]
+    want = [g["max_degree"] - b for b in bounds]
+    layout = stark._layout
+    for quotient_bounds in (stark._quotient_degree_bounds(challenges, terminals, cached=True),
+                            stark._quotient_degree_bounds(challenges, terminals, exact_terminals=True)):
+        assert layout.shifts(quotient_bounds) == want
+    assert layout.weight_count == 1 + 2 * len(want)
+
+
 def test_generated_constraint_code_matches_the_expression_graphs(tmp_path):
     """csrc/air_generated.hpp (what the quotient kernels run), compiled for the host, against air.evaluate at random
     points; also checks that the committed header is what tools/gen_air.py produces from air.py today."""

@@ -173,7 +173,7 @@ def write_params(name, path):
     stark = stark_of(name)
     proof = open(os.path.join(GOLDEN, "stark_%s_proof.bin" % name), "rb").read()
     n = stark.fri.domain.length
-    distances = list(set(t.unit_distance(n) for t in stark.tables))
+    distances = stark._layout.unit_distances(n)
     words = [n.bit_length() - 1, stark.expansion_factor, stark.num_colinearity_checks, stark.security_level, stark.fri.domain.offset.value, stark.fri.domain.omega.value]
     words += [t.height for t in stark.tables] + [t.length for t in stark.tables] + [t.omicron.value for t in stark.tables]
     words += [len(distances)] + distances + [0] * (8 - len(distances))
@@ -183,10 +183,7 @@ def write_params(name, path):
     g = json.load(open(os.path.join(GOLDEN, "stark_%s.json" % name)))
     challenges = tuple(tuple(c) for c in g["quotients"][0]["challenges"])
     terminals = [tuple(t) for t in g["terminals"]]
-    bounds = [t.interpolant_degree() for t in stark.tables for _ in range(t.base_width)]
-    bounds += [t.interpolant_degree() for t in stark.tables for _ in range(t.full_width - t.base_width)]
-    bounds += stark._quotient_degree_bounds_cached(challenges, terminals)
-    shifts = [stark.max_degree - b for b in bounds]
+    shifts = stark._layout.shifts(stark._quotient_degree_bounds(challenges, terminals, cached=True))
     for seq in (program, [ord(c) for c in stark.input_symbols], [ord(c) for c in stark.output_symbols], shifts):
         words += [len(seq)] + list(seq)
     with open(path, "wb") as f:

@@ -489,6 +489,12 @@ int bfs_fri_session_round(void* session, uint32_t round, const uint64_t** d_code
  * first): *mismatches must come back 0; the first mismatch is described by bfs_last_error().  A test hook -- it exists
  * because a compiler fold once broke a composition of two individually correct primitives (csrc/gl.hpp, gl_sub). */
 int bfs_selftest_field(uint32_t log_count, uint64_t* mismatches);
+/* The same kernel on the caller's operands, without the comparison: h_pairs holds n pairs of canonical residues (a_i, b_i) =
+ * (h_pairs[2 i], h_pairs[2 i + 1]) in host memory, h_out receives the raw device results, 50 words per pair: h_out[50 i + j] =
+ * operation j of csrc/selftest.hip (selftest_ops) on pair i.  Operations 0..41 are canonical; 42..49 involve the unreduced sum
+ * gl_add_lazy and are "in [0, 2^64), not necessarily canonical".  n <= 2^24; an operand >= p is refused (BFS_ERR_BAD_ARG) and
+ * nothing runs.  Synchronous (default stream). */
+int bfs_selftest_field_pairs(const uint64_t* h_pairs, uint64_t n, uint64_t* h_out);
 
 /* ---- STARK prover kernels around the transforms ------------------------------------------ */
 /*

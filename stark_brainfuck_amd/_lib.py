@@ -130,6 +130,7 @@ _SIGNATURES = {
     "bfs_fri_session_rounds": (u32, [vp]),
     "bfs_fri_session_round": (ci, [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(vp), vp]),
     "bfs_selftest_field": (ci, [u32, ctypes.POINTER(u64)]),
+    "bfs_selftest_field_pairs": (ci, [vp, u64, vp]),
     "bfs_vm_trace_new": (ci, [ctypes.POINTER(u64), sz, ctypes.POINTER(u32), sz, u64, ctypes.POINTER(vp)]),
     "bfs_vm_trace_free": (None, [vp]),
     "bfs_vm_trace_size": (ci, [vp, ci, ctypes.POINTER(sz)]),

@@ -42,6 +42,30 @@ __global__ void selftest_kernel(const u64* in, u64* out, u64 n) {
 
 using namespace bfs;
 
+// selftest_ops on n pairs (a_i, b_i) = (in[2 i], in[2 i + 1]) on the device; got[ST_OPS * i + j] = operation j of pair i
+static int selftest_run(const u64* in, u64 n, u64* got) {
+    u64 *d_in = nullptr, *d_out = nullptr;
+    BFS_HIP(hipMalloc(&d_in, 2 * n * sizeof(u64)));
+    if (hipMalloc(&d_out, ST_OPS * n * sizeof(u64)) != hipSuccess) { (void)hipFree(d_in); set_error("field self-test: out of device memory"); return BFS_ERR_HIP; }
+    hipError_t e = hipMemcpy(d_in, in, 2 * n * sizeof(u64), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(selftest_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(got, d_out, ST_OPS * n * sizeof(u64), hipMemcpyDeviceToHost);
+    (void)hipFree(d_in); (void)hipFree(d_out);
+    BFS_HIP(e);
+    return BFS_OK;
+}
+
+extern "C" int bfs_selftest_field_pairs(const uint64_t* h_pairs, uint64_t n, uint64_t* h_out) {
+    if (n == 0) return BFS_OK;
+    if (n > (1ull << 24)) { set_error("bfs_selftest_field_pairs: at most 2^24 pairs"); return BFS_ERR_BAD_ARG; }
+    for (u64 i = 0; i < 2 * n; ++i)
+        if (h_pairs[i] >= GL_P) { set_error("bfs_selftest_field_pairs: operand %llu is not a canonical residue", (unsigned long long)i); return BFS_ERR_BAD_ARG; }
+    return selftest_run(h_pairs, n, h_out);
+}
+
 extern "C" int bfs_selftest_field(uint32_t log_count, uint64_t* mismatches) {
     const u64 n = 1ull << log_count;
     std::vector<u64> in(2 * n), got(ST_OPS * n);
@@ -59,14 +83,7 @@ extern "C" int bfs_selftest_field(uint32_t log_count, uint64_t* mismatches) {
         if (i < ne * ne) { in[2 * i] = edges[i / ne]; in[2 * i + 1] = edges[i % ne]; }
         else { in[2 * i] = (i & 64) ? rnd() % 300 : ((i & 128) ? GL_P - 1 - rnd() % 300 : rnd()); in[2 * i + 1] = (i & 32) ? rnd() % 300 : rnd(); }
     }
-    u64 *d_in = nullptr, *d_out = nullptr;
-    BFS_HIP(hipMalloc(&d_in, in.size() * sizeof(u64)));
-    BFS_HIP(hipMalloc(&d_out, got.size() * sizeof(u64)));
-    BFS_HIP(hipMemcpy(d_in, in.data(), in.size() * sizeof(u64), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(selftest_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, n);
-    BFS_HIP(hipGetLastError());
-    BFS_HIP(hipMemcpy(got.data(), d_out, got.size() * sizeof(u64), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_out);
+    BFS_TRY(selftest_run(in.data(), n, got.data()));
     u64 bad = 0;
     for (u64 i = 0; i < n; ++i) {
         u64 want[ST_OPS];

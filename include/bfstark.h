@@ -284,6 +284,22 @@ int bfs_stark_push_openings(void* ps, const bfs_gather_request* base_row, uint32
                             const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
                             const uint64_t* indices, uint32_t n_indices, const uint64_t* distances, uint32_t n_distances,
                             uint64_t* out_leaf_handles, void* stream);
+/*
+ * bfs_stark_push_openings_cosets   the same for a combination tree with ONE LEAF PER FOLDING COSET (bfs_merkle_build_xfe_cosets over the
+ *     combination codeword, cosets of a = 2^log2_coset, log2_coset in 1..3, q = n / a leaves): rows, salts and row paths as above; then per
+ *     index i the coset tuple of leaf c = i mod q -- the a elements C[c + j q], j < a -- and ONE path of log2 q digests.  The a limb triples
+ *     of every opened coset travel in the same single gather as the rows.  Identity: one tuple object per coset, pushed again as the same
+ *     object when two indices share a coset (the same index twice, or two indices equal mod q); a tuple's elements are its own; every path
+ *     list is new, a tree node is one bytes object however often it appears.  No handles come back: a FRI session that commits to cosets
+ *     opens whole cosets itself and takes no aliases.  BFS_ERR_BAD_ARG for log2_coset outside 1..3, n < 2 a or an index >= n.
+ */
+int bfs_stark_push_openings_cosets(void* ps, const bfs_gather_request* base_row, uint32_t n_base_req, int32_t base_field_id,
+                                   const bfs_gather_request* ext_row, uint32_t n_ext_req, const uint64_t* ext_moduli, uint32_t n_ext_cols,
+                                   uint64_t n, const uint8_t* d_base_nodes, const uint8_t* base_salts, int base_salts_on_device,
+                                   const uint8_t* d_ext_nodes, const uint8_t* ext_salts, int ext_salts_on_device,
+                                   const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
+                                   uint32_t log2_coset, const uint64_t* indices, uint32_t n_indices, const uint64_t* distances,
+                                   uint32_t n_distances, void* stream);
 
 /* ---- Merkle trees ------------------------------------------------------------------------------------------- */
 /*
@@ -726,6 +742,13 @@ typedef struct bfs_stark_randomness {  /* every random draw of prove(), in the o
 } bfs_stark_randomness;
 void* bfs_stark_session_new(void);
 void bfs_stark_session_free(void* session);
+/* How FRI treats the combination codeword in the NEXT proof of the session: rounds fold by 2^log2_folding (1..3), coset_leaves != 0 commits
+ * to the combination codeword -- and FRI to its codewords -- with one Merkle leaf per folding coset (bfs_stark_finish then builds the tree
+ * with bfs_merkle_build_xfe_cosets, opens cosets with bfs_stark_push_openings_cosets and registers round 0 with
+ * bfs_fri_session_round0_coset_tree), grinding_bits (0..40) puts a proof of work in front of FRI's index sampling.  Call before
+ * bfs_stark_commit, which takes the setting for the proof it starts and puts the default (1, 0, 0: the reference's protocol) back.
+ * params->num_colinearity_checks is the caller's: (security_level - grinding_bits) / log2(expansion_factor) in BrainfuckStark. */
+int bfs_stark_session_set_fri(void* session, uint32_t log2_folding, int coset_leaves, uint32_t grinding_bits);
 int bfs_stark_commit(void* session, void* ps, const bfs_stark_params* params, const bfs_stark_table_in* tables, const bfs_stark_randomness* randomness,
                      uint64_t* out_challenges, uint64_t* out_scan_terminals, uint64_t* out_io_terminals, double* out_ms, void* stream);
 int bfs_stark_finish(void* session, void* ps, const uint64_t* terminal_handles, const uint64_t* terminals, const uint64_t* shifts,
@@ -758,6 +781,12 @@ typedef struct bfs_stark_verify_params {
 } bfs_stark_verify_params;
 int bfs_stark_verify_begin(void* ps, const bfs_stark_verify_params* params, uint64_t* out_challenges, uint64_t* out_terminals, int* verdict);
 int bfs_stark_verify_finish(void* ps, const bfs_stark_verify_params* params, const uint64_t* shifts, uint32_t num_terms, int* verdict);
+/* bfs_stark_verify_finish for a proof made with bfs_stark_session_set_fri(log2_folding, coset_leaves, grinding_bits): with coset leaves the
+ * combination value at index i is element i / q of the opened coset tuple, authenticated at leaf i mod q, q = n >> log2_folding; FRI's
+ * layers fold by 2^log2_folding, chain coset tuples from layer to layer and check the proof of work (bfs_pow_check's predicate on a nonce
+ * that is a plain int below 2^64) before the indices are drawn.  (1, 0, 0) is bfs_stark_verify_finish. */
+int bfs_stark_verify_finish_fri(void* ps, const bfs_stark_verify_params* params, const uint64_t* shifts, uint32_t num_terms, uint32_t log2_folding,
+                                int coset_leaves, uint32_t grinding_bits, int* verdict);
 
 #ifdef __cplusplus
 }

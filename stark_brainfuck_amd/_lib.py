@@ -101,6 +101,8 @@ _SIGNATURES = {
     "bfs_merkle_build_rows": (ci, [vp, u32, u64, vp, ci, vp, vp]),
     "bfs_stark_push_openings": (ci, [vp, vp, u32, ctypes.c_int32, vp, u32, ctypes.POINTER(u64), u32, u64, vp, vp, ci, vp, vp, ci, vp, u64, vp,
                                      ctypes.POINTER(u64), u32, ctypes.POINTER(u64), u32, ctypes.POINTER(u64), vp]),
+    "bfs_stark_push_openings_cosets": (ci, [vp, vp, u32, ctypes.c_int32, vp, u32, ctypes.POINTER(u64), u32, u64, vp, vp, ci, vp, vp, ci, vp, u64, vp,
+                                            u32, ctypes.POINTER(u64), u32, ctypes.POINTER(u64), u32, vp]),
     "bfs_merkle_build_rows_range": (ci, [vp, u32, u64, u64, vp, ci, vp, vp]),
     "bfs_merkle_build_rows_root": (ci, [vp, u32, u64, u64, vp, ci, vp, vp, vp]),
     "bfs_row_template_steps": (ci, [vp, u32, u32, ci, vp, vp, u32, vp, u32, vp]),
@@ -160,6 +162,8 @@ _SIGNATURES = {
     "bfs_air_check": (ci, [ci, ci, vp, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp]),
     "bfs_stark_verify_begin": (ci, [vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci)]),
     "bfs_stark_verify_finish": (ci, [vp, vp, ctypes.POINTER(u64), u32, ctypes.POINTER(ci)]),
+    "bfs_stark_verify_finish_fri": (ci, [vp, vp, ctypes.POINTER(u64), u32, u32, ci, u32, ctypes.POINTER(ci)]),
+    "bfs_stark_session_set_fri": (ci, [vp, u32, ci, u32]),
     "bfs_stark_session_new": (vp, []),
     "bfs_stark_session_free": (None, [vp]),
     "bfs_stark_commit": (ci, [vp, vp, vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), vp]),

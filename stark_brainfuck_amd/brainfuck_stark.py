@@ -31,12 +31,12 @@ from .arrays import XArray
 from .device import GatherBatch, current_stream, gather, synchronize
 from .evaluation_argument import EvaluationArgument, ProgramEvaluationArgument
 from .extension_field import ExtensionField, ExtensionFieldElement
-from .fri import Fri
+from .fri import MAX_GRINDING_BITS, Fri
 from .instruction_table import InstructionTable
 from .io_table import InputTable, OutputTable
 from .ip import ProofStream
 from .memory_table import MemoryTable
-from .merkle import Merkle, leaf_pickle_source
+from .merkle import CosetMerkle, Merkle, leaf_pickle_source
 from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
@@ -190,9 +190,19 @@ class BrainfuckStark:
     field = BaseField.main()
     xfield = ExtensionField.main()
 
-    def __init__(self, running_time, memory_length, program, input_symbols, output_symbols, log_expansion_factor=2, security_level=2):
+    def __init__(self, running_time, memory_length, program, input_symbols, output_symbols, log_expansion_factor=2, security_level=2,
+                 folding_factor=2, coset_leaves=False, grinding_bits=0):
         """the reference fixes log_expansion_factor = 2 and security_level = 2 "for speed" (brainfuck_stark.py:31-36, with 4 and 160
-        commented as the real values); they are parameters here, the defaults reproduce the reference"""
+        commented as the real values); they are parameters here, the defaults reproduce the reference.
+
+        folding_factor (2, 4 or 8), coset_leaves and grinding_bits (0..40) go to `Fri` unchanged (fri.py explains them; its assertions
+        fire here) and decide how the combination codeword is committed to and tested; the defaults are the reference's protocol,
+        byte for byte.  With coset_leaves the commitment to the combination codeword is CosetMerkle(combination, folding_factor) and
+        every opened index reveals the coset tuple it lies in with one path ("FRI modes at the STARK level").
+        grinding_bits = b buys b bits of FRI's conjectured security with a proof of work, so FRI runs
+        (security_level - b) // log_expansion_factor colinearity checks.  The number of row indices the STARK itself opens stays
+        security_level: grinding protects only FRI's query sampling, the only sampling that follows the nonce -- the row indices are
+        drawn before FRI begins, so a prover re-rolls them without paying for a nonce."""
         self.running_time = running_time
         self.memory_length = memory_length
         self.program = program
@@ -201,11 +211,17 @@ class BrainfuckStark:
 
         self.expansion_factor = 1 << log_expansion_factor
         self.security_level = security_level
-        self.num_colinearity_checks = self.security_level // log_expansion_factor
+        assert type(grinding_bits) is int and 0 <= grinding_bits <= MAX_GRINDING_BITS, "grinding_bits must be an int from 0 to 40"
+        self.num_colinearity_checks = (self.security_level - grinding_bits) // log_expansion_factor
         assert self.expansion_factor & (self.expansion_factor - 1) == 0, "expansion factor must be a power of 2"
         assert self.expansion_factor >= 4, "expansion factor must be 4 or greater"
-        assert self.num_colinearity_checks * log_expansion_factor >= self.security_level, \
-            "number of colinearity checks times log of expansion factor must be at least security level"
+        if grinding_bits == 0:
+            assert self.num_colinearity_checks * log_expansion_factor >= self.security_level, \
+                "number of colinearity checks times log of expansion factor must be at least security level"
+        else:
+            assert self.num_colinearity_checks * log_expansion_factor + grinding_bits >= self.security_level, \
+                "number of colinearity checks times log of expansion factor plus grinding bits must be at least security level"
+            assert self.num_colinearity_checks >= 1, "grinding bits must leave at least one colinearity check"
         self.num_randomizers = 1
 
         order = 1 << 32
@@ -235,7 +251,9 @@ class BrainfuckStark:
         fri_domain_length = (self.max_degree + 1) * self.expansion_factor
         generator = BrainfuckStark.field.generator()
         omega = BrainfuckStark.field.primitive_nth_root(fri_domain_length)
-        self.fri = Fri(generator, omega, fri_domain_length, self.expansion_factor, self.num_colinearity_checks, self.xfield)
+        self.fri = Fri(generator, omega, fri_domain_length, self.expansion_factor, self.num_colinearity_checks, self.xfield,
+                       folding_factor=folding_factor, coset_leaves=coset_leaves, grinding_bits=grinding_bits)
+        self._default_fri = folding_factor == 2 and not coset_leaves and grinding_bits == 0          # the reference's protocol
         self._layout = _TermLayout(self.tables, self.permutation_arguments, self.max_degree)
 
     def get_terminals(self):
@@ -294,6 +312,7 @@ class BrainfuckStark:
     def cooperate(self, world_size, rank, group=None, device=None):
         """this prover is one of `world_size` identical provers (one per GPU) working on the SAME proof: the zipped commitments are
         built cooperatively, every rank returns the same proof bytes.  Call prove() inside `with shard.shared_randomness(...)`."""
+        assert self._default_fri, "cooperate() proves with the default FRI mode only (folding_factor=2, coset_leaves=False, grinding_bits=0)"
         self._cooperation = (int(world_size), int(rank), group, device) if world_size > 1 else None
         return self
 
@@ -313,10 +332,14 @@ class BrainfuckStark:
         rows = list(dict.fromkeys((index + distance) % n for index in p.indices for distance in distances))
         batch = GatherBatch()
         row_tickets = {i: ([batch.add(*r) for r in p.rows.requests(0, i)], [batch.add(*r) for r in p.rows.requests(1, i)]) for i in rows}
-        leaf_tickets = {index: batch.add(p.combination.ptr + 8 * index, 3, p.combination.stride) for index in dict.fromkeys(p.indices)}
+        # (coset leaves: per opened coset c = index mod q its a elements c + j q, and the path of leaf c)
+        coset = self.fri.coset_leaves
+        a, q = (self.fri.folding_factor, n // self.fri.folding_factor) if coset else (1, n)
+        leaf_tickets = {c: [batch.add(p.combination.ptr + 8 * (c + j * q), 3, p.combination.stride) for j in range(a)]
+                        for c in dict.fromkeys(index % q for index in p.indices)}
         stores = [base_tree.prefetch_salts(rows, batch), extension_tree.prefetch_salts(rows, batch),
                   base_tree.prefetch_paths(rows, batch), extension_tree.prefetch_paths(rows, batch),
-                  combination_tree.prefetch_paths(p.indices, batch)]
+                  combination_tree.prefetch_paths([index % q for index in p.indices], batch)]
         batch.run()
         for store in stores:
             store()
@@ -332,19 +355,22 @@ class BrainfuckStark:
                 proof_stream.push(extension_tree.open(idx))
         known = {}
         for index in p.indices:
-            if index not in known:                   # the same index twice is the same leaf object twice
-                known[index] = self.xfield.from_limbs([int(v) for v in batch.words(leaf_tickets[index])])
-            proof_stream.push(known[index])
-            proof_stream.push(combination_tree.open(index))
-        return known
+            c = index % q
+            if c not in known:                       # the same index twice is the same leaf object twice -- and so is a coset two indices share
+                elements = [self.xfield.from_limbs([int(v) for v in batch.words(ticket)]) for ticket in leaf_tickets[c]]
+                known[c] = tuple(elements) if coset else elements[0]
+            proof_stream.push(known[c])
+            proof_stream.push(combination_tree.open(c))
+        return {} if coset else known                # (a Fri that commits to cosets opens whole cosets itself: nothing to alias)
 
     def _openings_native(self, p):
         """the same through bfs_stark_push_openings: rows, salts, paths and leaves go from HBM into the native transcript in one
         call, and become Python objects only if somebody looks at proof_stream.objects (ip.ProofStream._adopt_lazy).  Returns
         {index: handle of the combination leaf} for Fri.prove, or None when this route is not available."""
         base_tree, extension_tree, combination, combination_tree, xf = p.base_tree, p.extension_tree, p.combination, p.combination_tree, self.xfield
+        coset = self.fri.coset_leaves
         if (self._cooperation is not None or type(base_tree) is not ZippedSaltedMerkle or type(extension_tree) is not ZippedSaltedMerkle
-                or combination_tree._nodes_host is not None or combination_tree.num_leafs != p.n):
+                or combination_tree._nodes_host is not None or combination_tree.num_leafs != (p.n // self.fri.folding_factor if coset else p.n)):
             return None
         transcript = BrainfuckStark._native_transcript(p.proof_stream, xf)
         if transcript is None:
@@ -368,12 +394,15 @@ class BrainfuckStark:
         out = (_u64 * len(indices))()
         (bs, bs_dev), (es, es_dev) = salts(base_tree), salts(extension_tree)
         before = transcript.num_objects()
-        _lib.check(_lib.load().bfs_stark_push_openings(
-            transcript.handle, base_arr, len(base_arr), transcript._field_id(BrainfuckStark.field), ext_arr, len(ext_arr), mods, len(moduli), p.n,
-            base_tree._nodes.ptr, bs, bs_dev, extension_tree._nodes.ptr, es, es_dev, combination.ptr, combination.stride,
-            combination_tree._nodes.ptr, idx, len(indices), dist, len(dist), out, p.stream))
+        head = (transcript.handle, base_arr, len(base_arr), transcript._field_id(BrainfuckStark.field), ext_arr, len(ext_arr), mods, len(moduli), p.n,
+                base_tree._nodes.ptr, bs, bs_dev, extension_tree._nodes.ptr, es, es_dev, combination.ptr, combination.stride,
+                combination_tree._nodes.ptr)
+        if coset:          # the coset tuples and their paths (bfs_stark_push_openings_cosets); FRI takes no aliases in this form
+            _lib.check(_lib.load().bfs_stark_push_openings_cosets(*head, self.fri._log2_folding, idx, len(indices), dist, len(dist), p.stream))
+        else:
+            _lib.check(_lib.load().bfs_stark_push_openings(*head, idx, len(indices), dist, len(dist), out, p.stream))
         p.proof_stream._adopt_lazy(transcript, before, transcript.num_objects(), xf)
-        return {index: int(handle) for index, handle in zip(indices, out)}
+        return {} if coset else {index: int(handle) for index, handle in zip(indices, out)}
 
     @staticmethod
     def _native_transcript(proof_stream, xf, refuse_loaded=False):
@@ -561,6 +590,8 @@ class BrainfuckStark:
         for slot, v in zip(tabs, values):
             slot.values, slot.rows, slot.row_stride = (v.ctypes.data if v.shape[0] else None), v.shape[0], (v.shape[1] if v.shape[0] else 0)
         session = BrainfuckStark._native_session()
+        if not self._default_fri:          # (holds for the proof the next bfs_stark_commit starts)
+            _lib.check(lib.bfs_stark_session_set_fri(session, self.fri._log2_folding, int(self.fri.coset_leaves), self.fri.grinding_bits))
         before = transcript.num_objects()
         out_ch, out_scan, out_io = (_u64 * 33)(), (_u64 * 27)(), (_u64 * 6)()
         ms_a, ms_b = (ctypes.c_double * 5)(), (ctypes.c_double * 5)()
@@ -816,7 +847,10 @@ class BrainfuckStark:
 
     def _stage_combination_tree(self, p):
         """commitment to the combination codeword (:300-302).  (GPU work: 2^22 extension leaves are 1.1 ms)"""
-        p.combination_tree = Merkle(p.combination)
+        if self.fri.coset_leaves:          # one leaf per folding coset: the tree FRI's round 0 commits to in this form
+            p.combination_tree = CosetMerkle(p.combination, self.fri.folding_factor)
+        else:
+            p.combination_tree = Merkle(p.combination)
         p.proof_stream.push(p.combination_tree.root())
 
     def _stage_openings(self, p):          # the opened rows and combination leaves (:304-333)
@@ -831,7 +865,7 @@ class BrainfuckStark:
 
     def _stage_fri(self, p):
         """low-degree test of the combination codeword (:335-336); round 0 commits to the combination tree that was just built"""
-        self.fri.prove(p.combination, p.proof_stream, known_leafs=p.known, round0_tree=p.combination_tree)
+        self.fri.prove(p.combination, p.proof_stream, known_leafs=p.known or None, round0_tree=p.combination_tree)
         self._last = {"challenges": p.challenges, "terminals": p.terminals, "indices": p.indices, "weights_seed": p.weights_seed,
                       "quotient_degree_bounds": p.quotient_degree_bounds}
         if self.keep_intermediates:
@@ -965,7 +999,11 @@ class BrainfuckStark:
             return outcome()
         challenges, terminals = tuple(_triples(out_ch, 11)), _triples(out_tm, 5)
         shifts = self._layout.shifts(self._quotient_degree_bounds(challenges, terminals, exact_terminals=True))
-        _lib.check(lib.bfs_stark_verify_finish(t.handle, ctypes.byref(params), (_u64 * len(shifts))(*shifts), len(shifts), ctypes.byref(verdict)))
+        if self._default_fri:
+            _lib.check(lib.bfs_stark_verify_finish(t.handle, ctypes.byref(params), (_u64 * len(shifts))(*shifts), len(shifts), ctypes.byref(verdict)))
+        else:
+            _lib.check(lib.bfs_stark_verify_finish_fri(t.handle, ctypes.byref(params), (_u64 * len(shifts))(*shifts), len(shifts),
+                                                       self.fri._log2_folding, int(self.fri.coset_leaves), self.fri.grinding_bits, ctypes.byref(verdict)))
         return outcome()
 
     # ---- the Python verifier, in the order of the reference's verify(): head, opened rows, per index the combination, tail
@@ -983,7 +1021,19 @@ class BrainfuckStark:
             inner_product = (got[0], got[1], got[2])
             combination_leaf = proof_stream.pull()
             combination_path = proof_stream.pull()
-            if not Merkle.verify(head.combination_root, index, combination_path, combination_leaf):
+            if self.fri.coset_leaves:
+                # the opened leaf is the coset tuple of leaf c = index mod q: a extension elements, authenticated by log2 q digests;
+                # the combination value at `index` is its element number index // q
+                a, q = self.fri.folding_factor, self.fri.domain.length // self.fri.folding_factor
+                if not (isinstance(combination_leaf, tuple) and len(combination_leaf) == a and all(hasattr(e, "limbs") for e in combination_leaf)):
+                    return False
+                if not (isinstance(combination_path, list) and len(combination_path) == q.bit_length() - 1
+                        and all(isinstance(node, (bytes, bytearray)) for node in combination_path)):
+                    return False
+                if not Merkle.verify(head.combination_root, index % q, combination_path, combination_leaf):
+                    return False
+                combination_leaf = combination_leaf[index // q]
+            elif not Merkle.verify(head.combination_root, index, combination_path, combination_leaf):
                 return False
             # brainfuck_stark.py:567 compares the leaf OBJECT with the inner product (coefficient values as stored, algebra.py:36):
             # a leaf whose coefficients are not canonical residues is unequal there, and here

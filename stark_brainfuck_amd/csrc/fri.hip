@@ -610,16 +610,27 @@ int bfs_fri_prove_cosets(void* ps, const uint64_t* d_codeword, uint64_t limb_str
 // have (pickle memoises by identity): a row opened twice is one tuple object, a tree node or a salt one bytes object however often it
 // appears, every (salt, path) tuple and path list is new, extension elements of a column whose interpolant has all its non-zero
 // coefficients at multiples of 2^v share their coefficient objects with the rows i' = i mod modulus (table.ext_sharing_moduli).
-int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint32_t n_base_req, int32_t base_field_id,
-                            const bfs_gather_request* ext_row, uint32_t n_ext_req, const uint64_t* ext_moduli, uint32_t n_ext_cols,
-                            uint64_t n, const uint8_t* d_base_nodes, const uint8_t* base_salts, int base_salts_on_device,
-                            const uint8_t* d_ext_nodes, const uint8_t* ext_salts, int ext_salts_on_device,
-                            const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
-                            const uint64_t* indices, uint32_t n_indices, const uint64_t* distances, uint32_t n_distances,
-                            uint64_t* out_leaf_handles, void* stream_) {
+//
+// log2_coset = 0: the combination tree has one leaf per element, as above.  log2_coset = k in 1..3 (bfs_stark_push_openings_cosets): the
+// tree is bfs_merkle_build_xfe_cosets' over cosets of a = 2^k, q = n / a leaves; for index i the coset c = i mod q is opened -- the
+// tuple (C[c], C[c + q], .., C[c + (a - 1) q]), then one path of log2 q digests.  The a limb triples of every opened coset are a more
+// requests of the same single gather.  One tuple object per coset: a coset that two indices share (the same index twice, or two
+// indices that agree mod q) is pushed twice as the same object; the elements of a tuple are its own; a path list is new every time,
+// its digests one bytes object each per tree node, like the rows' paths.  No handles go out: FRI in this form opens whole cosets itself.
+static int stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint32_t n_base_req, int32_t base_field_id,
+                               const bfs_gather_request* ext_row, uint32_t n_ext_req, const uint64_t* ext_moduli, uint32_t n_ext_cols,
+                               uint64_t n, const uint8_t* d_base_nodes, const uint8_t* base_salts, int base_salts_on_device,
+                               const uint8_t* d_ext_nodes, const uint8_t* ext_salts, int ext_salts_on_device,
+                               const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
+                               uint32_t log2_coset, const uint64_t* indices, uint32_t n_indices, const uint64_t* distances,
+                               uint32_t n_distances, uint64_t* out_leaf_handles, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     rp::Transcript& ps = *(rp::Transcript*)ps_;
     if (n == 0 || (n & (n - 1))) { set_error("bfs_stark_push_openings: n must be a power of two"); return BFS_ERR_BAD_ARG; }
+    if (log2_coset > 3 || (log2_coset && (n >> log2_coset) < 2)) { set_error("bfs_stark_push_openings_cosets: cosets of 2^%u in a codeword of %llu", log2_coset, (unsigned long long)n); return BFS_ERR_BAD_ARG; }
+    if (combination_stride < n || combination_stride >> 32) { set_error("bfs_stark_push_openings: combination stride"); return BFS_ERR_BAD_ARG; }
+    const u32 fan = 1u << log2_coset;                   // elements per opened leaf of the combination tree
+    const u64 comb_leaves = n >> log2_coset;            // leaves of that tree
     u32 base_words = 0, ext_words = 0;
     for (u32 k = 0; k < n_base_req; ++k) base_words += base_row[k].nwords;
     for (u32 k = 0; k < n_ext_req; ++k) ext_words += ext_row[k].nwords;
@@ -631,7 +642,9 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
             const u64 r = (indices[a] + distances[b]) % n;
             if (std::find(rows.begin(), rows.end(), r) == rows.end()) rows.push_back(r);
         }
-        if (std::find(uniq_idx.begin(), uniq_idx.end(), indices[a]) == uniq_idx.end()) uniq_idx.push_back(indices[a]);
+        if (indices[a] >= n) { set_error("bfs_stark_push_openings: index %llu outside the domain", (unsigned long long)indices[a]); return BFS_ERR_BAD_ARG; }
+        const u64 leaf = indices[a] & (comb_leaves - 1);          // the opened leaf: the index itself, or its coset
+        if (std::find(uniq_idx.begin(), uniq_idx.end(), leaf) == uniq_idx.end()) uniq_idx.push_back(leaf);
     }
     // ---- one gather
     std::vector<GatherReq> reqs;
@@ -644,8 +657,9 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
     std::vector<std::pair<int, u64>> node_list;        // order of first use
     std::vector<u64> node_off;
     const uint8_t* tree_nodes[3] = {d_base_nodes, d_ext_nodes, d_combination_nodes};
+    const u64 tree_leaves[3] = {n, n, comb_leaves};
     auto want_path = [&](int tree, u64 leaf) {
-        for (u64 k = n | leaf; k > 1; k >>= 1) {
+        for (u64 k = tree_leaves[tree] | leaf; k > 1; k >>= 1) {
             const Key key(0, k ^ 1);
             if (node_at[tree].count(key)) continue;
             node_at[tree][key] = rp::mk_int(node_off.size());
@@ -666,7 +680,8 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
     }
     std::vector<u64> leaf_at(uniq_idx.size());
     for (size_t a = 0; a < uniq_idx.size(); ++a) {
-        leaf_at[a] = want(d_combination + uniq_idx[a], 3, (u32)combination_stride);
+        leaf_at[a] = nwords;                            // `fan` limb triples, one behind the other
+        for (u32 j = 0; j < fan; ++j) want(d_combination + uniq_idx[a] + j * comb_leaves, 3, (u32)combination_stride);
         want_path(2, uniq_idx[a]);
     }
     PinnedLease req_area, res_area;
@@ -677,7 +692,7 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
     for (size_t k = 0; k < node_list.size(); ++k) node_obj[k] = rp::mk_bytes(words + node_off[k], 64);
     auto path_obj = [&](int tree, u64 leaf) {
         std::vector<rp::Ref> items;
-        for (u64 k = n | leaf; k > 1; k >>= 1) items.push_back(node_obj[node_at[tree][Key(0, k ^ 1)]->ival]);
+        for (u64 k = tree_leaves[tree] | leaf; k > 1; k >>= 1) items.push_back(node_obj[node_at[tree][Key(0, k ^ 1)]->ival]);
         return rp::mk_list(items);
     };
     const rp::Ref base_field = ps.world.base_field(base_field_id);
@@ -721,16 +736,47 @@ int bfs_stark_push_openings(void* ps_, const bfs_gather_request* base_row, uint3
         }
     std::vector<rp::Ref> leaf_obj(uniq_idx.size());
     for (size_t a = 0; a < uniq_idx.size(); ++a) {
-        u64 l[3] = {words[leaf_at[a]], words[leaf_at[a] + 1], words[leaf_at[a] + 2]};
-        leaf_obj[a] = ps.world.xfe_compact(l);
+        std::vector<rp::Ref> items;
+        for (u32 j = 0; j < fan; ++j) {
+            const u64* w = words + leaf_at[a] + 3 * j;
+            u64 l[3] = {w[0], w[1], w[2]};
+            items.push_back(ps.world.xfe_compact(l));
+        }
+        leaf_obj[a] = log2_coset ? rp::mk_tuple(items) : items[0];
     }
     for (u32 a = 0; a < n_indices; ++a) {
-        const size_t u = (size_t)(std::find(uniq_idx.begin(), uniq_idx.end(), indices[a]) - uniq_idx.begin());
+        const u64 leaf = indices[a] & (comb_leaves - 1);
+        const size_t u = (size_t)(std::find(uniq_idx.begin(), uniq_idx.end(), leaf) - uniq_idx.begin());
         ps.objects.push_back(leaf_obj[u]);
-        ps.objects.push_back(path_obj(2, indices[a]));
-        out_leaf_handles[a] = ps.add(leaf_obj[u]);
+        ps.objects.push_back(path_obj(2, leaf));
+        if (out_leaf_handles) out_leaf_handles[a] = ps.add(leaf_obj[u]);
     }
     return BFS_OK;
+}
+
+int bfs_stark_push_openings(void* ps, const bfs_gather_request* base_row, uint32_t n_base_req, int32_t base_field_id,
+                            const bfs_gather_request* ext_row, uint32_t n_ext_req, const uint64_t* ext_moduli, uint32_t n_ext_cols,
+                            uint64_t n, const uint8_t* d_base_nodes, const uint8_t* base_salts, int base_salts_on_device,
+                            const uint8_t* d_ext_nodes, const uint8_t* ext_salts, int ext_salts_on_device,
+                            const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
+                            const uint64_t* indices, uint32_t n_indices, const uint64_t* distances, uint32_t n_distances,
+                            uint64_t* out_leaf_handles, void* stream) {
+    return stark_push_openings(ps, base_row, n_base_req, base_field_id, ext_row, n_ext_req, ext_moduli, n_ext_cols, n, d_base_nodes, base_salts,
+                               base_salts_on_device, d_ext_nodes, ext_salts, ext_salts_on_device, d_combination, combination_stride,
+                               d_combination_nodes, 0, indices, n_indices, distances, n_distances, out_leaf_handles, stream);
+}
+
+int bfs_stark_push_openings_cosets(void* ps, const bfs_gather_request* base_row, uint32_t n_base_req, int32_t base_field_id,
+                                   const bfs_gather_request* ext_row, uint32_t n_ext_req, const uint64_t* ext_moduli, uint32_t n_ext_cols,
+                                   uint64_t n, const uint8_t* d_base_nodes, const uint8_t* base_salts, int base_salts_on_device,
+                                   const uint8_t* d_ext_nodes, const uint8_t* ext_salts, int ext_salts_on_device,
+                                   const uint64_t* d_combination, uint64_t combination_stride, const uint8_t* d_combination_nodes,
+                                   uint32_t log2_coset, const uint64_t* indices, uint32_t n_indices, const uint64_t* distances,
+                                   uint32_t n_distances, void* stream) {
+    if (log2_coset < 1) { set_error("bfs_stark_push_openings_cosets: log2_coset must be 1, 2 or 3 (got %u)", log2_coset); return BFS_ERR_BAD_ARG; }
+    return stark_push_openings(ps, base_row, n_base_req, base_field_id, ext_row, n_ext_req, ext_moduli, n_ext_cols, n, d_base_nodes, base_salts,
+                               base_salts_on_device, d_ext_nodes, ext_salts, ext_salts_on_device, d_combination, combination_stride,
+                               d_combination_nodes, log2_coset, indices, n_indices, distances, n_distances, nullptr, stream);
 }
 
 int bfs_gather(const bfs_gather_request* requests, uint32_t count, uint64_t* h_out, void* stream_) {

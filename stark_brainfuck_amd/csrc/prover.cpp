@@ -164,6 +164,13 @@ struct StarkSession {
     u64 ext_moduli[16] = {0};
     bool committed = false;
     hipStream_t stream = nullptr;
+    // How FRI treats the combination codeword (bfs_stark_session_set_fri): `fri_next` is what the caller asked for, bfs_stark_commit moves
+    // it into `fri` for the proof it starts and puts the default back, so a session that is kept between proofs never inherits a mode.
+    struct FriMode {
+        u32 log2_folding = 1;                               // every FRI round folds by 2^log2_folding
+        bool coset_leaves = false;                          // the combination tree and FRI's trees have one leaf per folding coset
+        u32 grinding_bits = 0;                              // proof of work in front of FRI's index sampling
+    } fri, fri_next;
     // The commitment to the zipped extension rows is the first thing bfs_stark_finish needs and depends on nothing the caller does
     // between the two calls, so bfs_stark_commit hands it to a thread of its own: the GPU hashes rows while the caller's interpreter
     // makes terminal objects and degree bounds.  Joined by bfs_stark_finish (or by whatever ends the session first).
@@ -376,6 +383,17 @@ extern "C" {
 void* bfs_stark_session_new(void) { return new StarkSession(); }
 void bfs_stark_session_free(void* s) { delete (StarkSession*)s; }
 
+int bfs_stark_session_set_fri(void* session, uint32_t log2_folding, int coset_leaves, uint32_t grinding_bits) {
+    BFS_TRY(check_session(session, "bfs_stark_session_set_fri"));
+    if (log2_folding < 1 || log2_folding > 3) { set_error("bfs_stark_session_set_fri: log2_folding must be 1, 2 or 3 (got %u)", log2_folding); return BFS_ERR_BAD_ARG; }
+    if (grinding_bits > 40) { set_error("bfs_stark_session_set_fri: grinding_bits must be in 0..40 (got %u)", grinding_bits); return BFS_ERR_BAD_ARG; }
+    StarkSession& S = *(StarkSession*)session;
+    S.fri_next.log2_folding = log2_folding;
+    S.fri_next.coset_leaves = coset_leaves != 0;
+    S.fri_next.grinding_bits = grinding_bits;
+    return BFS_OK;
+}
+
 int bfs_stark_commit(void* session, void* ps, const bfs_stark_params* params, const bfs_stark_table_in* tables, const bfs_stark_randomness* rnd,
                      uint64_t* out_challenges, uint64_t* out_scan_terminals, uint64_t* out_io_terminals, double* out_ms, void* stream_) {
     BFS_TRY(check_session(session, "bfs_stark_commit"));
@@ -386,6 +404,8 @@ int bfs_stark_commit(void* session, void* ps, const bfs_stark_params* params, co
     S.P = *params;
     S.stream = stream;
     S.committed = false;
+    S.fri = S.fri_next;
+    S.fri_next = StarkSession::FriMode{};
     BFS_TRY(validate_commit(S, tables, *rnd));
     const bfs_stark_params& P = S.P;
     const u64 n = S.n, stride = S.stride;
@@ -673,8 +693,11 @@ int bfs_stark_finish(void* session, void* ps, const uint64_t* terminal_handles, 
     clock.end(1);
 
     // ---- commitment to the combination codeword (:300-301), indices (:303-304)
+    const StarkSession::FriMode mode = S.fri;
+    if (mode.coset_leaves && (n >> mode.log2_folding) < 2) { set_error("bfs_stark_finish: a domain of %llu points has no coset tree of cosets of %u", (unsigned long long)n, 1u << mode.log2_folding); return BFS_ERR_BAD_ARG; }
     BFS_TRY(M.comb_nodes.get(2 * n * 64, stream));
-    BFS_TRY(bfs_merkle_build_xfe(M.combination.words(), n, n, (uint8_t*)M.comb_nodes.ptr, stream));
+    if (mode.coset_leaves) BFS_TRY(bfs_merkle_build_xfe_cosets(M.combination.words(), n, n, mode.log2_folding, (uint8_t*)M.comb_nodes.ptr, stream));
+    else BFS_TRY(bfs_merkle_build_xfe(M.combination.words(), n, n, (uint8_t*)M.comb_nodes.ptr, stream));
     uint8_t comb_root[64];
     BFS_HIP(hipMemcpyAsync(comb_root, M.comb_nodes.bytes() + 64, 64, hipMemcpyDeviceToHost, stream));
     BFS_HIP(hipStreamSynchronize(stream));
@@ -705,16 +728,28 @@ int bfs_stark_finish(void* session, void* ps, const uint64_t* terminal_handles, 
     std::vector<u64> leaf_handles(num_indices);
     const auto [base_salts, base_salts_on_device] = M.base_salts.where();
     const auto [ext_salts, ext_salts_on_device] = M.ext_salts.where();
-    BFS_TRY(bfs_stark_push_openings(ps, base_req, 1 + NT, base_field_id, ext_req, NT, S.ext_moduli, S.total_ext, n, M.base_nodes.bytes(), base_salts,
-                                    base_salts_on_device, M.ext_nodes.bytes(), ext_salts, ext_salts_on_device, M.combination.words(), n,
-                                    M.comb_nodes.bytes(), indices.data(), num_indices, distances, n_distances, leaf_handles.data(), stream));
+    if (mode.coset_leaves)
+        BFS_TRY(bfs_stark_push_openings_cosets(ps, base_req, 1 + NT, base_field_id, ext_req, NT, S.ext_moduli, S.total_ext, n, M.base_nodes.bytes(),
+                                               base_salts, base_salts_on_device, M.ext_nodes.bytes(), ext_salts, ext_salts_on_device,
+                                               M.combination.words(), n, M.comb_nodes.bytes(), mode.log2_folding, indices.data(), num_indices,
+                                               distances, n_distances, stream));
+    else
+        BFS_TRY(bfs_stark_push_openings(ps, base_req, 1 + NT, base_field_id, ext_req, NT, S.ext_moduli, S.total_ext, n, M.base_nodes.bytes(), base_salts,
+                                        base_salts_on_device, M.ext_nodes.bytes(), ext_salts, ext_salts_on_device, M.combination.words(), n,
+                                        M.comb_nodes.bytes(), indices.data(), num_indices, distances, n_distances, leaf_handles.data(), stream));
     clock.end(3);
 
     // ---- FRI on the combination codeword (:335-336): round 0 is the tree that was just built
+    // (in the coset form the openings above and FRI's are distinct objects: a session that commits to cosets takes no aliases)
     void* fri = bfs_fri_session_new();
-    int rc = bfs_fri_session_round0_tree(fri, M.comb_nodes.bytes(), comb_root);
+    int rc = BFS_OK;
+    if (mode.log2_folding != 1) rc = bfs_fri_session_set_folding(fri, mode.log2_folding);
+    if (rc == BFS_OK && mode.grinding_bits) rc = bfs_fri_session_set_grinding(fri, mode.grinding_bits, 0);
+    if (rc == BFS_OK && mode.coset_leaves) rc = bfs_fri_session_set_coset_leaves(fri, 1);
+    if (rc == BFS_OK) rc = mode.coset_leaves ? bfs_fri_session_round0_coset_tree(fri, M.comb_nodes.bytes(), n >> mode.log2_folding, comb_root)
+                                             : bfs_fri_session_round0_tree(fri, M.comb_nodes.bytes(), comb_root);
     if (rc == BFS_OK) rc = bfs_fri_commit(fri, ps, M.combination.words(), n, P.log_n, offset, omega, P.expansion_factor, stream);
-    for (u32 a = 0; rc == BFS_OK && a < num_indices; ++a) rc = bfs_fri_session_alias(fri, ps, 0, indices[a], leaf_handles[a]);
+    for (u32 a = 0; rc == BFS_OK && !mode.coset_leaves && a < num_indices; ++a) rc = bfs_fri_session_alias(fri, ps, 0, indices[a], leaf_handles[a]);
     std::vector<u64> top(P.num_colinearity_checks ? P.num_colinearity_checks : 1);
     if (rc == BFS_OK) rc = bfs_fri_query(fri, ps, P.num_colinearity_checks, top.data(), stream);
     bfs_fri_session_free(fri);

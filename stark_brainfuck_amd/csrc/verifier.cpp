@@ -125,11 +125,57 @@ void read_begin(Reader& rd, Begin& b) {
     }
 }
 
-// fri.py:201-319 (stark_brainfuck_amd/fri.py: Fri.verify), on the reader's stream
-bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0) {
+// How FRI treats the combination codeword: BrainfuckStark(..., folding_factor, coset_leaves, grinding_bits) (stark_brainfuck_amd/fri.py)
+struct FriMode {
+    u32 k = 1;                 // every round folds by a = 2^k
+    bool coset = false;        // one Merkle leaf per folding coset, in the combination tree and in every FRI tree but the last
+    u32 grinding = 0;          // proof-of-work bits in front of FRI's index sampling
+};
+
+// stark_brainfuck_amd/fri.py: _fold_coset -- the a = 2^k values C[c + j q] folded k times (fri.py:127-128 per step), alpha, offset g and
+// generator w squared between the steps
+Xfe fold_coset(std::vector<Xfe> v, Xfe alpha, u64 g, u64 w, u64 c, u64 q, u32 k) {
+    const u64 half_inv = gl_inv(2);
+    for (u32 step = 0; step < k; ++step) {
+        const size_t h = v.size() / 2;
+        std::vector<Xfe> folded(h);
+        for (size_t m = 0; m < h; ++m) {
+            const u64 x_inv = gl_inv(gl_mul(g, gl_pow(w, c + m * q)));
+            const Xfe beta = xfe_scale(alpha, gl_mul(half_inv, x_inv));
+            folded[m] = xfe_add(xfe_scale(xfe_add(v[m], v[m + h]), half_inv), xfe_mul(beta, xfe_sub(v[m], v[m + h])));
+        }
+        v.swap(folded);
+        alpha = xfe_mul(alpha, alpha);
+        g = gl_mul(g, g);
+        w = gl_mul(w, w);
+    }
+    return v[0];
+}
+
+bool is_xfe(const Ref& r) { return r && r->kind == rp::K_INSTANCE && r->role == rp::R_XFE; }
+bool stored_eq(const Ref& r, const Xfe& v) { return r->limbs[0] == v.c[0] && r->limbs[1] == v.c[1] && r->limbs[2] == v.c[2]; }
+// a tuple of `count` extension elements / an authentication path of `depth` digests (what the coset form requires of an opened leaf)
+bool is_xfe_tuple(const Ref& r, size_t count) {
+    if (!r || r->kind != rp::K_TUPLE || r->items.size() != count) return false;
+    for (const Ref& e : r->items) if (!is_xfe(e)) return false;
+    return true;
+}
+bool is_digest_path(const Ref& r, size_t depth) {
+    if (!r || r->kind != rp::K_LIST || r->items.size() != depth) return false;
+    for (const Ref& node : r->items) if (!node || node->kind != rp::K_BYTES) return false;
+    return true;
+}
+u32 log2_of(u64 v) { u32 l = 0; while ((1ull << l) < v) ++l; return l; }
+
+// fri.py:201-319 (stark_brainfuck_amd/fri.py: Fri.verify and its one layer loop, _verify_layers / _judge), on the reader's stream: every
+// mode, the checks in the order of the Python verifier
+bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0, const FriMode& M) {
     const u64 N = 1ull << P.log_n;
-    u32 rounds = 0;
-    for (u64 len = N; len > P.expansion_factor; len /= 2) ++rounds;
+    const u32 k = M.k, a = 1u << k;
+    const bool coset = M.coset;
+    u32 halvings = 0;
+    for (u64 len = N; len > P.expansion_factor; len /= 2) ++halvings;
+    const u32 rounds = (k == 1 || halvings == 0) ? halvings : (halvings - 1) / k + 1;          // Fri.num_rounds
     const u32 t = P.num_colinearity_checks;
     std::vector<Ref> roots{root0};
     std::vector<Xfe> alphas;
@@ -172,7 +218,8 @@ bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0) 
     // sum_i y_i omega^(-i j)
     u64 omega = P.omega % GL_P, offset = P.offset % GL_P;
     u64 last_omega = omega;
-    for (u32 r = 0; r + 1 < rounds; ++r) last_omega = gl_mul(last_omega, last_omega);
+    for (u32 r = 0; r + 1 < rounds; ++r)
+        for (u32 j = 0; j < k; ++j) last_omega = gl_mul(last_omega, last_omega);
     if (gl_pow(last_omega, n_last) != 1) throw Assertion{"omega does not have right order"};
     {
         const long degree = (long)(n_last / P.expansion_factor) - 1;
@@ -190,10 +237,21 @@ bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0) 
         }
         if (top > degree) return false;
     }
+    if (M.grinding) {
+        // the proof of work: over the stream up to the last codeword, the nonce a plain int in [0, 2^64) (the reader takes no other
+        // integers: a stream with one never gets here) that satisfies bfs_pow_check
+        unsigned char seed[32];
+        rd.fiat_shamir(seed);
+        const Ref nonce = rd.pull();
+        int ok = 0;
+        if (!nonce || nonce->kind != rp::K_INT) return false;
+        if (bfs_pow_check(seed, M.grinding, nonce->ival, &ok) != BFS_OK) throw Fallback{};
+        if (!ok) return false;
+    }
     // indices (fri.py:62-86)
     std::vector<u64> top_level;
     {
-        const u64 size = N >> 1, reduced_size = N >> (rounds - 1);
+        const u64 size = N >> k, reduced_size = N >> (k * (rounds - 1));
         if (t > reduced_size) {
             char msg[160];
             snprintf(msg, sizeof msg, "cannot sample more indices than available in last codeword; requested: %u, available: %llu", t, (unsigned long long)reduced_size);
@@ -210,46 +268,86 @@ bool fri_verify(Reader& rd, const bfs_stark_verify_params& P, const Ref& root0) 
             if (!seen) { top_level.push_back(index); reduced.push_back(red); }
         }
     }
+    // the layers (Fri._verify_layers).  Per test and layer: the opened leaf -- (C_r[c + j q], j < a, C_{r+1}[c]) per element, the a values
+    // alone in the coset form -- then the paths.  expected: in the coset form, where in this layer's tuple the value sits that the same
+    // test's tuple of the layer before folded to
+    std::vector<u32> expected_at(t);
+    std::vector<Xfe> expected(t);
+    bool have_expected = false;
     for (u32 r = 0; r + 1 < rounds; ++r) {
-        const u64 half = N >> (r + 1);
-        std::vector<u64> c_idx(t), a_idx(t), b_idx(t);
-        for (u32 s = 0; s < t; ++s) { c_idx[s] = top_level[s] % half; a_idx[s] = c_idx[s]; b_idx[s] = c_idx[s] + half; }
+        const u64 q = N >> (k * (r + 1));
+        const bool last_layer = r + 1 == rounds - 1;
+        std::vector<u64> c_idx(t);
+        for (u32 s = 0; s < t; ++s) c_idx[s] = top_level[s] % q;
         const Xfe alpha = alphas[r];
-        std::vector<Ref> aa(t), bb(t), cc(t);
+        std::vector<Ref> opened(t), next_ref(t);          // the pulled tuple; per element: its last item
+        std::vector<Xfe> folded(t);                       // coset form: what the tuple folds to
         for (u32 s = 0; s < t; ++s) {
-            Ref triple = rd.pull();
-            if (!triple || triple->kind != rp::K_TUPLE || triple->items.size() != 3) throw Fallback{};
-            aa[s] = triple->items[0]; bb[s] = triple->items[1]; cc[s] = triple->items[2];
-            const u64 ax = gl_mul(offset, gl_pow(omega, a_idx[s])), bx = gl_mul(offset, gl_pow(omega, b_idx[s]));
-            const Xfe ya = xfe_value_of(aa[s]), yb = xfe_value_of(bb[s]), yc = xfe_value_of(cc[s]);
-            // three points on a line: (ax, ya), (bx, yb), (alpha, yc)  (univariate.py: test_colinearity; stark_brainfuck_amd/fri.py: _on_a_line)
-            const u64 d1 = gl_sub(bx, ax);
-            const Xfe d2 = xfe_sub_base(alpha, ax), dx = xfe_sub_base(alpha, bx);
-            if (!d1 || xfe_is_zero(d2) || xfe_is_zero(dx)) throw Fallback{};       // coinciding abscissae: the general routine decides
-            const Xfe e1 = xfe_sub(yb, ya);
-            const bool on_a_line = !xfe_is_zero(e1) && xfe_eq(xfe_scale(xfe_sub(yc, ya), d1), xfe_mul(e1, d2));
-            if (!on_a_line) return false;
-        }
-        for (u32 i = 0; i < t; ++i) {
-            if (!path_ok(rd.t, aa[i], nullptr, rd.pull(), a_idx[i], roots[r])) return false;
-            if (!path_ok(rd.t, bb[i], nullptr, rd.pull(), b_idx[i], roots[r])) return false;
-            if (r + 1 != rounds - 1 && !path_ok(rd.t, cc[i], nullptr, rd.pull(), c_idx[i], roots[r + 1])) return false;
-        }
-        if (r + 1 == rounds - 1) {
-            // fri.py:311-315: the folded values are elements of the last codeword (object comparison: coefficient values as stored)
-            for (u32 i = 0; i < t; ++i) {
-                const Ref& e = last->items[c_idx[i]];
-                if (cc[i]->role != rp::R_XFE || e->role != rp::R_XFE) throw Fallback{};
-                if (cc[i]->limbs[0] != e->limbs[0] || cc[i]->limbs[1] != e->limbs[1] || cc[i]->limbs[2] != e->limbs[2]) return false;
+            const Ref tuple = rd.pull();
+            opened[s] = tuple;
+            if (!coset && a == 2) {
+                if (!tuple || tuple->kind != rp::K_TUPLE || tuple->items.size() != 3) throw Fallback{};
+                const u64 ax = gl_mul(offset, gl_pow(omega, c_idx[s])), bx = gl_mul(offset, gl_pow(omega, c_idx[s] + q));
+                const Xfe ya = xfe_value_of(tuple->items[0]), yb = xfe_value_of(tuple->items[1]), yc = xfe_value_of(tuple->items[2]);
+                // three points on a line: (ax, ya), (bx, yb), (alpha, yc)  (univariate.py: test_colinearity; stark_brainfuck_amd/fri.py: _on_a_line)
+                const u64 d1 = gl_sub(bx, ax);
+                const Xfe d2 = xfe_sub_base(alpha, ax), dx = xfe_sub_base(alpha, bx);
+                if (!d1 || xfe_is_zero(d2) || xfe_is_zero(dx)) throw Fallback{};       // coinciding abscissae: the general routine decides
+                const Xfe e1 = xfe_sub(yb, ya);
+                const bool on_a_line = !xfe_is_zero(e1) && xfe_eq(xfe_scale(xfe_sub(yc, ya), d1), xfe_mul(e1, d2));
+                if (!on_a_line) return false;
+                next_ref[s] = tuple->items[2];
+                continue;
             }
+            if (!tuple || tuple->kind != rp::K_TUPLE || tuple->items.size() != (coset ? a : a + 1)) return false;
+            if (coset && !is_xfe_tuple(tuple, a)) return false;
+            std::vector<Xfe> v(a);
+            for (u32 j = 0; j < a; ++j) {
+                if (!is_xfe(tuple->items[j])) throw Fallback{};
+                v[j] = xfe_value_of(tuple->items[j]);
+            }
+            if (have_expected && !stored_eq(tuple->items[expected_at[s]], expected[s])) return false;
+            folded[s] = fold_coset(v, alpha, offset, omega, c_idx[s], q, k);
+            if (coset) continue;
+            if (!is_xfe(tuple->items[a])) throw Fallback{};
+            if (!stored_eq(tuple->items[a], folded[s])) return false;
+            next_ref[s] = tuple->items[a];
         }
-        omega = gl_mul(omega, omega);
-        offset = gl_mul(offset, offset);
+        // fri.py:311-315: the folded values are elements of the last codeword (coefficient values as stored); the coset form compares
+        // before it pulls the paths, the per-element protocols after
+        auto matches_last_codeword = [&]() {
+            for (u32 s = 0; s < t; ++s) {
+                const Ref& e = last->items[c_idx[s]];
+                if (!is_xfe(e)) throw Fallback{};
+                if (coset) { if (!stored_eq(e, folded[s])) return false; continue; }
+                if (!is_xfe(next_ref[s])) throw Fallback{};
+                if (next_ref[s]->limbs[0] != e->limbs[0] || next_ref[s]->limbs[1] != e->limbs[1] || next_ref[s]->limbs[2] != e->limbs[2]) return false;
+            }
+            return true;
+        };
+        if (coset && last_layer && !matches_last_codeword()) return false;
+        for (u32 s = 0; s < t; ++s) {
+            if (coset) {
+                const Ref path = rd.pull();
+                if (!is_digest_path(path, log2_of(q)) || !path_ok(rd.t, opened[s], nullptr, path, c_idx[s], roots[r])) return false;
+                continue;
+            }
+            for (u32 j = 0; j < a; ++j)
+                if (!path_ok(rd.t, opened[s]->items[j], nullptr, rd.pull(), c_idx[s] + j * q, roots[r])) return false;
+            if (!last_layer && !path_ok(rd.t, next_ref[s], nullptr, rd.pull(), c_idx[s], roots[r + 1])) return false;
+        }
+        if (!coset && last_layer && !matches_last_codeword()) return false;
+        if (coset && !last_layer) {
+            const u64 q_next = q >> k;
+            for (u32 s = 0; s < t; ++s) { expected_at[s] = (u32)(c_idx[s] / q_next); expected[s] = folded[s]; }
+            have_expected = true;
+        }
+        for (u32 j = 0; j < k; ++j) { omega = gl_mul(omega, omega); offset = gl_mul(offset, offset); }
     }
     return true;
 }
 
-int verify_finish(Transcript* t, const bfs_stark_verify_params& P, const u64* shifts, u32 num_terms) {
+int verify_finish(Transcript* t, const bfs_stark_verify_params& P, const u64* shifts, u32 num_terms, const FriMode& M) {
     Reader rd{t};
     Begin b;
     read_begin(rd, b);
@@ -356,12 +454,19 @@ int verify_finish(Transcript* t, const bfs_stark_verify_params& P, const u64* sh
             inner = xfe_add(inner, xfe_mul(Xfe{{weights[3 * i], weights[3 * i + 1], weights[3 * i + 2]}}, terms[i]));
         Ref leaf = rd.pull();
         Ref path = rd.pull();
-        if (!path_ok(t, leaf, nullptr, path, index, comb_root)) return V_FALSE;
+        if (M.coset) {
+            // the combination tree has one leaf per folding coset: the opened leaf is the tuple of the a values at c + j q, c = index mod q,
+            // authenticated at c by log2 q digests; the combination value at `index` is its element number index / q
+            const u64 q = n >> M.k;
+            if (!is_xfe_tuple(leaf, 1u << M.k) || !is_digest_path(path, log2_of(q))) return V_FALSE;
+            if (!path_ok(t, leaf, nullptr, path, index % q, comb_root)) return V_FALSE;
+            leaf = leaf->items[index / q];
+        } else if (!path_ok(t, leaf, nullptr, path, index, comb_root)) return V_FALSE;
         // brainfuck_stark.py:567 compares the leaf OBJECT with the inner product: coefficient values as stored
         if (!leaf || leaf->kind != rp::K_INSTANCE || leaf->role != rp::R_XFE) return V_FALSE;
         if (leaf->limbs[0] != inner.c[0] || leaf->limbs[1] != inner.c[1] || leaf->limbs[2] != inner.c[2]) return V_FALSE;
     }
-    bool verdict = fri_verify(rd, P, comb_root);
+    bool verdict = fri_verify(rd, P, comb_root, M);
     // evaluation arguments (evaluation_argument.py:1-53): the input / output symbols in gamma / delta, the program rows in eta
     auto C = [&](int i) { return Xfe{{b.challenges[3 * i], b.challenges[3 * i + 1], b.challenges[3 * i + 2]}}; };
     auto horner_symbols = [&](const u64* s, size_t count, const Xfe& point) {
@@ -459,7 +564,23 @@ int bfs_stark_verify_finish(void* ps, const bfs_stark_verify_params* params, con
     if (params->log_n < 2 || params->log_n > 32 || params->num_distances > 8 || params->expansion_factor < 2) { set_error("bfs_stark_verify_finish: parameters"); return BFS_ERR_BAD_ARG; }
     for (uint32_t s = 0; s < num_terms; ++s)
         if (shifts[s] >> 32) { set_error("bfs_stark_verify_finish: shift of term %u does not fit 32 bits", s); return BFS_ERR_BAD_ARG; }
-    return guarded([&]() { return verify_finish(t, *params, shifts, num_terms); }, verdict);
+    return guarded([&]() { return verify_finish(t, *params, shifts, num_terms, FriMode{}); }, verdict);
+}
+
+int bfs_stark_verify_finish_fri(void* ps, const bfs_stark_verify_params* params, const uint64_t* shifts, uint32_t num_terms, uint32_t log2_folding,
+                                int coset_leaves, uint32_t grinding_bits, int* verdict) {
+    Transcript* t = (Transcript*)ps;
+    if (!t || !t->loaded_from_bytes) { set_error("bfs_stark_verify_finish_fri: the stream was not read by bfs_ps_loads"); return BFS_ERR_BAD_ARG; }
+    if (params->log_n < 2 || params->log_n > 32 || params->num_distances > 8 || params->expansion_factor < 2) { set_error("bfs_stark_verify_finish_fri: parameters"); return BFS_ERR_BAD_ARG; }
+    if (log2_folding < 1 || log2_folding > 3 || grinding_bits > 40 || (coset_leaves && params->log_n <= log2_folding)) {
+        set_error("bfs_stark_verify_finish_fri: log2_folding %u, grinding_bits %u", log2_folding, grinding_bits);
+        return BFS_ERR_BAD_ARG;
+    }
+    for (uint32_t s = 0; s < num_terms; ++s)
+        if (shifts[s] >> 32) { set_error("bfs_stark_verify_finish_fri: shift of term %u does not fit 32 bits", s); return BFS_ERR_BAD_ARG; }
+    FriMode mode;
+    mode.k = log2_folding; mode.coset = coset_leaves != 0; mode.grinding = grinding_bits;
+    return guarded([&]() { return verify_finish(t, *params, shifts, num_terms, mode); }, verdict);
 }
 
 }  // extern "C"

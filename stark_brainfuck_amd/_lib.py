@@ -171,6 +171,12 @@ _SIGNATURES = {
                               ctypes.POINTER(u64), vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), vp]),
 }
 
+# include/bfstark_ext.h: entry points declared beside bfstark.h (the header says why); bound together with the table above
+_EXT_SIGNATURES = {
+    "bfs_poly_eval_points": (ci, [vp, u64, u64, u32, ctypes.POINTER(u64), u32, vp, vp]),
+    "bfs_deep_quotient": (ci, [vp, u32, u64, u32, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), u32, ctypes.POINTER(u64), vp, u64, vp]),
+}
+
 
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
@@ -245,6 +251,11 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
+def ext_exported_symbols():
+    """names include/bfstark_ext.h declares beyond bfstark.h's"""
+    return sorted(_EXT_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -261,7 +272,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

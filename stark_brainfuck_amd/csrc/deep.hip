@@ -1,0 +1,183 @@
+// deep.hip -- opening committed polynomials at points outside the FRI domain (include/bfstark_ext.h): the values f_b(z_j) of
+// coefficient columns in HBM at up to four points of F_p^3, and the DEEP quotient codeword that ties the values to the committed
+// codewords.  The per-thread arithmetic, with the cost argument, is deep_core.hpp; DESIGN.md "Opening at out-of-domain points".
+// Neither entry synchronises, copies from the host or allocates outside the stream-ordered pool: the points, weights and constants
+// of a call travel as kernel arguments.
+#include "../../include/bfstark_ext.h"
+#include "deep_core.hpp"
+#include "runtime.hpp"
+
+namespace bfs {
+
+// the table of a launch (deep_core.hpp): block j = point j
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_table_kernel(DeepPoints pts, u64* table) {
+    deep_eval_table_entry(pts.z[blockIdx.x], blockIdx.x, threadIdx.x, table);
+}
+
+// the sum of the workgroup's 256 elements, in thread 0 (field addition is exact: any order gives the same element)
+__device__ __forceinline__ Xfe deep_block_sum(const Xfe& mine, u64* red) {
+    const u32 t = threadIdx.x;
+    __syncthreads();                                      // (the previous sum has been read)
+    red[t] = mine.c[0]; red[DEEP_EVAL_T + t] = mine.c[1]; red[2 * DEEP_EVAL_T + t] = mine.c[2];
+    __syncthreads();
+    for (u32 d = DEEP_EVAL_T / 2; d > 0; d >>= 1) {
+        if (t < d) {
+            red[t] = gl_add(red[t], red[t + d]);
+            red[DEEP_EVAL_T + t] = gl_add(red[DEEP_EVAL_T + t], red[DEEP_EVAL_T + t + d]);
+            red[2 * DEEP_EVAL_T + t] = gl_add(red[2 * DEEP_EVAL_T + t], red[2 * DEEP_EVAL_T + t + d]);
+        }
+        __syncthreads();
+    }
+    return Xfe{{red[0], red[DEEP_EVAL_T], red[2 * DEEP_EVAL_T]}};
+}
+
+// launch 1: grid (blocks, batch); partial[((b * K + j) * blocks + block) * 3 ..] = the workgroup's share of f_b(z_j) without its z_j^(B block)
+template <int K>
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_partial_kernel(const u64* coeffs, u64 n, u64 in_stride, const u64* table, u64* partial) {
+    __shared__ u64 steps[K * DEEP_EVAL_S * 3];
+    __shared__ u64 red[3 * DEEP_EVAL_T];
+    const u32 t = threadIdx.x;
+    for (u32 w = t; w < (u32)K * DEEP_EVAL_S * 3; w += DEEP_EVAL_T) steps[w] = table[DEEP_EVAL_STEPS_AT + w];
+    __syncthreads();
+    Xfe mine[K];
+    deep_eval_thread<K>(coeffs + (u64)blockIdx.y * in_stride, n, blockIdx.x, t, steps, table, mine);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const Xfe total = deep_block_sum(mine[j], red);
+        if (t == 0) {
+            u64* out = partial + (((u64)blockIdx.y * K + j) * gridDim.x + blockIdx.x) * 3;
+            out[0] = total.c[0]; out[1] = total.c[1]; out[2] = total.c[2];
+        }
+    }
+}
+
+// launch 2: block (b * k + j) adds the `blocks` partial sums of f_b(z_j), each scaled by (z_j^B)^block
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_combine_kernel(const u64* partial, u32 blocks, u32 k, const u64* table, u64* out) {
+    __shared__ u64 red[3 * DEEP_EVAL_T];
+    const u32 t = threadIdx.x, j = blockIdx.x % k;
+    const Xfe zb = deep_eval_block_power(table, j);
+    Xfe acc{{0, 0, 0}};
+    for (u32 p = t; p < blocks; p += DEEP_EVAL_T)
+        acc = xfe_add(acc, xfe_mul(xfe_load3(partial + ((u64)blockIdx.x * blocks + p) * 3), xfe_pow_small(zb, p)));
+    const Xfe total = deep_block_sum(acc, red);
+    if (t == 0) { out[(u64)blockIdx.x * 3] = total.c[0]; out[(u64)blockIdx.x * 3 + 1] = total.c[1]; out[(u64)blockIdx.x * 3 + 2] = total.c[2]; }
+}
+
+template <int K>
+__global__ void __launch_bounds__(DEEP_Q_T) deep_quotient_kernel(DeepQuotientArgs a, u64* out, u64 out_stride) {
+    const u64 first = (u64)blockIdx.x * (DEEP_Q_T * DEEP_Q_E) + threadIdx.x;
+    u64 idx[DEEP_Q_E];
+#pragma unroll
+    for (u32 e = 0; e < DEEP_Q_E; ++e) idx[e] = first + (u64)e * DEEP_Q_T;
+    Xfe g[DEEP_Q_E];
+    deep_quotient_thread<K>(a, idx, g);
+#pragma unroll
+    for (u32 e = 0; e < DEEP_Q_E; ++e) {
+        if (idx[e] < a.n) { out[idx[e]] = g[e].c[0]; out[out_stride + idx[e]] = g[e].c[1]; out[2 * out_stride + idx[e]] = g[e].c[2]; }
+    }
+}
+
+template <class Fn>
+static int with_point_count(u32 k, Fn&& fn) {
+    switch (k) {
+    case 1: return fn(std::integral_constant<int, 1>());
+    case 2: return fn(std::integral_constant<int, 2>());
+    case 3: return fn(std::integral_constant<int, 3>());
+    case 4: return fn(std::integral_constant<int, 4>());
+    default: set_error("the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG;
+    }
+}
+
+static bool canonical3(const u64* w) { return w[0] < GL_P && w[1] < GL_P && w[2] < GL_P; }
+
+static bool overlaps(const void* a, u64 a_bytes, const void* b, u64 b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+}  // namespace bfs
+
+using namespace bfs;
+
+extern "C" int bfs_poly_eval_points(const uint64_t* d_coeffs, uint64_t n_coeffs, uint64_t in_stride, uint32_t batch, const uint64_t* h_points,
+                                    uint32_t k, uint64_t* d_out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_coeffs || !h_points || !d_out) { set_error("bfs_poly_eval_points: null argument"); return BFS_ERR_BAD_ARG; }
+    if (n_coeffs < 1 || n_coeffs > (1ull << 24)) { set_error("bfs_poly_eval_points: n_coeffs must be 1..2^24 (got %llu)", (unsigned long long)n_coeffs); return BFS_ERR_BAD_ARG; }
+    if (batch < 1 || batch > 65535) { set_error("bfs_poly_eval_points: batch must be 1..65535 (got %u)", batch); return BFS_ERR_BAD_ARG; }
+    if (batch > 1 && in_stride < n_coeffs) { set_error("bfs_poly_eval_points: in_stride < n_coeffs"); return BFS_ERR_BAD_ARG; }
+    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfs_poly_eval_points: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
+    DeepPoints pts{};
+    for (u32 j = 0; j < k; ++j) {
+        if (!canonical3(h_points + 3 * j)) { set_error("bfs_poly_eval_points: point %u is not reduced", j); return BFS_ERR_BAD_ARG; }
+        pts.z[j] = Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}};
+    }
+    const u32 blocks = (u32)((n_coeffs + DEEP_EVAL_BLOCK - 1) / DEEP_EVAL_BLOCK);
+    const u64 results = (u64)batch * k;
+    if (overlaps(d_out, results * 24, d_coeffs, ((u64)(batch - 1) * in_stride + n_coeffs) * 8)) { set_error("bfs_poly_eval_points: d_out overlaps the coefficients"); return BFS_ERR_BAD_ARG; }
+    void* scratch = nullptr;
+    BFS_TRY(device_alloc((DEEP_EVAL_TABLE_WORDS + results * blocks * 3) * sizeof(u64), stream, &scratch));
+    u64* table = (u64*)scratch;
+    u64* partial = table + DEEP_EVAL_TABLE_WORDS;
+    hipLaunchKernelGGL(deep_eval_table_kernel, dim3(k), dim3(DEEP_EVAL_T), 0, stream, pts, table);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        (void)with_point_count(k, [&](auto kk) -> int {
+            hipLaunchKernelGGL((deep_eval_partial_kernel<decltype(kk)::value>), dim3(blocks, batch), dim3(DEEP_EVAL_T), 0, stream, d_coeffs, n_coeffs, in_stride,
+                               (const u64*)table, partial);
+            return BFS_OK;
+        });
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(deep_eval_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, (const u64*)partial, blocks, k, (const u64*)table, d_out);
+        e = hipGetLastError();
+    }
+    (void)device_release(scratch, stream);                // stream-ordered: the launches above are ahead of whoever gets the block next
+    if (e != hipSuccess) { set_error("bfs_poly_eval_points: %s", hipGetErrorString(e)); return BFS_ERR_HIP; }
+    return BFS_OK;
+}
+
+extern "C" int bfs_deep_quotient(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                                 const uint64_t* h_points, const uint64_t* h_values, uint32_t k, const uint64_t h_lambda[3], uint64_t* d_out,
+                                 uint64_t out_stride, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!h_columns || !h_points || !h_values || !h_lambda || !d_out) { set_error("bfs_deep_quotient: null argument"); return BFS_ERR_BAD_ARG; }
+    if (m < 1 || m > DEEP_MAX_COLUMNS) { set_error("bfs_deep_quotient: 1..%u codewords (got %u)", DEEP_MAX_COLUMNS, m); return BFS_ERR_BAD_ARG; }
+    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfs_deep_quotient: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
+    if (log_n < 1 || log_n > 24) { set_error("bfs_deep_quotient: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
+    const u64 n = 1ull << log_n;
+    if (limb_stride < n || out_stride < n) { set_error("bfs_deep_quotient: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
+    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfs_deep_quotient: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
+    if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
+    if (!canonical3(h_lambda)) { set_error("bfs_deep_quotient: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
+    DeepQuotientArgs a{};
+    a.m = m; a.limb_stride = limb_stride; a.n = n; a.offset = offset;
+    const Xfe lambda{{h_lambda[0], h_lambda[1], h_lambda[2]}};
+    const u64 out_bytes = (2 * out_stride + n) * 8;
+    Xfe power{{1, 0, 0}};                                 // lambda^p
+    for (u32 p = 0; p < m; ++p) {
+        const bfs_row_column& c = h_columns[p];
+        if (!c.d_values) { set_error("bfs_deep_quotient: codeword %u is null", p); return BFS_ERR_BAD_ARG; }
+        if (overlaps(d_out, out_bytes, c.d_values, (c.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfs_deep_quotient: d_out overlaps codeword %u", p); return BFS_ERR_BAD_ARG; }
+        a.col[p] = c.d_values;
+        if (c.is_ext) a.ext_mask |= 1u << p;
+        lazy_weight_matrix(power, a.weight[p]);
+        power = xfe_mul(power, lambda);
+    }
+    Xfe scale{{1, 0, 0}};                                 // lambda^(j m)
+    for (u32 j = 0; j < k; ++j) {
+        if (!canonical3(h_points + 3 * j) || !canonical3(h_values + 3 * j)) { set_error("bfs_deep_quotient: point or value %u is not reduced", j); return BFS_ERR_BAD_ARG; }
+        deep_point_consts(a.pt[j], Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}}, scale,
+                          Xfe{{h_values[3 * j], h_values[3 * j + 1], h_values[3 * j + 2]}});
+        scale = xfe_mul(scale, power);
+    }
+    BFS_TRY(ntt_power_tables(omega, log_n, &a.w_lo, &a.w_hi, &a.lo_bits));
+    const u32 grid = (u32)((n + DEEP_Q_T * DEEP_Q_E - 1) / (DEEP_Q_T * DEEP_Q_E));
+    BFS_TRY(with_point_count(k, [&](auto kk) -> int {
+        hipLaunchKernelGGL((deep_quotient_kernel<decltype(kk)::value>), dim3(grid), dim3(DEEP_Q_T), 0, stream, a, d_out, out_stride);
+        return BFS_OK;
+    }));
+    BFS_HIP(hipGetLastError());
+    return BFS_OK;
+}

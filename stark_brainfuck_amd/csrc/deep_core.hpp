@@ -1,0 +1,189 @@
+// deep_core.hpp -- the per-thread half of the two kernels of deep.hip, host/device, so that tests/emu/emu_deep.cpp runs it against
+// CPython integers:
+//   1. out-of-domain evaluation  f(z_j) = sum_i c_i z_j^i  of a column of BASE coefficients at up to four points of F_p^3;
+//   2. the DEEP quotient  g[i] = sum_j (lambda^(j m) S_i - Y_j) / (x_i - z_j),  S_i = sum_p lambda^p f_p(x_i),  over x_i = offset omega^i.
+//
+// Evaluation.  A workgroup of T = 256 threads owns B = T * S = 16384 consecutive coefficients; thread t takes c[b B + s T + t], s < S
+// (coalesced), and
+//     sum_{s, t} c[b B + s T + t] z^(s T + t) = sum_t z^t * ( sum_s c[..] * (z^T)^s ).
+// The inner sum has the SAME weight (z^T)^s in every lane -- a table of S elements per point -- so a coefficient costs one
+// base-by-extension product per point, three base products, accumulated without reduction (lazy.hpp: 24 VALU instructions); the
+// thread's sum is reduced once and multiplied by the lane's own z^t (the only extension-by-extension product, one per S coefficients),
+// the workgroup adds its 256 values, and the combining launch scales workgroup b's sum by (z^B)^b.  Horner's rule would pay nine base
+// products and a reduction per coefficient and could not share a load between the points.
+//
+// Quotient.  A thread owns E = 2 points of the domain.  S_i is one unreduced weighted sum over the m codewords (lazy.hpp, the weights
+// lambda^p wave-uniform), whatever k is.  1 / (x - z) for x in F_p is adj / norm with the cofactors and the norm of the matrix of
+// multiplication by (x - z0) - z1 X - z2 X^2 (pointwise.hip: xfe_cofactors_kernel); z1 and z2 do not depend on the point of the domain,
+// so their products are constants of the launch.  The E * k norms of a thread share ONE base-field inversion (Montgomery's trick).
+#pragma once
+#include <stddef.h>
+
+#include "lazy.hpp"
+
+namespace bfs {
+
+constexpr u32 DEEP_MAX_POINTS = 4;
+constexpr u32 DEEP_MAX_COLUMNS = 32;                       // bfs_merkle_build_rows' limit
+constexpr u32 DEEP_EVAL_T = 256;                           // threads of a workgroup = distance between two coefficients of a thread
+constexpr u32 DEEP_EVAL_S = 64;                            // coefficients of a thread
+constexpr u32 DEEP_EVAL_BLOCK = DEEP_EVAL_T * DEEP_EVAL_S; // coefficients of a workgroup
+// the table of one launch, words: lane factors z_j^t at ((j T + t) * 3), behind all of them the step weights z_j^(T s) at ((j S + s) * 3)
+constexpr u32 DEEP_EVAL_STEPS_AT = DEEP_MAX_POINTS * DEEP_EVAL_T * 3;
+constexpr u32 DEEP_EVAL_TABLE_WORDS = DEEP_EVAL_STEPS_AT + DEEP_MAX_POINTS * DEEP_EVAL_S * 3;
+
+struct DeepPoints {
+    Xfe z[DEEP_MAX_POINTS];
+};
+
+BFS_HD Xfe xfe_load3(const u64* w) { return Xfe{{w[0], w[1], w[2]}}; }
+
+BFS_HD Xfe xfe_pow_small(Xfe a, u64 e) {
+    Xfe acc{{1, 0, 0}};
+    while (e) {
+        if (e & 1) acc = xfe_mul(acc, a);
+        e >>= 1;
+        if (e) a = xfe_mul(a, a);
+    }
+    return acc;
+}
+
+// entry t < T of point j's part of the table (and, for t < S, step weight t)
+BFS_HD void deep_eval_table_entry(const Xfe& z, u32 j, u32 t, u64* table) {
+    const Xfe lane = xfe_pow_small(z, t);
+    u64* at = table + ((size_t)j * DEEP_EVAL_T + t) * 3;
+    at[0] = lane.c[0]; at[1] = lane.c[1]; at[2] = lane.c[2];
+    if (t < DEEP_EVAL_S) {
+        const Xfe step = xfe_pow_small(z, (u64)t * DEEP_EVAL_T);
+        u64* st = table + DEEP_EVAL_STEPS_AT + ((size_t)j * DEEP_EVAL_S + t) * 3;
+        st[0] = step.c[0]; st[1] = step.c[1]; st[2] = step.c[2];
+    }
+}
+
+// thread t of workgroup `block`: z_j^t * sum_s col[block B + s T + t] * z_j^(T s), j < K.  steps: K * S * 3 words, point-major (LDS on
+// the device); lanes: the table's lane factors
+template <int K>
+BFS_HD void deep_eval_thread(const u64* col, u64 n, u64 block, u32 t, const u64* steps, const u64* lanes, Xfe out[K]) {
+    LazyX acc[K];
+    BFS_UNROLL
+    for (int j = 0; j < K; ++j) acc[j] = lazyx_zero();
+    const u64 first = block * DEEP_EVAL_BLOCK + t;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 4
+#endif
+    for (u32 s = 0; s < DEEP_EVAL_S; ++s) {
+        const u64 i = first + (u64)s * DEEP_EVAL_T;
+        const u64 c = i < n ? col[i] : 0;
+        BFS_UNROLL
+        for (int j = 0; j < K; ++j) lazyx_mac_base(acc[j], steps + ((size_t)j * DEEP_EVAL_S + s) * 3, c);
+    }
+    BFS_UNROLL
+    for (int j = 0; j < K; ++j) out[j] = xfe_mul(lazyx_reduce(acc[j]), xfe_load3(lanes + ((size_t)j * DEEP_EVAL_T + t) * 3));
+}
+
+// z^B from the table of point j: z^(T (S - 1)) * z^T
+BFS_HD Xfe deep_eval_block_power(const u64* table, u32 j) {
+    const u64* st = table + DEEP_EVAL_STEPS_AT + (size_t)j * DEEP_EVAL_S * 3;
+    return xfe_mul(xfe_load3(st + (DEEP_EVAL_S - 1) * 3), xfe_load3(st + 3));
+}
+
+// ---- the quotient ----
+constexpr u32 DEEP_Q_T = 256;       // threads of a workgroup
+constexpr u32 DEEP_Q_E = 2;         // points of a thread, DEEP_Q_T apart
+
+struct DeepPointConsts {            // of one z = (z0, z1, z2), with a1 = -z1, a2 = -z2, d = a1 - a2
+    u64 z0, a1, a2, d_a1, d_a2, a1_sq;
+    Xfe scale;                      // lambda^(j m)
+    Xfe y;                          // Y_j
+};
+
+struct DeepQuotientArgs {
+    const u64* col[DEEP_MAX_COLUMNS];
+    u64 weight[DEEP_MAX_COLUMNS][LAZY_W_EXT];      // lambda^p as lazy.hpp lays a weight out (a base column reads the first three words)
+    DeepPointConsts pt[DEEP_MAX_POINTS];
+    u32 m, ext_mask;                // bit p: column p is an extension column (three planes, limb_stride apart)
+    u64 limb_stride, n, offset;
+    const u64* w_lo;                // two-level powers of omega
+    const u64* w_hi;
+    u32 lo_bits;
+};
+
+inline void deep_point_consts(DeepPointConsts& c, const Xfe& z, const Xfe& scale, const Xfe& y) {
+    c.z0 = z.c[0];
+    c.a1 = gl_neg(z.c[1]);
+    c.a2 = gl_neg(z.c[2]);
+    const u64 d = gl_sub(c.a1, c.a2);
+    c.d_a1 = gl_mul(d, c.a1);
+    c.d_a2 = gl_mul(d, c.a2);
+    c.a1_sq = gl_mul(c.a1, c.a1);
+    c.scale = scale;
+    c.y = y;
+}
+
+// S_i: the weighted sum of the m codewords at point i
+BFS_HD Xfe deep_row_sum(const DeepQuotientArgs& a, u64 i) {
+    LazyX L = lazyx_zero();
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+    for (u32 p = 0; p < a.m; ++p) {
+        const u64* w = a.weight[p];
+        const u64* src = a.col[p];
+        if ((a.ext_mask >> p) & 1) {
+            const Xfe v{{src[i], src[a.limb_stride + i], src[2 * a.limb_stride + i]}};
+            lazy_mac(L.r[0], v.c[0], w[0]); lazy_mac(L.r[0], v.c[1], w[3]); lazy_mac(L.r[0], v.c[2], w[4]);
+            lazy_mac(L.r[1], v.c[0], w[1]); lazy_mac(L.r[1], v.c[1], w[5]); lazy_mac(L.r[1], v.c[2], w[6]);
+            lazy_mac(L.r[2], v.c[0], w[2]); lazy_mac(L.r[2], v.c[1], w[1]); lazy_mac(L.r[2], v.c[2], w[5]);
+        } else {
+            const u64 v = src[i];
+            lazy_mac(L.r[0], v, w[0]); lazy_mac(L.r[1], v, w[1]); lazy_mac(L.r[2], v, w[2]);
+        }
+    }
+    return lazyx_reduce(L);
+}
+
+// the E points idx[e] of one thread (idx[e] >= n: none); K points z_j
+template <int K>
+BFS_HD void deep_quotient_thread(const DeepQuotientArgs& a, const u64 idx[DEEP_Q_E], Xfe out[DEEP_Q_E]) {
+    Xfe sum[DEEP_Q_E], cof[DEEP_Q_E][K];
+    u64 norm[DEEP_Q_E][K], before[DEEP_Q_E][K];
+    u64 run = 1;
+    BFS_UNROLL
+    for (u32 e = 0; e < DEEP_Q_E; ++e) {
+        const bool live = idx[e] < a.n;
+        const u64 i = live ? idx[e] : 0;
+        sum[e] = deep_row_sum(a, i);
+        const u64 x = gl_mul(a.offset, gl_mul(a.w_lo[i & ((1ull << a.lo_bits) - 1)], a.w_hi[i >> a.lo_bits]));
+        BFS_UNROLL
+        for (int j = 0; j < K; ++j) {
+            const DeepPointConsts& c = a.pt[j];
+            const u64 a0 = gl_sub(x, c.z0);
+            const u64 s = gl_add(a0, c.a2);
+            const u64 c0 = gl_sub(gl_mul(s, s), c.d_a1);                       // (a0+a2)^2 - (a1-a2) a1
+            const u64 c1 = gl_sub(c.d_a2, gl_mul(c.a1, s));                    // (a1-a2) a2 - a1 (a0+a2)
+            const u64 c2 = gl_sub(c.a1_sq, gl_mul(s, c.a2));                   // a1^2 - (a0+a2) a2
+            u64 nm = gl_sub(gl_mul(a0, c0), gl_add(gl_mul(c.a2, c1), gl_mul(c.a1, c2)));
+            if (nm == 0) nm = 1;          // x = z: the caller has refused such points; the thread's other inverses stay right
+            cof[e][j] = Xfe{{c0, c1, c2}};
+            norm[e][j] = nm;
+            before[e][j] = run;
+            run = gl_mul(run, nm);
+        }
+    }
+    u64 inv = gl_inv(run);
+    BFS_UNROLL
+    for (int e = DEEP_Q_E - 1; e >= 0; --e) {
+        LazyX G = lazyx_zero();
+        BFS_UNROLL
+        for (int j = K - 1; j >= 0; --j) {
+            const u64 ninv = gl_mul(inv, before[e][j]);
+            inv = gl_mul(inv, norm[e][j]);
+            const Xfe scaled = j == 0 ? sum[e] : xfe_mul(sum[e], a.pt[j].scale);      // (lambda^0 = 1)
+            const Xfe num = xfe_sub(scaled, a.pt[j].y);
+            lazyx_mac_scale(G, xfe_mul(num, cof[e][j]), ninv);
+        }
+        out[e] = lazyx_reduce(G);
+    }
+}
+
+}  // namespace bfs

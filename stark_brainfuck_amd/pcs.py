@@ -1,0 +1,401 @@
+"""A polynomial commitment from FRI: commit to polynomials, then prove what they evaluate to at points OUTSIDE the FRI domain.
+
+    evaluate_at(coeffs, points)                       values of coefficient arrays in HBM at points of the extension field
+    PolynomialCommitment(fri)
+      .commit(polys, proof_stream) -> Commitment      codewords + one unsalted row tree in HBM; pushes the root
+      .open(commitment, points, proof_stream)         pushes the opening proof; returns the values
+      .verify(root, points, values, proof_stream)     host only (ints, hashlib, Fri.verify)
+
+The reference has nothing of the kind: its STARK only ever opens committed codewords ON the domain.  The statement "the polynomial behind
+this root takes the value y at z" is reduced to a low-degree test of the DEEP quotient (csrc/deep.hip, include/bfstark_ext.h)
+
+    g(x) = sum_{j < k} ( lambda^(j m) * S(x) - Y_j ) / (x - z_j),   S = sum_{p < m} lambda^p f_p,   Y_j = sum_{p < m} lambda^(j m + p) y_{p,j}
+
+over the m committed columns f_p (extension columns first, then base columns, each group in the caller's order) with one Fiat-Shamir
+challenge lambda: g is a polynomial of degree < d exactly when every y_{p,j} = f_p(z_j).
+
+Proof stream of `open`, after the root that `commit` pushed:
+    the points (a list of elements); the values (a list per point of a list per polynomial, in row order);
+    [lambda = xfield.sample(fiat_shamir)];  the root of the tree over g (Merkle, or CosetMerkle when the Fri commits to cosets);
+    [t indices = BrainfuckStark.sample_indices(t, fiat_shamir, N)];  per index i: the row tuple at x_i, its authentication path, the
+    opening of g (the element g[i] and its path; with coset leaves the tuple of leaf i mod (N / a) and its one path);
+    then Fri.prove over g.
+"""
+import ctypes
+from hashlib import blake2b
+
+import numpy as np
+
+from . import _lib
+from .air import P, xadd, xinv, xmul, xsub
+from .algebra import BaseFieldElement
+from .arrays import BaseArray, XArray, raw_ntt
+from .device import DeviceBuffer, current_stream, gather
+from .extension_field import ExtensionFieldElement
+from .merkle import CosetMerkle, Merkle
+from .ntt import _base_value
+
+_u64 = ctypes.c_uint64
+MAX_POINTS_PER_LAUNCH = 4          # bfs_poly_eval_points, bfs_deep_quotient
+MAX_COLUMNS, MAX_EXT_COLUMNS = 32, 16   # bfs_merkle_build_rows
+
+
+def _limbs(z):
+    """(c0, c1, c2) of an ExtensionFieldElement, a BaseFieldElement, an int or a limb triple"""
+    if isinstance(z, ExtensionFieldElement):
+        return tuple(z.limbs())
+    if isinstance(z, BaseFieldElement):
+        return (z.value % P, 0, 0)
+    if isinstance(z, (tuple, list)):
+        return tuple(int(v) % P for v in z)
+    return (int(z) % P, 0, 0)
+
+
+def _times_x(a):
+    """a * X in F_p[X]/(X^3 - X + 1)"""
+    return (-a[2] % P, (a[0] + a[2]) % P, a[1])
+
+
+def _eval_jobs(jobs, points):
+    """jobs: (ptr, n, stride, batch) coefficient arrays -> per job [[limb triple of column b at point j] per column] per point:
+    bfs_poly_eval_points, four points per launch, every launch enqueued before the ONE read-back of all results"""
+    lib, stream = _lib.load(), current_stream()
+    out = DeviceBuffer(3 * len(points) * sum(job[3] for job in jobs))
+    at = 0
+    for ptr, n, stride, batch in jobs:
+        for first in range(0, len(points), MAX_POINTS_PER_LAUNCH):
+            chunk = points[first:first + MAX_POINTS_PER_LAUNCH]
+            flat = (_u64 * (3 * len(chunk)))(*[v for z in chunk for v in z])
+            _lib.check(lib.bfs_poly_eval_points(ptr, n, stride, batch, flat, len(chunk), out.ptr + 8 * at, stream))
+            at += 3 * batch * len(chunk)
+    words = [int(v) for v in out.to_numpy()]
+    out.free()
+    results, at = [], 0
+    for ptr, n, stride, batch in jobs:
+        values = [[None] * batch for _ in points]
+        for first in range(0, len(points), MAX_POINTS_PER_LAUNCH):
+            k = min(MAX_POINTS_PER_LAUNCH, len(points) - first)
+            for b in range(batch):
+                for j in range(k):
+                    values[first + j][b] = tuple(words[at:at + 3])
+                    at += 3
+        results.append(values)
+    return results
+
+
+def _eval_columns(ptr, n, stride, batch, points):
+    return _eval_jobs([(ptr, n, stride, batch)], points)[0]
+
+
+def _combine_planes(v):
+    """v0 + X v1 + X^2 v2 for the values of an extension polynomial's three limb columns"""
+    return xadd(v[0], xadd(_times_x(v[1]), _times_x(_times_x(v[2]))))
+
+
+def evaluate_at(coeffs, points, xfield=None):
+    """f(z) for every z of `points` (ExtensionFieldElements; BaseFieldElements and ints are lifted), f given by coefficients in HBM.
+    coeffs: an XArray, or a BaseArray -- of batch 1: a list with one ExtensionFieldElement per point; of batch b > 1: per point a list
+    of the b columns' values.  The coefficients are read once per four points and nothing but the 3 k (b) result words leaves HBM."""
+    from .extension_field import ExtensionField
+    pts = [_limbs(z) for z in points]
+    xf = xfield or next((z.field for z in points if isinstance(z, ExtensionFieldElement)), None) or (coeffs.field if isinstance(coeffs, XArray) else ExtensionField.main())
+    if not pts:
+        return []
+    assert len(coeffs) >= 1, "evaluate_at: no coefficients (the zero polynomial is one zero coefficient)"
+    if isinstance(coeffs, XArray):
+        raw = _eval_columns(coeffs.ptr, coeffs.n, coeffs.stride, 3, pts)
+        return [xf.from_limbs(_combine_planes(v)) for v in raw]
+    assert isinstance(coeffs, BaseArray), "evaluate_at takes a BaseArray or an XArray"
+    raw = _eval_columns(coeffs.ptr, coeffs.n, coeffs.n, coeffs.batch, pts)
+    if coeffs.batch == 1:
+        return [xf.from_limbs(v[0]) for v in raw]
+    return [[xf.from_limbs(c) for c in v] for v in raw]
+
+
+class _RowCount:
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+
+class Commitment:
+    """what `commit` returns: coefficients, codewords and the row tree, all in HBM"""
+
+    def __init__(self, polys, is_ext, order, codewords, n, tree):
+        self.polys, self.is_ext, self.order, self.codewords, self.n, self.tree = polys, is_ext, order, codewords, n, tree
+        self.n_ext = sum(is_ext)
+        self.n_base = len(polys) - self.n_ext
+        self._rows = {}
+
+    def root(self):
+        return self.tree.root()
+
+    def column_ptr(self, c):
+        """first word of column c of the row (extension columns first)"""
+        return self.codewords.ptr + 8 * self.n * (3 * c if c < self.n_ext else 3 * self.n_ext + (c - self.n_ext))
+
+    def row_requests(self, i):
+        reqs = [(self.column_ptr(c) + 8 * i, 3, self.n) for c in range(self.n_ext)]
+        if self.n_base:
+            reqs.append((self.column_ptr(self.n_ext) + 8 * i, self.n_base, self.n))
+        return reqs
+
+
+class PolynomialCommitment:
+    """commit / open / verify over a `Fri` of any mode (folding factor, coset leaves, grinding).
+
+    With N = fri.domain.length, d = N // fri.expansion_factor and t = fri.num_colinearity_tests: polynomials have at most d coefficients
+    (a polynomial with more is not what the low-degree test vouches for).  An accepted opening says: the columns behind `root` are
+    within the FRI proximity bound of polynomials of degree < d that take the claimed values.
+
+    What this scheme is NOT:
+      * it is not hiding -- the row tree is unsalted and no randomizer polynomial is mixed into g: the opened rows are plain values of
+        the committed polynomials, and the values themselves are in the proof;
+      * it does not choose the points -- the caller must draw them AFTER the commitment's root is in the transcript (from
+        proof_stream.prover_fiat_shamir()); for points fixed beforehand a prover can commit to polynomials made to fit.
+    Points of the FRI domain cannot be opened (the quotient's denominator vanishes there): `open` refuses them."""
+
+    def __init__(self, fri):
+        self.fri = fri
+        self.xfield = fri.field
+        self.n = fri.domain.length
+        self.max_coefficients = self.n // fri.expansion_factor
+        self.offset, self.omega = _base_value(fri.domain.offset), _base_value(fri.domain.omega)
+
+    # ---------------------------------------------------------------------------------------------------------- shared
+    def _base_field(self):
+        return self.xfield.modulus.coefficients[0].field          # the BaseField instance the rows' base elements point at
+
+    def in_domain(self, z):
+        """is z one of the points offset * omega^i: a lifted base value v with (v / offset)^N = 1"""
+        c0, c1, c2 = _limbs(z)
+        return c1 == 0 and c2 == 0 and pow(c0 * pow(self.offset, P - 2, P) % P, self.n, P) == 1
+
+    @staticmethod
+    def _indices(t, seed, n):
+        return [int.from_bytes(blake2b(seed + bytes(i)).digest(), "big") % n for i in range(t)]      # BrainfuckStark.sample_indices
+
+    @staticmethod
+    def _combined_values(values, lam):
+        """Y_j = sum_p lambda^(j m + p) y_{p,j}, p in row order"""
+        out, power = [], (1, 0, 0)
+        for per_point in values:
+            acc = (0, 0, 0)
+            for y in per_point:
+                acc = xadd(acc, xmul(power, y))
+                power = xmul(power, lam)
+            out.append(acc)
+        return out
+
+    # ---------------------------------------------------------------------------------------------------------- prover
+    def commit(self, polys, proof_stream):
+        """polys: BaseArrays (batch 1) and XArrays of coefficients in HBM, at most N // expansion_factor each; at most 32 columns, at
+        most 16 of them extension columns.  Extends every polynomial to the FRI domain (bfs_gl_ntt), hashes the rows
+        (bfs_merkle_build_rows without salts: leaf i = the tuple of all values at x_i, extension columns first) and pushes the root."""
+        lib, stream, n = _lib.load(), current_stream(), self.n
+        assert polys, "nothing to commit to"
+        for f in polys:
+            assert isinstance(f, XArray) or (isinstance(f, BaseArray) and f.batch == 1), "polynomials are BaseArrays of batch 1 and XArrays"
+            assert 1 <= len(f) <= self.max_coefficients, "a polynomial has 1 .. N / expansion_factor coefficients"
+        is_ext = [isinstance(f, XArray) for f in polys]
+        order = [i for i, e in enumerate(is_ext) if e] + [i for i, e in enumerate(is_ext) if not e]
+        n_ext = sum(is_ext)
+        assert len(polys) <= MAX_COLUMNS and n_ext <= MAX_EXT_COLUMNS, "at most 32 columns, at most 16 extension columns"
+        codewords = DeviceBuffer((3 * n_ext + len(polys) - n_ext) * n)
+        committed = Commitment(list(polys), is_ext, order, codewords, n, None)
+        log_n = n.bit_length() - 1
+        cols = (_lib.RowColumn * len(polys))()
+        for c, position in enumerate(order):
+            f = polys[position]
+            if is_ext[position]:
+                raw_ntt(f.ptr, f.n, f.stride, committed.column_ptr(c), n, log_n, 3, self.omega, self.offset, 1, stream)
+            else:
+                raw_ntt(f.ptr, f.n, f.n, committed.column_ptr(c), n, log_n, 1, self.omega, self.offset, 1, stream)
+            cols[c].d_values, cols[c].is_ext, cols[c].field_id = committed.column_ptr(c), int(is_ext[position]), 1
+        nodes = DeviceBuffer(2 * n * 8)
+        _lib.check(lib.bfs_merkle_build_rows(cols, len(polys), n, None, 0, nodes.ptr, stream))
+        committed.tree = Merkle(_RowCount(n), _device_nodes=nodes)
+        proof_stream.push(committed.tree.root())
+        return committed
+
+    def _row(self, committed, i, words):
+        """the tuple of element objects of row i (one object per row: a row opened twice is the same tuple twice)"""
+        if i not in committed._rows:
+            xf, base = self.xfield, self._base_field()
+            ext = [xf.from_limbs([int(v) for v in words[3 * c:3 * c + 3]]) for c in range(committed.n_ext)]
+            committed._rows[i] = tuple(ext + [BaseFieldElement(int(v), base) for v in words[3 * committed.n_ext:]])
+        return committed._rows[i]
+
+    def quotient(self, committed, points, values, lam):
+        """the DEEP quotient codeword (XArray) of the commitment's columns: bfs_deep_quotient"""
+        n, m = self.n, len(committed.polys)
+        cols = (_lib.RowColumn * m)()
+        for c in range(m):
+            cols[c].d_values, cols[c].is_ext, cols[c].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
+        combined = self._combined_values(values, lam)
+        g = XArray.empty(n, self.xfield)
+        _lib.check(_lib.load().bfs_deep_quotient(cols, m, n, n.bit_length() - 1, self.offset, self.omega,
+                                                 (_u64 * (3 * len(points)))(*[v for z in points for v in z]),
+                                                 (_u64 * (3 * len(points)))(*[v for y in combined for v in y]), len(points),
+                                                 (_u64 * 3)(*lam), g.ptr, g.stride, current_stream()))
+        return g
+
+    def open(self, committed, points, proof_stream):
+        """proves the values of every committed polynomial at `points` (1..4 ExtensionFieldElements outside the FRI domain); returns
+        them: a list per point of a list per polynomial IN ROW ORDER -- extension polynomials first, then base polynomials, each group in
+        the order `commit` was given them (Commitment.order[c] = position of row column c in that list)"""
+        xf, n, t, fri = self.xfield, self.n, self.fri.num_colinearity_tests, self.fri
+        assert 1 <= len(points) <= MAX_POINTS_PER_LAUNCH, "1 .. 4 points per opening"
+        for z in points:
+            if self.in_domain(z):
+                raise ValueError("cannot open at a point of the FRI domain: %s" % (z,))
+        pts = [_limbs(z) for z in points]
+        point_objects = [xf.from_limbs(z) for z in pts]
+        proof_stream.push(point_objects)
+        raw = [[None] * len(committed.polys) for _ in pts]
+        in_row_order = [committed.polys[position] for position in committed.order]
+        jobs = [(f.ptr, f.n, f.stride, 3) if isinstance(f, XArray) else (f.ptr, f.n, f.n, 1) for f in in_row_order]
+        for c, (f, got) in enumerate(zip(in_row_order, _eval_jobs(jobs, pts))):
+            for j, v in enumerate(got):
+                raw[j][c] = _combine_planes(v) if isinstance(f, XArray) else v[0]
+        values = [[xf.from_limbs(v) for v in per_point] for per_point in raw]
+        proof_stream.push(values)
+        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
+        g = self.quotient(committed, pts, raw, lam)
+        coset = fri.coset_leaves
+        a = fri.folding_factor if coset else 1
+        q = n // a
+        g_tree = CosetMerkle(g, a) if coset else Merkle(g)
+        proof_stream.push(g_tree.root())
+        indices = self._indices(t, proof_stream.prover_fiat_shamir(), n)
+        # everything the openings read from HBM in one round trip
+        rows = list(dict.fromkeys(indices))
+        leaves = list(dict.fromkeys(i % q for i in indices))
+        requests, spans = [], {}
+        for i in rows:
+            reqs = committed.row_requests(i)
+            spans["row", i] = (len(requests), len(reqs))
+            requests += reqs
+        for c in leaves:
+            spans["leaf", c] = (len(requests), a)
+            requests += [(g.ptr + 8 * (c + j * q), 3, g.stride) for j in range(a)]
+        fetched = gather(requests)
+        starts = np.concatenate([[0], np.cumsum([r[1] for r in requests])])
+
+        def words(key):
+            first, count = spans[key]
+            return fetched[starts[first]:starts[first + count]]
+        known = {}
+        for i in indices:
+            proof_stream.push(self._row(committed, i, words(("row", i))))
+            proof_stream.push(committed.tree.open(i))
+            c = i % q
+            if c not in known:
+                w = [int(v) for v in words(("leaf", c))]
+                elements = [xf.from_limbs(w[3 * j:3 * j + 3]) for j in range(a)]
+                known[c] = tuple(elements) if coset else elements[0]
+            proof_stream.push(known[c])
+            proof_stream.push(g_tree.open(c))
+        if coset:
+            fri.prove(g, proof_stream, round0_tree=g_tree)
+        else:
+            fri.prove(g, proof_stream, known_leafs=known or None, round0_tree=g_tree)
+        return values
+
+    # ---------------------------------------------------------------------------------------------------------- verifier (host only)
+    def verify(self, root, points, values, proof_stream):
+        """does the proof in `proof_stream` (read position right behind the commitment's root) show that the polynomials behind `root`
+        take `values` (what `open` returned: a list per point of a list per polynomial in row order) at `points`?
+        Host code only: Python ints, hashlib and Fri.verify; one printed line per refusal."""
+        from .merkle import leaf_pickle_source
+        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
+            token = leaf_pickle_source.set(proof_stream.pickle_of)
+            try:
+                return self.verify(root, points, values, proof_stream)
+            finally:
+                leaf_pickle_source.reset(token)
+        n, t, fri = self.n, self.fri.num_colinearity_tests, self.fri
+        is_element = lambda e: isinstance(e, ExtensionFieldElement)
+        pts = [_limbs(z) for z in points]
+        if not 1 <= len(pts) <= MAX_POINTS_PER_LAUNCH or any(self.in_domain(z) for z in pts):
+            print("points cannot be opened")
+            return False
+        pushed = proof_stream.pull()
+        if not isinstance(pushed, list) or not all(is_element(z) for z in pushed) or [_limbs(z) for z in pushed] != pts:
+            print("points differ from the caller's")
+            return False
+        claimed = proof_stream.pull()
+        want = [[_limbs(v) for v in per_point] for per_point in values]
+        m = len(want[0]) if want else 0
+        if (not isinstance(claimed, list) or len(claimed) != len(want) or m < 1 or any(len(w) != m for w in want)
+                or not all(isinstance(c, list) and len(c) == m and all(is_element(v) for v in c) for c in claimed)
+                or [[_limbs(v) for v in c] for c in claimed] != want):
+            print("values differ from the caller's")
+            return False
+        lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
+        g_root = proof_stream.pull()
+        if not isinstance(g_root, (bytes, bytearray)):
+            print("quotient root is not a digest")
+            return False
+        indices = self._indices(t, proof_stream.verifier_fiat_shamir(), n)
+        coset = fri.coset_leaves
+        a = fri.folding_factor if coset else 1
+        q = n // a
+        # a row has its extension columns first; how many there are is read off the first row and must hold for every row
+        powers = [(1, 0, 0)]
+        for _ in range(len(pts) * m):
+            powers.append(xmul(powers[-1], lam))
+        shape = None
+        for i in indices:
+            row = proof_stream.pull()
+            if not isinstance(row, tuple) or len(row) != m or not all(is_element(e) or isinstance(e, BaseFieldElement) for e in row):
+                print("opened row is not well formed")
+                return False
+            kinds = [is_element(e) for e in row]
+            if kinds != sorted(kinds, reverse=True) or (shape is not None and kinds != shape):
+                print("opened row is not well formed")
+                return False
+            shape = kinds
+            path = proof_stream.pull()
+            if not self._is_path(path, n) or not Merkle.verify(root, i, path, row):
+                print("merkle authentication path verification fails for an opened row")
+                return False
+            leaf = proof_stream.pull()
+            path = proof_stream.pull()
+            c = i % q
+            if coset:
+                well_formed = isinstance(leaf, tuple) and len(leaf) == a and all(is_element(e) for e in leaf)
+            else:
+                well_formed = is_element(leaf)
+            if not well_formed or not self._is_path(path, q) or not Merkle.verify(g_root, c, path, leaf):
+                print("merkle authentication path verification fails for the quotient")
+                return False
+            opened = _limbs(leaf[i // q] if coset else leaf)
+            if opened != self._quotient_at(i, [_limbs(e) for e in row], pts, want, powers, m):
+                print("quotient does not match the opened row")
+                return False
+        if not fri.verify(proof_stream, g_root):
+            print("low-degree test of the quotient fails")
+            return False
+        return True
+
+    @staticmethod
+    def _is_path(path, leaves):
+        return (isinstance(path, list) and len(path) == leaves.bit_length() - 1
+                and all(isinstance(node, (bytes, bytearray)) for node in path))
+
+    def _quotient_at(self, i, row, pts, values, powers, m):
+        """g[i] from the row at x_i: sum_j (lambda^(j m) S - Y_j) / (x_i - z_j).  values[j][p]: y_{p,j}"""
+        x = self.offset * pow(self.omega, i, P) % P
+        s = (0, 0, 0)
+        for p in range(m):
+            s = xadd(s, xmul(powers[p], row[p]))
+        g = (0, 0, 0)
+        for j, z in enumerate(pts):
+            y = (0, 0, 0)
+            for p in range(m):
+                y = xadd(y, xmul(powers[j * m + p], values[j][p]))
+            g = xadd(g, xmul(xsub(xmul(powers[j * m], s), y), xinv(xsub((x, 0, 0), z))))
+        return g

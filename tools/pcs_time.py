@@ -1,0 +1,142 @@
+"""Times the opening of committed polynomials at out-of-domain points (stark_brainfuck_amd/pcs.py, csrc/deep.hip) at N = 2^22,
+expansion 4, 16 base + 4 extension polynomials of 2^20 coefficients, k = 2 points: HIP events around each call after one warm-up call
+of the same shape, the median of --reps calls per line (ms):
+
+    evaluation      bfs_poly_eval_points over the 28 coefficient columns (one call, batch 28), and as `open` makes it (one call per polynomial, one read-back)
+    quotient        bfs_deep_quotient over the 20 codewords
+    open            PolynomialCommitment.open as a whole (host clock, ends in the stream synchronise of Fri.prove's read-backs)
+    combination     bfs_combination over the same 20 codewords as sources (what the quotient is compared with)
+    extension       bfs_gl_ntt of the same 28 columns from 2^20 coefficients to the 2^22 coset (what the evaluation is compared with)
+
+and the shader clock sampled under a loop of quotient launches.  The numbers of profiles/pcs.md come from one run of this.
+
+    python tools/pcs_time.py [--reps 7] [--log-n 22]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+import stark_brainfuck_amd as sb
+from stark_brainfuck_amd import _lib, pcs
+from stark_brainfuck_amd.arrays import raw_ntt
+from stark_brainfuck_amd.device import DeviceBuffer, current_stream, synchronize
+
+EXPANSION, N_BASE, N_EXT, K, T = 4, 16, 4, 2, 8
+u64 = ctypes.c_uint64
+
+
+def timed(fn, reps):
+    fn()                                                      # warm-up: tables, pool blocks
+    synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return round(statistics.median(ms), 4), round(min(ms), 4), round(max(ms), 4)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--log-n", type=int, default=22)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    lib = _lib.load()
+    N = 1 << args.log_n
+    d = N // EXPANSION
+    XF = sb.ExtensionField.main()
+    BF = XF.modulus.coefficients[0].field
+    P = BF.p
+    fri = sb.Fri(BF.generator(), BF.primitive_nth_root(N), N, EXPANSION, T, XF)
+    pc = sb.PolynomialCommitment(fri)
+    rng = np.random.default_rng(1)
+    columns = 3 * N_EXT + N_BASE
+    coeffs = DeviceBuffer.from_numpy(rng.integers(0, P, size=columns * d, dtype=np.uint64))
+    polys = [sb.XArray(_view(coeffs, 3 * e * d, 3 * d), d, XF) for e in range(N_EXT)]
+    polys += [sb.BaseArray(_view(coeffs, (3 * N_EXT + b) * d, d), d) for b in range(N_BASE)]
+    points = [XF.from_limbs([int(v) for v in rng.integers(1, P, size=3, dtype=np.uint64)]) for _ in range(K)]
+    pts = [tuple(z.limbs()) for z in points]
+    flat = (u64 * (3 * K))(*[v for z in pts for v in z])
+    out = DeviceBuffer(3 * columns * K)
+    stream = current_stream()
+    report = {"log_n": args.log_n, "coefficients": d, "base_polynomials": N_BASE, "extension_polynomials": N_EXT, "points": K, "reps": args.reps}
+
+    report["evaluation_one_call_ms"] = timed(lambda: _lib.check(lib.bfs_poly_eval_points(coeffs.ptr, d, d, columns, flat, K, out.ptr, stream)), args.reps)
+    report["evaluation_as_open_ms"] = timed(lambda: pcs._eval_jobs([(f.ptr, f.n, getattr(f, "stride", f.n), 3 if isinstance(f, sb.XArray) else 1) for f in polys], pts),
+                                            args.reps)
+    codewords = DeviceBuffer(columns * N)
+    report["extension_ms"] = timed(lambda: raw_ntt(coeffs.ptr, d, d, codewords.ptr, N, args.log_n, columns, pc.omega, pc.offset, 1, stream), args.reps)
+
+    ps = sb.ProofStream()
+    t0 = time.perf_counter()
+    committed = pc.commit(polys, ps)
+    synchronize()
+    report["commit_wall_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+    values = [[(1 + j, 2 + p, 3) for p in range(N_BASE + N_EXT)] for j in range(K)]      # (the kernel's time does not depend on the claims)
+    lam = (5, 6, 7)
+    report["quotient_ms"] = timed(lambda: pc.quotient(committed, pts, values, lam), args.reps)
+
+    sources = (_lib.CombSource * (N_BASE + N_EXT))()
+    for c in range(N_BASE + N_EXT):
+        s = sources[c]
+        s.ptr, s.is_ext, s.pad, s.shift = committed.column_ptr(c), int(c < N_EXT), 0, 0
+        for l in range(3):
+            s.wa[l], s.wb[l] = 11 + c + l, 0
+    randomizer = sb.XArray.empty(N, XF)
+    lib.bfs_memset(randomizer.ptr, 0, 24 * N, stream)
+    comb = sb.XArray.empty(N, XF)
+    report["combination_ms"] = timed(lambda: _lib.check(lib.bfs_combination(sources, N_BASE + N_EXT, randomizer.ptr, (u64 * 3)(1, 0, 0), comb.ptr, args.log_n,
+                                                                          pc.offset, pc.omega, stream)), args.reps)
+
+    def whole_open():
+        stream_ = sb.ProofStream()
+        stream_.push(committed.root())
+        pc.open(committed, points, stream_)
+        synchronize()
+    whole_open()
+    wall = []
+    for _ in range(args.reps):
+        t = time.perf_counter()
+        whole_open()
+        wall.append(1e3 * (time.perf_counter() - t))
+    report["open_wall_ms"] = (round(statistics.median(wall), 3), round(min(wall), 3), round(max(wall), 3))
+
+    # the shader clock half a second into a loop of quotient launches
+    import bench
+    stop = []
+
+    def load():
+        while not stop:
+            for _ in range(20):
+                pc.quotient(committed, pts, values, lam)
+            synchronize()
+    worker = threading.Thread(target=load)
+    worker.start()
+    report["clock_under_quotient_load"] = bench.sample_clock_under_load(0, delay_s=0.5)
+    stop.append(1)
+    worker.join()
+    report["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(report), flush=True)
+
+
+def _view(buf, offset, count):
+    from stark_brainfuck_amd.device import DeviceView
+    return DeviceView(buf, offset, count)
+
+
+if __name__ == "__main__":
+    main()

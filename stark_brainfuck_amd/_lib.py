@@ -177,6 +177,13 @@ _EXT_SIGNATURES = {
     "bfs_deep_quotient": (ci, [vp, u32, u64, u32, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), u32, ctypes.POINTER(u64), vp, u64, vp]),
 }
 
+# include/bfstark_open.h: opening plans (prefix bfsx_; the header says why); bound together with the two tables above
+_OPEN_SIGNATURES = {
+    "bfsx_poly_eval_columns": (ci, [vp, u32, ctypes.POINTER(u64), u32, vp, vp]),
+    "bfsx_deep_quotient_groups": (ci, [vp, u32, u64, u32, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), u32, ctypes.POINTER(u64), u32,
+                                       ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, u64, vp]),
+}
+
 
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
@@ -191,6 +198,11 @@ class AirViolation(ctypes.Structure):
 class RowColumn(ctypes.Structure):
     """bfs_row_column (include/bfstark.h)"""
     _fields_ = [("d_values", vp), ("is_ext", ctypes.c_int32), ("field_id", ctypes.c_int32)]
+
+
+class EvalColumn(ctypes.Structure):
+    """bfsx_eval_column (include/bfstark_open.h)"""
+    _fields_ = [("d_coeffs", vp), ("n_coeffs", u64)]
 
 
 class TracePadTable(ctypes.Structure):
@@ -256,6 +268,11 @@ def ext_exported_symbols():
     return sorted(_EXT_SIGNATURES)
 
 
+def open_exported_symbols():
+    """names include/bfstark_open.h declares"""
+    return sorted(_OPEN_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -272,7 +289,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

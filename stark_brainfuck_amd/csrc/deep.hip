@@ -1,9 +1,12 @@
 // deep.hip -- opening committed polynomials at points outside the FRI domain (include/bfstark_ext.h): the values f_b(z_j) of
 // coefficient columns in HBM at up to four points of F_p^3, and the DEEP quotient codeword that ties the values to the committed
 // codewords.  The per-thread arithmetic, with the cost argument, is deep_core.hpp; DESIGN.md "Opening at out-of-domain points".
-// Neither entry synchronises, copies from the host or allocates outside the stream-ordered pool: the points, weights and constants
-// of a call travel as kernel arguments.
+// include/bfstark_open.h adds the same two for opening plans: separate columns of their own lengths evaluated in one call, and the
+// quotient of groups of columns that are opened at different points, in one launch.
+// No entry synchronises, copies from the host or allocates outside the stream-ordered pool: the points, weights, constants, column
+// tables and plans of a call travel as kernel arguments.
 #include "../../include/bfstark_ext.h"
+#include "../../include/bfstark_open.h"
 #include "deep_core.hpp"
 #include "runtime.hpp"
 
@@ -31,36 +34,59 @@ __device__ __forceinline__ Xfe deep_block_sum(const Xfe& mine, u64* red) {
     return Xfe{{red[0], red[DEEP_EVAL_T], red[2 * DEEP_EVAL_T]}};
 }
 
-// launch 1: grid (blocks, batch); partial[((b * K + j) * blocks + block) * 3 ..] = the workgroup's share of f_b(z_j) without its z_j^(B block)
+// a workgroup's share of one column: out[3 j ..] = its part of f(z_j) without its z_j^(B block)
 template <int K>
-__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_partial_kernel(const u64* coeffs, u64 n, u64 in_stride, const u64* table, u64* partial) {
+__device__ __forceinline__ void deep_eval_partial_block(const u64* col, u64 n, u32 block, const u64* table, u64* out, u32 out_step) {
     __shared__ u64 steps[K * DEEP_EVAL_S * 3];
     __shared__ u64 red[3 * DEEP_EVAL_T];
     const u32 t = threadIdx.x;
     for (u32 w = t; w < (u32)K * DEEP_EVAL_S * 3; w += DEEP_EVAL_T) steps[w] = table[DEEP_EVAL_STEPS_AT + w];
     __syncthreads();
     Xfe mine[K];
-    deep_eval_thread<K>(coeffs + (u64)blockIdx.y * in_stride, n, blockIdx.x, t, steps, table, mine);
+    deep_eval_thread<K>(col, n, block, t, steps, table, mine);
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const Xfe total = deep_block_sum(mine[j], red);
-        if (t == 0) {
-            u64* out = partial + (((u64)blockIdx.y * K + j) * gridDim.x + blockIdx.x) * 3;
-            out[0] = total.c[0]; out[1] = total.c[1]; out[2] = total.c[2];
-        }
+        if (t == 0) { out[(size_t)j * out_step] = total.c[0]; out[(size_t)j * out_step + 1] = total.c[1]; out[(size_t)j * out_step + 2] = total.c[2]; }
     }
 }
 
-// launch 2: block (b * k + j) adds the `blocks` partial sums of f_b(z_j), each scaled by (z_j^B)^block
-__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_combine_kernel(const u64* partial, u32 blocks, u32 k, const u64* table, u64* out) {
+// `blocks` partial sums at `partial`, each scaled by (z_j^B)^block, added into out[0..3)
+__device__ __forceinline__ void deep_eval_combine_block(const u64* partial, u32 blocks, u32 j, const u64* table, u64* out) {
     __shared__ u64 red[3 * DEEP_EVAL_T];
-    const u32 t = threadIdx.x, j = blockIdx.x % k;
+    const u32 t = threadIdx.x;
     const Xfe zb = deep_eval_block_power(table, j);
     Xfe acc{{0, 0, 0}};
-    for (u32 p = t; p < blocks; p += DEEP_EVAL_T)
-        acc = xfe_add(acc, xfe_mul(xfe_load3(partial + ((u64)blockIdx.x * blocks + p) * 3), xfe_pow_small(zb, p)));
+    for (u32 p = t; p < blocks; p += DEEP_EVAL_T) acc = xfe_add(acc, xfe_mul(xfe_load3(partial + (u64)p * 3), xfe_pow_small(zb, p)));
     const Xfe total = deep_block_sum(acc, red);
-    if (t == 0) { out[(u64)blockIdx.x * 3] = total.c[0]; out[(u64)blockIdx.x * 3 + 1] = total.c[1]; out[(u64)blockIdx.x * 3 + 2] = total.c[2]; }
+    if (t == 0) { out[0] = total.c[0]; out[1] = total.c[1]; out[2] = total.c[2]; }
+}
+
+// launch 1: grid (blocks, batch); partial[((b * K + j) * blocks + block) * 3 ..] = the workgroup's share of f_b(z_j)
+template <int K>
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_partial_kernel(const u64* coeffs, u64 n, u64 in_stride, const u64* table, u64* partial) {
+    deep_eval_partial_block<K>(coeffs + (u64)blockIdx.y * in_stride, n, blockIdx.x, table,
+                               partial + deep_eval_partial_at(blockIdx.y, K, 0, gridDim.x, blockIdx.x), gridDim.x * 3);
+}
+
+// launch 2: block (b * k + j) adds the `blocks` partial sums of f_b(z_j)
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_combine_kernel(const u64* partial, u32 blocks, u32 k, const u64* table, u64* out) {
+    deep_eval_combine_block(partial + (u64)blockIdx.x * blocks * 3, blocks, blockIdx.x % k, table, out + (u64)blockIdx.x * 3);
+}
+
+// the same two launches over separate columns (deep_core.hpp): grid (blocks of the longest column, columns); a workgroup past the
+// end of its column leaves as a whole, and the slots it would have filled are never read
+template <int K>
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_columns_partial_kernel(DeepEvalColumns cols, const u64* table, u64* partial) {
+    const u32 b = blockIdx.y, n = cols.n[b];
+    if (blockIdx.x >= deep_eval_blocks(n)) return;
+    deep_eval_partial_block<K>(cols.col[b], n, blockIdx.x, table, partial + deep_eval_partial_at(b, K, 0, gridDim.x, blockIdx.x), gridDim.x * 3);
+}
+
+__global__ void __launch_bounds__(DEEP_EVAL_T) deep_eval_columns_combine_kernel(DeepEvalColumns cols, const u64* partial, u32 row_blocks, u32 k,
+                                                                                const u64* table, u64* out) {
+    const u32 b = blockIdx.x / k, j = blockIdx.x % k;
+    deep_eval_combine_block(partial + deep_eval_partial_at(b, k, j, row_blocks, 0), deep_eval_blocks(cols.n[b]), j, table, out + (u64)blockIdx.x * 3);
 }
 
 template <int K>
@@ -77,6 +103,25 @@ __global__ void __launch_bounds__(DEEP_Q_T) deep_quotient_kernel(DeepQuotientArg
     }
 }
 
+// one launch for a whole opening plan (deep_core.hpp): NP distinct points, E = deep_groups_e(NP) points of the domain per thread
+static_assert(sizeof(DeepGroupsArgs) + 2 * sizeof(u64) <= 4096, "the plan must fit the kernel-argument block");
+static_assert(sizeof(DeepEvalColumns) + 4 * sizeof(u64) <= 4096, "the column table must fit the kernel-argument block");
+
+template <int NP>
+__global__ void __launch_bounds__(DEEP_G_T) deep_groups_kernel(DeepGroupsArgs a, u64* out, u64 out_stride) {
+    constexpr int E = (int)deep_groups_e(NP);
+    const u64 first = (u64)blockIdx.x * (DEEP_G_T * E) + threadIdx.x;
+    u64 idx[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) idx[e] = first + (u64)e * DEEP_G_T;
+    Xfe g[E];
+    deep_groups_thread<NP, E>(a, idx, g);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (idx[e] < a.n) { out[idx[e]] = g[e].c[0]; out[out_stride + idx[e]] = g[e].c[1]; out[2 * out_stride + idx[e]] = g[e].c[2]; }
+    }
+}
+
 template <class Fn>
 static int with_point_count(u32 k, Fn&& fn) {
     switch (k) {
@@ -85,6 +130,17 @@ static int with_point_count(u32 k, Fn&& fn) {
     case 3: return fn(std::integral_constant<int, 3>());
     case 4: return fn(std::integral_constant<int, 4>());
     default: set_error("the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG;
+    }
+}
+
+template <class Fn>
+static int with_distinct_points(u32 n_points, Fn&& fn) {
+    switch (n_points) {
+    case 5: return fn(std::integral_constant<int, 5>());
+    case 6: return fn(std::integral_constant<int, 6>());
+    case 7: return fn(std::integral_constant<int, 7>());
+    case 8: return fn(std::integral_constant<int, 8>());
+    default: return with_point_count(n_points, fn);
     }
 }
 
@@ -176,6 +232,125 @@ extern "C" int bfs_deep_quotient(const bfs_row_column* h_columns, uint32_t m, ui
     const u32 grid = (u32)((n + DEEP_Q_T * DEEP_Q_E - 1) / (DEEP_Q_T * DEEP_Q_E));
     BFS_TRY(with_point_count(k, [&](auto kk) -> int {
         hipLaunchKernelGGL((deep_quotient_kernel<decltype(kk)::value>), dim3(grid), dim3(DEEP_Q_T), 0, stream, a, d_out, out_stride);
+        return BFS_OK;
+    }));
+    BFS_HIP(hipGetLastError());
+    return BFS_OK;
+}
+
+extern "C" int bfsx_poly_eval_columns(const bfsx_eval_column* h_columns, uint32_t count, const uint64_t* h_points, uint32_t k, uint64_t* d_out,
+                                      void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!h_columns || !h_points || !d_out) { set_error("bfsx_poly_eval_columns: null argument"); return BFS_ERR_BAD_ARG; }
+    if (count < 1 || count > DEEP_EVAL_MAX_COLUMNS) { set_error("bfsx_poly_eval_columns: 1..%u columns (got %u)", DEEP_EVAL_MAX_COLUMNS, count); return BFS_ERR_BAD_ARG; }
+    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfsx_poly_eval_columns: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
+    DeepPoints pts{};
+    for (u32 j = 0; j < k; ++j) {
+        if (!canonical3(h_points + 3 * j)) { set_error("bfsx_poly_eval_columns: point %u is not reduced", j); return BFS_ERR_BAD_ARG; }
+        pts.z[j] = Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}};
+    }
+    const u64 results = (u64)count * k;
+    DeepEvalColumns cols{};
+    u32 row_blocks = 0;
+    for (u32 b = 0; b < count; ++b) {
+        const bfsx_eval_column& c = h_columns[b];
+        if (!c.d_coeffs) { set_error("bfsx_poly_eval_columns: column %u is null", b); return BFS_ERR_BAD_ARG; }
+        if (c.n_coeffs < 1 || c.n_coeffs > (1ull << 24)) { set_error("bfsx_poly_eval_columns: column %u: n_coeffs must be 1..2^24 (got %llu)", b, (unsigned long long)c.n_coeffs); return BFS_ERR_BAD_ARG; }
+        if (overlaps(d_out, results * 24, c.d_coeffs, c.n_coeffs * 8)) { set_error("bfsx_poly_eval_columns: d_out overlaps column %u", b); return BFS_ERR_BAD_ARG; }
+        cols.col[b] = c.d_coeffs;
+        cols.n[b] = (u32)c.n_coeffs;
+        if (deep_eval_blocks(c.n_coeffs) > row_blocks) row_blocks = deep_eval_blocks(c.n_coeffs);
+    }
+    void* scratch = nullptr;
+    BFS_TRY(device_alloc((DEEP_EVAL_TABLE_WORDS + results * row_blocks * 3) * sizeof(u64), stream, &scratch));
+    u64* table = (u64*)scratch;
+    u64* partial = table + DEEP_EVAL_TABLE_WORDS;
+    hipLaunchKernelGGL(deep_eval_table_kernel, dim3(k), dim3(DEEP_EVAL_T), 0, stream, pts, table);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        (void)with_point_count(k, [&](auto kk) -> int {
+            hipLaunchKernelGGL((deep_eval_columns_partial_kernel<decltype(kk)::value>), dim3(row_blocks, count), dim3(DEEP_EVAL_T), 0, stream, cols,
+                               (const u64*)table, partial);
+            return BFS_OK;
+        });
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(deep_eval_columns_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, cols, (const u64*)partial, row_blocks, k,
+                           (const u64*)table, d_out);
+        e = hipGetLastError();
+    }
+    (void)device_release(scratch, stream);                // stream-ordered: the launches above are ahead of whoever gets the block next
+    if (e != hipSuccess) { set_error("bfsx_poly_eval_columns: %s", hipGetErrorString(e)); return BFS_ERR_HIP; }
+    return BFS_OK;
+}
+
+extern "C" int bfsx_deep_quotient_groups(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
+                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
+                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
+                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!h_columns || !h_group_columns || !h_group_pairs || !h_points || !h_pair_point || !h_pair_values || !h_lambda || !d_out) {
+        set_error("bfsx_deep_quotient_groups: null argument"); return BFS_ERR_BAD_ARG;
+    }
+    if (m < 1 || m > DEEP_MAX_COLUMNS) { set_error("bfsx_deep_quotient_groups: 1..%u codewords (got %u)", DEEP_MAX_COLUMNS, m); return BFS_ERR_BAD_ARG; }
+    if (n_groups < 1 || n_groups > DEEP_G_GROUPS) { set_error("bfsx_deep_quotient_groups: 1..%u groups (got %u)", DEEP_G_GROUPS, n_groups); return BFS_ERR_BAD_ARG; }
+    if (n_points < 1 || n_points > DEEP_G_POINTS) { set_error("bfsx_deep_quotient_groups: 1..%u distinct points (got %u)", DEEP_G_POINTS, n_points); return BFS_ERR_BAD_ARG; }
+    if (log_n < 1 || log_n > 24) { set_error("bfsx_deep_quotient_groups: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
+    const u64 n = 1ull << log_n;
+    if (limb_stride < n || out_stride < n) { set_error("bfsx_deep_quotient_groups: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
+    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfsx_deep_quotient_groups: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
+    if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
+    if (!canonical3(h_lambda)) { set_error("bfsx_deep_quotient_groups: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
+    u32 columns = 0, pairs = 0;
+    for (u32 g = 0; g < n_groups; ++g) {
+        if (h_group_columns[g] < 1 || h_group_columns[g] > m - columns) { set_error("bfsx_deep_quotient_groups: group %u: an empty group, or more columns than there are", g); return BFS_ERR_BAD_ARG; }
+        if (h_group_pairs[g] < 1 || h_group_pairs[g] > DEEP_MAX_POINTS) { set_error("bfsx_deep_quotient_groups: group %u: 1..%u points (got %u)", g, DEEP_MAX_POINTS, h_group_pairs[g]); return BFS_ERR_BAD_ARG; }
+        columns += h_group_columns[g];
+        pairs += h_group_pairs[g];
+    }
+    if (columns != m) { set_error("bfsx_deep_quotient_groups: the groups hold %u columns, not %u", columns, m); return BFS_ERR_BAD_ARG; }
+    if (pairs > DEEP_G_PAIRS) { set_error("bfsx_deep_quotient_groups: at most %u (group, point) pairs (got %u)", DEEP_G_PAIRS, pairs); return BFS_ERR_BAD_ARG; }
+    DeepGroupsArgs a{};
+    a.n_groups = n_groups; a.limb_stride = limb_stride; a.n = n; a.offset = offset;
+    for (u32 p = 0; p < n_points; ++p) {
+        if (!canonical3(h_points + 3 * p)) { set_error("bfsx_deep_quotient_groups: point %u is not reduced", p); return BFS_ERR_BAD_ARG; }
+        deep_group_point(a.pt[p], xfe_load3(h_points + 3 * p));
+    }
+    const Xfe lambda = xfe_load3(h_lambda);
+    const u64 out_bytes = (2 * out_stride + n) * 8;
+    u32 c = 0, q = 0;
+    Xfe scale{{1, 0, 0}};                                 // lambda^base of the next pair
+    for (u32 g = 0; g < n_groups; ++g) {
+        Xfe power{{1, 0, 0}};                             // lambda^r
+        for (u32 r = 0; r < h_group_columns[g]; ++r, ++c) {
+            const bfs_row_column& col = h_columns[c];
+            if (!col.d_values) { set_error("bfsx_deep_quotient_groups: codeword %u is null", c); return BFS_ERR_BAD_ARG; }
+            if (overlaps(d_out, out_bytes, col.d_values, (col.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfsx_deep_quotient_groups: d_out overlaps codeword %u", c); return BFS_ERR_BAD_ARG; }
+            a.col[c] = col.d_values;
+            if (col.is_ext) a.ext_mask |= 1u << c;
+            lazy_weight_matrix(power, a.weight[c]);
+            power = xfe_mul(power, lambda);
+        }
+        u32 seen = 0;
+        for (u32 j = 0; j < h_group_pairs[g]; ++j, ++q) {
+            const u32 point = h_pair_point[q];
+            if (point >= n_points) { set_error("bfsx_deep_quotient_groups: pair %u names point %u of %u", q, point, n_points); return BFS_ERR_BAD_ARG; }
+            if ((seen >> point) & 1) { set_error("bfsx_deep_quotient_groups: group %u opens point %u twice", g, point); return BFS_ERR_BAD_ARG; }
+            seen |= 1u << point;
+            if (!canonical3(h_pair_values + 3 * q)) { set_error("bfsx_deep_quotient_groups: value %u is not reduced", q); return BFS_ERR_BAD_ARG; }
+            DeepGroupPair& pr = a.pair[q];
+            pr.scale = scale; pr.y = xfe_load3(h_pair_values + 3 * q); pr.point = point;
+            pr.unit = scale.c[0] == 1 && scale.c[1] == 0 && scale.c[2] == 0;
+            scale = xfe_mul(scale, power);                // power = lambda^|columns_g| here
+        }
+        a.col_end[g] = c; a.pair_end[g] = q;
+    }
+    BFS_TRY(ntt_power_tables(omega, log_n, &a.w_lo, &a.w_hi, &a.lo_bits));
+    const u64 share = (u64)DEEP_G_T * deep_groups_e(n_points);
+    const u32 grid = (u32)((n + share - 1) / share);
+    BFS_TRY(with_distinct_points(n_points, [&](auto np) -> int {
+        hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
         return BFS_OK;
     }));
     BFS_HIP(hipGetLastError());

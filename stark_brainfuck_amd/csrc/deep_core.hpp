@@ -16,6 +16,9 @@
 // lambda^p wave-uniform), whatever k is.  1 / (x - z) for x in F_p is adj / norm with the cofactors and the norm of the matrix of
 // multiplication by (x - z0) - z1 X - z2 X^2 (pointwise.hip: xfe_cofactors_kernel); z1 and z2 do not depend on the point of the domain,
 // so their products are constants of the launch.  The E * k norms of a thread share ONE base-field inversion (Montgomery's trick).
+//
+// The two entries of include/bfstark_open.h reuse both: evaluation of separate columns of different lengths in one launch, and the
+// quotient of an opening plan (groups of columns, each with its own points); their parts of this file say what is new.
 #pragma once
 #include <stddef.h>
 
@@ -87,8 +90,22 @@ BFS_HD Xfe deep_eval_block_power(const u64* table, u32 j) {
     return xfe_mul(xfe_load3(st + (DEEP_EVAL_S - 1) * 3), xfe_load3(st + 3));
 }
 
+// ---- evaluation of separate columns in one call (include/bfstark_open.h: bfsx_poly_eval_columns) ----
+// The same launches over a grid (blocks of the LONGEST column, columns): pointers and lengths are kernel arguments, a workgroup past
+// the end of its own column leaves, and the combining launch adds only the deep_eval_blocks(n_b) partial sums that column b has.
+constexpr u32 DEEP_EVAL_MAX_COLUMNS = 96;
+
+struct DeepEvalColumns {
+    const u64* col[DEEP_EVAL_MAX_COLUMNS];
+    u32 n[DEEP_EVAL_MAX_COLUMNS];                          // 1 .. 2^24 coefficients
+};
+
+BFS_HD u32 deep_eval_blocks(u64 n) { return (u32)((n + DEEP_EVAL_BLOCK - 1) / DEEP_EVAL_BLOCK); }
+// word at which workgroup `block` of column b leaves its sum for point j of k; row_blocks: the blocks of the longest column
+BFS_HD size_t deep_eval_partial_at(u32 b, u32 k, u32 j, u32 row_blocks, u32 block) { return (((size_t)b * k + j) * row_blocks + block) * 3; }
+
 // ---- the quotient ----
-constexpr u32 DEEP_Q_T = 256;       // threads of a workgroup
+constexpr u32 DEEP_Q_T = 256;      // threads of a workgroup
 constexpr u32 DEEP_Q_E = 2;         // points of a thread, DEEP_Q_T apart
 
 struct DeepPointConsts {            // of one z = (z0, z1, z2), with a1 = -z1, a2 = -z2, d = a1 - a2
@@ -120,13 +137,14 @@ inline void deep_point_consts(DeepPointConsts& c, const Xfe& z, const Xfe& scale
     c.y = y;
 }
 
-// S_i: the weighted sum of the m codewords at point i
-BFS_HD Xfe deep_row_sum(const DeepQuotientArgs& a, u64 i) {
+// the weighted sum of the codewords first .. last - 1 at point i (A: DeepQuotientArgs or DeepGroupsArgs)
+template <class A>
+BFS_HD Xfe deep_range_sum(const A& a, u32 first, u32 last, u64 i) {
     LazyX L = lazyx_zero();
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma nounroll
 #endif
-    for (u32 p = 0; p < a.m; ++p) {
+    for (u32 p = first; p < last; ++p) {
         const u64* w = a.weight[p];
         const u64* src = a.col[p];
         if ((a.ext_mask >> p) & 1) {
@@ -140,6 +158,21 @@ BFS_HD Xfe deep_row_sum(const DeepQuotientArgs& a, u64 i) {
         }
     }
     return lazyx_reduce(L);
+}
+
+// S_i: the weighted sum of the m codewords at point i
+BFS_HD Xfe deep_row_sum(const DeepQuotientArgs& a, u64 i) { return deep_range_sum(a, 0, a.m, i); }
+
+// cofactors and norm of the matrix of multiplication by x - z (x in F_p): 1 / (x - z) = cof / norm
+BFS_HD u64 deep_cofactors(const u64 x, u64 z0, u64 a1, u64 a2, u64 d_a1, u64 d_a2, u64 a1_sq, Xfe& cof) {
+    const u64 a0 = gl_sub(x, z0);
+    const u64 s = gl_add(a0, a2);
+    const u64 c0 = gl_sub(gl_mul(s, s), d_a1);                       // (a0+a2)^2 - (a1-a2) a1
+    const u64 c1 = gl_sub(d_a2, gl_mul(a1, s));                      // (a1-a2) a2 - a1 (a0+a2)
+    const u64 c2 = gl_sub(a1_sq, gl_mul(s, a2));                     // a1^2 - (a0+a2) a2
+    const u64 nm = gl_sub(gl_mul(a0, c0), gl_add(gl_mul(a2, c1), gl_mul(a1, c2)));
+    cof = Xfe{{c0, c1, c2}};
+    return nm == 0 ? 1 : nm;      // x = z: the caller has refused such points; the thread's other inverses stay right
 }
 
 // the E points idx[e] of one thread (idx[e] >= n: none); K points z_j
@@ -157,14 +190,7 @@ BFS_HD void deep_quotient_thread(const DeepQuotientArgs& a, const u64 idx[DEEP_Q
         BFS_UNROLL
         for (int j = 0; j < K; ++j) {
             const DeepPointConsts& c = a.pt[j];
-            const u64 a0 = gl_sub(x, c.z0);
-            const u64 s = gl_add(a0, c.a2);
-            const u64 c0 = gl_sub(gl_mul(s, s), c.d_a1);                       // (a0+a2)^2 - (a1-a2) a1
-            const u64 c1 = gl_sub(c.d_a2, gl_mul(c.a1, s));                    // (a1-a2) a2 - a1 (a0+a2)
-            const u64 c2 = gl_sub(c.a1_sq, gl_mul(s, c.a2));                   // a1^2 - (a0+a2) a2
-            u64 nm = gl_sub(gl_mul(a0, c0), gl_add(gl_mul(c.a2, c1), gl_mul(c.a1, c2)));
-            if (nm == 0) nm = 1;          // x = z: the caller has refused such points; the thread's other inverses stay right
-            cof[e][j] = Xfe{{c0, c1, c2}};
+            const u64 nm = deep_cofactors(x, c.z0, c.a1, c.a2, c.d_a1, c.d_a2, c.a1_sq, cof[e][j]);
             norm[e][j] = nm;
             before[e][j] = run;
             run = gl_mul(run, nm);
@@ -184,6 +210,114 @@ BFS_HD void deep_quotient_thread(const DeepQuotientArgs& a, const u64 idx[DEEP_Q
         }
         out[e] = lazyx_reduce(G);
     }
+}
+
+// ---- the quotient of an opening plan (include/bfstark_open.h: bfsx_deep_quotient_groups) ----
+// The columns lie in group order; group g owns the columns col_end[g-1] .. col_end[g] - 1 and the pairs pair_end[g-1] .. pair_end[g] - 1,
+// a pair being (lambda^base, Y, index of its point among the distinct points).  A thread first takes 1 / (x - z) for every DISTINCT
+// point (one shared inversion, as above), then goes group by group: S_g, and per pair of the group (scale * S_g - Y) / (x - z).
+// Nothing is indexed by a run-time value in registers: the pair's point is picked by a chain of wave-uniform selects.
+constexpr u32 DEEP_G_GROUPS = 8;
+constexpr u32 DEEP_G_POINTS = 8;    // distinct points of a plan
+constexpr u32 DEEP_G_PAIRS = 16;    // (group, point) pairs of a plan
+constexpr u32 DEEP_G_T = 256;       // threads of a workgroup
+// points of the domain per thread, DEEP_G_T apart: the (cofactors, norm, running product) sets a thread holds are E * distinct points
+constexpr u32 deep_groups_e(u32 n_points) { return n_points <= DEEP_MAX_POINTS ? 2 : 1; }
+
+struct DeepGroupPoint {             // DeepPointConsts without the pair's part
+    u64 z0, a1, a2, d_a1, d_a2, a1_sq;
+};
+
+struct DeepGroupPair {
+    Xfe scale;                      // lambda^base[g][j]
+    Xfe y;                          // Y_{g,j}
+    u32 point;                      // < n_points
+    u32 unit;                       // scale = 1: no product
+};
+
+struct DeepGroupsArgs {
+    const u64* col[DEEP_MAX_COLUMNS];
+    u64 weight[DEEP_MAX_COLUMNS][LAZY_W_EXT];      // lambda^r, r = the column's place in its group
+    DeepGroupPoint pt[DEEP_G_POINTS];
+    DeepGroupPair pair[DEEP_G_PAIRS];
+    u32 col_end[DEEP_G_GROUPS], pair_end[DEEP_G_GROUPS];
+    u32 n_groups, ext_mask;
+    u64 limb_stride, n, offset;
+    const u64* w_lo;
+    const u64* w_hi;
+    u32 lo_bits;
+};
+
+inline void deep_group_point(DeepGroupPoint& c, const Xfe& z) {
+    DeepPointConsts full;
+    deep_point_consts(full, z, Xfe{{1, 0, 0}}, Xfe{{0, 0, 0}});
+    c.z0 = full.z0; c.a1 = full.a1; c.a2 = full.a2; c.d_a1 = full.d_a1; c.d_a2 = full.d_a2; c.a1_sq = full.a1_sq;
+}
+
+// the E points idx[e] of one thread (idx[e] >= n: none); NP distinct points
+template <int NP, int E>
+BFS_HD void deep_groups_thread(const DeepGroupsArgs& a, const u64 idx[E], Xfe out[E]) {
+    Xfe cof[E][NP];
+    u64 norm[E][NP], before[E][NP], at[E];
+    u64 run = 1;
+    BFS_UNROLL
+    for (int e = 0; e < E; ++e) {
+        at[e] = idx[e] < a.n ? idx[e] : 0;
+        const u64 x = gl_mul(a.offset, gl_mul(a.w_lo[at[e] & ((1ull << a.lo_bits) - 1)], a.w_hi[at[e] >> a.lo_bits]));
+        BFS_UNROLL
+        for (int p = 0; p < NP; ++p) {
+            const DeepGroupPoint& c = a.pt[p];
+            norm[e][p] = deep_cofactors(x, c.z0, c.a1, c.a2, c.d_a1, c.d_a2, c.a1_sq, cof[e][p]);
+            before[e][p] = run;
+            run = gl_mul(run, norm[e][p]);
+        }
+    }
+    u64 inv = gl_inv(run);
+    BFS_UNROLL
+    for (int e = E - 1; e >= 0; --e) {
+        BFS_UNROLL
+        for (int p = NP - 1; p >= 0; --p) {
+            const u64 ninv = gl_mul(inv, before[e][p]);
+            inv = gl_mul(inv, norm[e][p]);
+            norm[e][p] = ninv;                                     // from here on: 1 / norm
+        }
+    }
+    Xfe g[E];
+    BFS_UNROLL
+    for (int e = 0; e < E; ++e) g[e] = Xfe{{0, 0, 0}};
+    u32 c0 = 0, q0 = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+    for (u32 grp = 0; grp < a.n_groups; ++grp) {
+        const u32 c1 = a.col_end[grp], q1 = a.pair_end[grp];
+        Xfe sum[E];
+        BFS_UNROLL
+        for (int e = 0; e < E; ++e) sum[e] = deep_range_sum(a, c0, c1, at[e]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma nounroll
+#endif
+        for (u32 q = q0; q < q1; ++q) {
+            const DeepGroupPair& pr = a.pair[q];
+            BFS_UNROLL
+            for (int e = 0; e < E; ++e) {
+                Xfe c = cof[e][0];
+                u64 ninv = norm[e][0];
+                BFS_UNROLL
+                for (int p = 1; p < NP; ++p) {
+                    const bool here = pr.point == (u32)p;
+                    c.c[0] = here ? cof[e][p].c[0] : c.c[0]; c.c[1] = here ? cof[e][p].c[1] : c.c[1]; c.c[2] = here ? cof[e][p].c[2] : c.c[2];
+                    ninv = here ? norm[e][p] : ninv;
+                }
+                const Xfe num = xfe_sub(pr.unit ? sum[e] : xfe_mul(sum[e], pr.scale), pr.y);
+                const Xfe term = xfe_mul(num, c);
+                g[e] = xfe_add(g[e], Xfe{{gl_mul(term.c[0], ninv), gl_mul(term.c[1], ninv), gl_mul(term.c[2], ninv)}});
+            }
+        }
+        c0 = c1; q0 = q1;
+    }
+    BFS_UNROLL
+    for (int e = 0; e < E; ++e) out[e] = g[e];
 }
 
 }  // namespace bfs

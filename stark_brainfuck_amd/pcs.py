@@ -20,6 +20,19 @@ Proof stream of `open`, after the root that `commit` pushed:
     [t indices = BrainfuckStark.sample_indices(t, fiat_shamir, N)];  per index i: the row tuple at x_i, its authentication path, the
     opening of g (the element g[i] and its path; with coset leaves the tuple of leaf i mod (N / a) and its one path);
     then Fri.prove over g.
+
+Opening each polynomial at its own points (include/bfstark_open.h):
+      .open_at(commitment, plan, proof_stream)        plan: groups (row columns, points), see OpeningPlan; returns values[g][j][r]
+      .verify_at(root, plan, values, proof_stream)    host only
+With base[g][j] a running count over the pairs in plan order, raised by |columns_g| per pair:
+
+    g(x) = sum_g sum_j ( lambda^base[g][j] * S_g(x) - Y_{g,j} ) / (x - z_{g,j}),   S_g = sum_r lambda^r f_{columns_g[r]},
+    Y_{g,j} = sum_r lambda^(base[g][j] + r) y_{g,j,r}
+
+-- for one group of all columns the formula above word for word.  Proof stream of `open_at`, after the root: the DISTINCT points in order
+of first appearance (a list of elements); the plan's shape (a list per group of (tuple(columns), tuple(point indices)), plain ints, so that
+the plan is inside every later Fiat-Shamir hash); the values (a list per group of a list per point of a list per column); from lambda on
+exactly as `open`.
 """
 import ctypes
 from hashlib import blake2b
@@ -38,6 +51,8 @@ from .ntt import _base_value
 _u64 = ctypes.c_uint64
 MAX_POINTS_PER_LAUNCH = 4          # bfs_poly_eval_points, bfs_deep_quotient
 MAX_COLUMNS, MAX_EXT_COLUMNS = 32, 16   # bfs_merkle_build_rows
+MAX_COLUMNS_PER_EVALUATION = 96    # bfsx_poly_eval_columns
+MAX_GROUPS, MAX_PLAN_POINTS, MAX_PAIRS = 8, 8, 16   # bfsx_deep_quotient_groups: an opening plan
 
 
 def _limbs(z):
@@ -56,35 +71,70 @@ def _times_x(a):
     return (-a[2] % P, (a[0] + a[2]) % P, a[1])
 
 
-def _eval_jobs(jobs, points):
-    """jobs: (ptr, n, stride, batch) coefficient arrays -> per job [[limb triple of column b at point j] per column] per point:
-    bfs_poly_eval_points, four points per launch, every launch enqueued before the ONE read-back of all results"""
+def _point_chunks(points):
+    return [points[first:first + MAX_POINTS_PER_LAUNCH] for first in range(0, len(points), MAX_POINTS_PER_LAUNCH)]
+
+
+def _flat_points(points):
+    return (_u64 * (3 * len(points)))(*[v for z in points for v in z])
+
+
+def _eval_requests(requests):
+    """requests: (columns, points), columns a list of (ptr, n) SEPARATE base-coefficient arrays -> per request values[b][j] = limb
+    triple of column b at point j: bfsx_poly_eval_columns, one call per 96 columns and four points, every call enqueued before the ONE
+    read-back of all results"""
     lib, stream = _lib.load(), current_stream()
-    out = DeviceBuffer(3 * len(points) * sum(job[3] for job in jobs))
-    at = 0
-    for ptr, n, stride, batch in jobs:
-        for first in range(0, len(points), MAX_POINTS_PER_LAUNCH):
-            chunk = points[first:first + MAX_POINTS_PER_LAUNCH]
-            flat = (_u64 * (3 * len(chunk)))(*[v for z in chunk for v in z])
-            _lib.check(lib.bfs_poly_eval_points(ptr, n, stride, batch, flat, len(chunk), out.ptr + 8 * at, stream))
-            at += 3 * batch * len(chunk)
+    out = DeviceBuffer(3 * sum(len(columns) * len(points) for columns, points in requests))
+    at, calls = 0, []
+    for r, (columns, points) in enumerate(requests):
+        for first in range(0, len(columns), MAX_COLUMNS_PER_EVALUATION):
+            some = columns[first:first + MAX_COLUMNS_PER_EVALUATION]
+            table = (_lib.EvalColumn * len(some))(*[_lib.EvalColumn(ptr, n) for ptr, n in some])
+            for j0, chunk in enumerate(_point_chunks(points)):
+                _lib.check(lib.bfsx_poly_eval_columns(table, len(some), _flat_points(chunk), len(chunk), out.ptr + 8 * at, stream))
+                calls.append((r, first, len(some), j0 * MAX_POINTS_PER_LAUNCH, len(chunk), at))
+                at += 3 * len(some) * len(chunk)
     words = [int(v) for v in out.to_numpy()]
     out.free()
+    results = [[[None] * len(points) for _ in columns] for columns, points in requests]
+    for r, first, count, j0, k, at in calls:
+        for b in range(count):
+            for j in range(k):
+                w = at + 3 * (b * k + j)
+                results[r][first + b][j0 + j] = tuple(words[w:w + 3])
+    return results
+
+
+def _eval_jobs(jobs, points):
+    """jobs: (ptr, n, stride, batch) coefficient arrays -> per job [[limb triple of column b at point j] per column] per point: all
+    columns of all jobs in one bfsx_poly_eval_columns call per four points"""
+    columns = [(ptr + 8 * b * stride, n) for ptr, n, stride, batch in jobs for b in range(batch)]
+    got = _eval_requests([(columns, points)])[0]
     results, at = [], 0
     for ptr, n, stride, batch in jobs:
-        values = [[None] * batch for _ in points]
-        for first in range(0, len(points), MAX_POINTS_PER_LAUNCH):
-            k = min(MAX_POINTS_PER_LAUNCH, len(points) - first)
-            for b in range(batch):
-                for j in range(k):
-                    values[first + j][b] = tuple(words[at:at + 3])
-                    at += 3
-        results.append(values)
+        results.append([[got[at + b][j] for b in range(batch)] for j in range(len(points))])
+        at += batch
     return results
 
 
 def _eval_columns(ptr, n, stride, batch, points):
-    return _eval_jobs([(ptr, n, stride, batch)], points)[0]
+    """one strided buffer of `batch` columns of equal length -> [[limb triple of column b at point j] per column] per point:
+    bfs_poly_eval_points, four points per launch, every launch enqueued before the ONE read-back"""
+    lib, stream = _lib.load(), current_stream()
+    out = DeviceBuffer(3 * len(points) * batch)
+    at = 0
+    for chunk in _point_chunks(points):
+        _lib.check(lib.bfs_poly_eval_points(ptr, n, stride, batch, _flat_points(chunk), len(chunk), out.ptr + 8 * at, stream))
+        at += 3 * batch * len(chunk)
+    words = [int(v) for v in out.to_numpy()]
+    out.free()
+    values, at = [[None] * batch for _ in points], 0
+    for first, chunk in enumerate(_point_chunks(points)):
+        for b in range(batch):
+            for j in range(len(chunk)):
+                values[first * MAX_POINTS_PER_LAUNCH + j][b] = tuple(words[at:at + 3])
+                at += 3
+    return values
 
 
 def _combine_planes(v):
@@ -132,6 +182,10 @@ class Commitment:
     def root(self):
         return self.tree.root()
 
+    def column_of(self, position):
+        """the row column of the polynomial at `position` of the list `commit` was given (the inverse of `order`)"""
+        return self.order.index(position)
+
     def column_ptr(self, c):
         """first word of column c of the row (extension columns first)"""
         return self.codewords.ptr + 8 * self.n * (3 * c if c < self.n_ext else 3 * self.n_ext + (c - self.n_ext))
@@ -141,6 +195,72 @@ class Commitment:
         if self.n_base:
             reqs.append((self.column_ptr(self.n_ext) + 8 * i, self.n_base, self.n))
         return reqs
+
+
+class OpeningPlan:
+    """a checked opening plan: which row columns are opened where.  plan: a list of groups (columns_g, points_g) -- columns_g an
+    ascending, non-empty list of row columns, every column 0 .. m - 1 in exactly one group; points_g 1..4 pairwise different points
+    outside the domain (equal limb triples are one point; the same point may serve several groups).  At most 8 groups, 8 distinct
+    points, 16 (group, point) pairs, 32 columns.  Anything else raises ValueError with the reason -- before any GPU work.
+
+        points      the distinct points as limb triples, in order of first appearance
+        groups      per group (columns, indices into `points`)
+        base        base[g][j]: the exponent of lambda at which pair (g, j) starts (a running count of the pairs' columns)
+        shape       what the proof stream carries: per group (tuple(columns), tuple(point indices)), plain ints"""
+
+    def __init__(self, plan, in_domain, m=None):
+        try:
+            groups = [([int(c) for c in columns], [_limbs(z) for z in points]) for columns, points in plan]
+        except (TypeError, ValueError):
+            raise ValueError("an opening plan is a list of (columns, points) groups")
+        if not 1 <= len(groups) <= MAX_GROUPS:
+            raise ValueError("an opening plan has 1 .. %d groups (got %d)" % (MAX_GROUPS, len(groups)))
+        self.points, self.groups, self.base = [], [], []
+        seen, count = set(), 0
+        for g, (columns, points) in enumerate(groups):
+            if not columns or columns != sorted(set(columns)) or columns[0] < 0:
+                raise ValueError("group %d: columns must be an ascending, non-empty list of row columns" % g)
+            if seen & set(columns):
+                raise ValueError("group %d: column %d lies in an earlier group too" % (g, min(seen & set(columns))))
+            seen |= set(columns)
+            if not 1 <= len(points) <= MAX_POINTS_PER_LAUNCH or any(len(z) != 3 for z in points):
+                raise ValueError("group %d: 1 .. %d points of three limbs each" % (g, MAX_POINTS_PER_LAUNCH))
+            if len(set(points)) != len(points):
+                raise ValueError("group %d: a point appears twice" % g)
+            for z in points:
+                if in_domain(z):
+                    raise ValueError("cannot open at a point of the FRI domain: %s" % (z,))
+                if z not in self.points:
+                    self.points.append(z)
+            self.groups.append((columns, [self.points.index(z) for z in points]))
+            self.base.append([count + j * len(columns) for j in range(len(points))])
+            count += len(points) * len(columns)
+        self.m, self.exponents = len(seen), count
+        self.pairs = sum(len(indices) for _, indices in self.groups)
+        if seen != set(range(self.m)) or (m is not None and self.m != m):
+            raise ValueError("the groups must hold every column 0 .. %d exactly once" % ((self.m if m is None else m) - 1))
+        if self.m > MAX_COLUMNS:
+            raise ValueError("at most %d columns (got %d)" % (MAX_COLUMNS, self.m))
+        if len(self.points) > MAX_PLAN_POINTS:
+            raise ValueError("at most %d distinct points (got %d)" % (MAX_PLAN_POINTS, len(self.points)))
+        if self.pairs > MAX_PAIRS:
+            raise ValueError("at most %d (group, point) pairs (got %d)" % (MAX_PAIRS, self.pairs))
+        self.shape = [(tuple(columns), tuple(indices)) for columns, indices in self.groups]
+
+    def combined_values(self, values, lam):
+        """Y[g][j] = sum_r lambda^(base[g][j] + r) y_{g,j,r}; also the powers of lambda it used"""
+        powers = [(1, 0, 0)]
+        for _ in range(self.exponents):
+            powers.append(xmul(powers[-1], lam))
+        combined = []
+        for g, per_group in enumerate(values):
+            combined.append([])
+            for j, per_point in enumerate(per_group):
+                acc = (0, 0, 0)
+                for r, y in enumerate(per_point):
+                    acc = xadd(acc, xmul(powers[self.base[g][j] + r], y))
+                combined[-1].append(acc)
+        return combined, powers
 
 
 class PolynomialCommitment:
@@ -246,7 +366,7 @@ class PolynomialCommitment:
         """proves the values of every committed polynomial at `points` (1..4 ExtensionFieldElements outside the FRI domain); returns
         them: a list per point of a list per polynomial IN ROW ORDER -- extension polynomials first, then base polynomials, each group in
         the order `commit` was given them (Commitment.order[c] = position of row column c in that list)"""
-        xf, n, t, fri = self.xfield, self.n, self.fri.num_colinearity_tests, self.fri
+        xf = self.xfield
         assert 1 <= len(points) <= MAX_POINTS_PER_LAUNCH, "1 .. 4 points per opening"
         for z in points:
             if self.in_domain(z):
@@ -263,7 +383,13 @@ class PolynomialCommitment:
         values = [[xf.from_limbs(v) for v in per_point] for per_point in raw]
         proof_stream.push(values)
         lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        g = self.quotient(committed, pts, raw, lam)
+        self._prove_quotient(committed, self.quotient(committed, pts, raw, lam), proof_stream)
+        return values
+
+    def _prove_quotient(self, committed, g, proof_stream):
+        """what follows lambda in every opening: the root of the tree over g, the t consistency indices with their rows and openings of
+        g, then Fri.prove over g"""
+        xf, n, t, fri = self.xfield, self.n, self.fri.num_colinearity_tests, self.fri
         coset = fri.coset_leaves
         a = fri.folding_factor if coset else 1
         q = n // a
@@ -302,7 +428,6 @@ class PolynomialCommitment:
             fri.prove(g, proof_stream, round0_tree=g_tree)
         else:
             fri.prove(g, proof_stream, known_leafs=known or None, round0_tree=g_tree)
-        return values
 
     # ---------------------------------------------------------------------------------------------------------- verifier (host only)
     def verify(self, root, points, values, proof_stream):
@@ -316,7 +441,6 @@ class PolynomialCommitment:
                 return self.verify(root, points, values, proof_stream)
             finally:
                 leaf_pickle_source.reset(token)
-        n, t, fri = self.n, self.fri.num_colinearity_tests, self.fri
         is_element = lambda e: isinstance(e, ExtensionFieldElement)
         pts = [_limbs(z) for z in points]
         if not 1 <= len(pts) <= MAX_POINTS_PER_LAUNCH or any(self.in_domain(z) for z in pts):
@@ -335,6 +459,15 @@ class PolynomialCommitment:
             print("values differ from the caller's")
             return False
         lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
+        powers = [(1, 0, 0)]
+        for _ in range(len(pts) * m):
+            powers.append(xmul(powers[-1], lam))
+        return self._check_quotient(root, m, lambda i, row: self._quotient_at(i, row, pts, want, powers, m), proof_stream)
+
+    def _check_quotient(self, root, m, quotient_at, proof_stream):
+        """what follows lambda in every opening, read back: quotient_at(i, row as limb triples) is g[i] as the statement has it"""
+        n, t, fri = self.n, self.fri.num_colinearity_tests, self.fri
+        is_element = lambda e: isinstance(e, ExtensionFieldElement)
         g_root = proof_stream.pull()
         if not isinstance(g_root, (bytes, bytearray)):
             print("quotient root is not a digest")
@@ -344,9 +477,6 @@ class PolynomialCommitment:
         a = fri.folding_factor if coset else 1
         q = n // a
         # a row has its extension columns first; how many there are is read off the first row and must hold for every row
-        powers = [(1, 0, 0)]
-        for _ in range(len(pts) * m):
-            powers.append(xmul(powers[-1], lam))
         shape = None
         for i in indices:
             row = proof_stream.pull()
@@ -373,7 +503,7 @@ class PolynomialCommitment:
                 print("merkle authentication path verification fails for the quotient")
                 return False
             opened = _limbs(leaf[i // q] if coset else leaf)
-            if opened != self._quotient_at(i, [_limbs(e) for e in row], pts, want, powers, m):
+            if opened != quotient_at(i, [_limbs(e) for e in row]):
                 print("quotient does not match the opened row")
                 return False
         if not fri.verify(proof_stream, g_root):
@@ -398,4 +528,114 @@ class PolynomialCommitment:
             for p in range(m):
                 y = xadd(y, xmul(powers[j * m + p], values[j][p]))
             g = xadd(g, xmul(xsub(xmul(powers[j * m], s), y), xinv(xsub((x, 0, 0), z))))
+        return g
+
+    # ---------------------------------------------------------------------------------------------------------- opening plans
+    def plan(self, plan, m=None):
+        """the checked OpeningPlan of a list of (columns, points) groups (ValueError with the reason otherwise)"""
+        return plan if isinstance(plan, OpeningPlan) else OpeningPlan(plan, self.in_domain, m)
+
+    def quotient_at(self, committed, plan, values, lam):
+        """the DEEP quotient codeword (XArray) of an opening plan: bfsx_deep_quotient_groups.  values[g][j][r]: limb triples"""
+        n, m = self.n, len(committed.polys)
+        cols = (_lib.RowColumn * m)()
+        for at, c in enumerate(c for columns, _ in plan.groups for c in columns):         # (the kernel wants the columns in group order)
+            cols[at].d_values, cols[at].is_ext, cols[at].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
+        combined, _ = plan.combined_values(values, lam)
+        u32 = ctypes.c_uint32
+        g = XArray.empty(n, self.xfield)
+        _lib.check(_lib.load().bfsx_deep_quotient_groups(
+            cols, m, n, n.bit_length() - 1, self.offset, self.omega,
+            (u32 * len(plan.groups))(*[len(columns) for columns, _ in plan.groups]), (u32 * len(plan.groups))(*[len(indices) for _, indices in plan.groups]),
+            len(plan.groups), _flat_points(plan.points), len(plan.points), (u32 * plan.pairs)(*[p for _, indices in plan.groups for p in indices]),
+            _flat_points([y for per_group in combined for y in per_group]), (_u64 * 3)(*lam), g.ptr, g.stride, current_stream()))
+        return g
+
+    def open_at(self, committed, plan, proof_stream):
+        """proves, for every group (columns_g, points_g) of `plan` (see OpeningPlan), the values of the row columns columns_g at the
+        points points_g; returns them as values[g][j][r] = f_{columns_g[r]}(points_g[j]).  Commitment.column_of(position) is the row
+        column of the polynomial at `position` of the list `commit` was given.  The plan is checked before any GPU work (ValueError)."""
+        xf = self.xfield
+        plan = self.plan(plan, len(committed.polys))
+        proof_stream.push([xf.from_limbs(z) for z in plan.points])
+        proof_stream.push(plan.shape)
+        # one evaluation call per distinct point set: the coefficient columns of every group that is opened there
+        point_sets = list(dict.fromkeys(tuple(indices) for _, indices in plan.groups))
+        requests, places = [], {}
+        for point_set in point_sets:
+            coefficient_columns = []
+            for g, (columns, indices) in enumerate(plan.groups):
+                if tuple(indices) == point_set:
+                    for r, c in enumerate(columns):
+                        f = committed.polys[committed.order[c]]
+                        planes = [(f.ptr + 8 * l * f.stride, f.n) for l in range(3)] if isinstance(f, XArray) else [(f.ptr, f.n)]
+                        places[g, r] = (len(requests), len(coefficient_columns), len(planes))
+                        coefficient_columns += planes
+            requests.append((coefficient_columns, [plan.points[p] for p in point_set]))
+        got = _eval_requests(requests)
+        raw = []
+        for g, (columns, indices) in enumerate(plan.groups):
+            raw.append([[None] * len(columns) for _ in indices])
+            for r in range(len(columns)):
+                request, first, planes = places[g, r]
+                for j in range(len(indices)):
+                    v = [got[request][first + l][j] for l in range(planes)]
+                    raw[g][j][r] = _combine_planes(v) if planes == 3 else v[0]
+        values = [[[xf.from_limbs(v) for v in per_point] for per_point in per_group] for per_group in raw]
+        proof_stream.push(values)
+        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
+        self._prove_quotient(committed, self.quotient_at(committed, plan, raw, lam), proof_stream)
+        return values
+
+    def verify_at(self, root, plan, values, proof_stream):
+        """does the proof in `proof_stream` (read position right behind the commitment's root) show that the polynomials behind `root`
+        take `values` (what `open_at` returned: values[g][j][r]) under `plan`?  Host code only: Python ints, hashlib and Fri.verify; one
+        printed line per refusal."""
+        from .merkle import leaf_pickle_source
+        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
+            token = leaf_pickle_source.set(proof_stream.pickle_of)
+            try:
+                return self.verify_at(root, plan, values, proof_stream)
+            finally:
+                leaf_pickle_source.reset(token)
+        is_element = lambda e: isinstance(e, ExtensionFieldElement)
+        try:
+            plan = self.plan(plan)
+        except ValueError as e:
+            print("plan cannot be opened: %s" % e)
+            return False
+        pushed = proof_stream.pull()
+        if not isinstance(pushed, list) or not all(is_element(z) for z in pushed) or [_limbs(z) for z in pushed] != plan.points:
+            print("points differ from the caller's plan")
+            return False
+        if proof_stream.pull() != plan.shape:
+            print("groups differ from the caller's plan")
+            return False
+        claimed = proof_stream.pull()
+        try:
+            want = [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in values]
+        except TypeError:
+            want = None
+        lengths = [[len(columns)] * len(indices) for columns, indices in plan.groups]
+        if (want is None or [[len(per_point) for per_point in per_group] for per_group in want] != lengths or not isinstance(claimed, list)
+                or not all(isinstance(per_group, list) and all(isinstance(per_point, list) and all(is_element(v) for v in per_point) for per_point in per_group)
+                           for per_group in claimed)
+                or [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in claimed] != want):
+            print("values differ from the caller's")
+            return False
+        lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
+        combined, powers = plan.combined_values(want, lam)
+        return self._check_quotient(root, plan.m, lambda i, row: self._plan_quotient_at(i, row, plan, combined, powers), proof_stream)
+
+    def _plan_quotient_at(self, i, row, plan, combined, powers):
+        """g[i] from the row at x_i: sum_g sum_j (lambda^base[g][j] S_g - Y_{g,j}) / (x_i - z_{g,j})"""
+        x = self.offset * pow(self.omega, i, P) % P
+        inverse = [xinv(xsub((x, 0, 0), z)) for z in plan.points]
+        g = (0, 0, 0)
+        for (columns, indices), base, ys in zip(plan.groups, plan.base, combined):
+            s = (0, 0, 0)
+            for r, c in enumerate(columns):
+                s = xadd(s, xmul(powers[r], row[c]))
+            for p, b, y in zip(indices, base, ys):
+                g = xadd(g, xmul(xsub(xmul(powers[b], s), y), inverse[p]))
         return g

@@ -2,8 +2,9 @@
 expansion 4, 16 base + 4 extension polynomials of 2^20 coefficients, k = 2 points: HIP events around each call after one warm-up call
 of the same shape, the median of --reps calls per line (ms):
 
-    evaluation      bfs_poly_eval_points over the 28 coefficient columns (one call, batch 28), and as `open` makes it (one call per polynomial, one read-back)
-    quotient        bfs_deep_quotient over the 20 codewords
+    evaluation      bfs_poly_eval_points over the 28 coefficient columns (one call, batch 28), and as `open` makes it (separate arrays, one read-back)
+    quotient        bfs_deep_quotient over the 20 codewords; bfsx_deep_quotient_groups over the same codewords as one group at the same
+                    points, and as a STARK's plan (7 groups, 6 distinct points, 11 pairs)
     open            PolynomialCommitment.open as a whole (host clock, ends in the stream synchronise of Fri.prove's read-backs)
     combination     bfs_combination over the same 20 codewords as sources (what the quotient is compared with)
     extension       bfs_gl_ntt of the same 28 columns from 2^20 coefficients to the 2^22 coset (what the evaluation is compared with)
@@ -89,6 +90,21 @@ def main():
     values = [[(1 + j, 2 + p, 3) for p in range(N_BASE + N_EXT)] for j in range(K)]      # (the kernel's time does not depend on the claims)
     lam = (5, 6, 7)
     report["quotient_ms"] = timed(lambda: pc.quotient(committed, pts, values, lam), args.reps)
+
+    # the same codewords through bfsx_deep_quotient_groups: as ONE group at the same two points, and in the shape a STARK asks for --
+    # 7 groups, 6 distinct points (z, and z times one factor per table), 11 (group, point) pairs
+    m = N_BASE + N_EXT
+    one = pc.plan([(list(range(m)), pts)], m)
+    report["quotient_one_group_ms"] = timed(lambda: pc.quotient_at(committed, one, [values], lam), args.reps)
+    z = pts[0]
+    nexts = [tuple(v * pow(pc.omega, 1 << (3 + i), P) % P for v in z) for i in range(5)]
+    sizes, where = [4, 3, 3, 3, 2, 3, 2], [[z, nexts[0]], [z, nexts[1]], [z, nexts[2]], [z, nexts[3]], [nexts[4]], [z], [z]]
+    firsts = [sum(sizes[:g]) for g in range(len(sizes))]
+    stark = pc.plan([(list(range(first, first + size)), points_g) for first, size, points_g in zip(firsts, sizes, where)], m)
+    assert (len(stark.groups), len(stark.points), stark.pairs) == (7, 6, 11)
+    stark_values = [[[(1 + j, 2 + r, 3) for r in range(len(columns))] for j in range(len(indices))] for columns, indices in stark.groups]
+    report["quotient_stark_plan_ms"] = timed(lambda: pc.quotient_at(committed, stark, stark_values, lam), args.reps)
+    report["quotient_again_ms"] = timed(lambda: pc.quotient(committed, pts, values, lam), args.reps)      # (the old kernel once more: its run-to-run spread)
 
     sources = (_lib.CombSource * (N_BASE + N_EXT))()
     for c in range(N_BASE + N_EXT):

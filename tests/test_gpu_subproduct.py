@@ -1,13 +1,18 @@
 """The subproduct tree on the MI355X (csrc/subproduct.hip, SubproductTree, the array and list forms of fast_zerofier /
 fast_evaluate / fast_interpolate): against the reference's fixtures, the private recursion, host arithmetic on Python ints and the
-NTT on cosets.  Expected values never come from the tree itself."""
+NTT on cosets; and, on ragged domains whose trees have partial and empty nodes, at EVERY output against the oracle's coset
+transform (tests/subproduct_check.py).  Expected values never come from the tree itself."""
+import ctypes
 import importlib
 import random
 
 import numpy as np
 import pytest
 
+import subproduct_check as sc
 from conftest import load_golden
+from painted import PAINT_WORD, Arena
+from stream_builders import strided
 
 pytestmark = pytest.mark.gpu
 
@@ -294,3 +299,217 @@ def test_lifted_memory_table_shape_is_fast(sb):
     for i in rng.sample(range(n), 6):
         assert poly.evaluate(D[i]) == V[i]
     assert dt < 1.0, dt
+
+
+# ---- every output, on domains with partial and empty nodes (tests/subproduct_check.py) -------------------------------------------------
+# A domain is made of points the oracle's coset transform reaches (plus a few free points for Horner), so all n outputs of all
+# three operations are decided on the CPU without O(n^2) work: an evaluation is compared word for word, an interpolant is the one
+# vector of n words that takes the values, a zerofier the one monic vector of n + 1 words that vanishes on the domain.
+# tests/test_subproduct_checker.py holds the checkers to that and the size lists to the node shapes they must reach.
+BFS_ERR_ZERO_IN_BATCH_INVERSE = 5
+SEED = 0x5B
+
+
+@pytest.fixture(scope="module")
+def lib(sb):
+    from stark_brainfuck_amd import _lib
+    return _lib.load()
+
+
+def ok(rc):
+    from stark_brainfuck_amd import _lib
+    _lib.check(rc)
+
+
+def ragged_domain(n):
+    return sc.ragged(n, SEED, sc.FREE_POINTS if n in sc.FREE_SIZES else ())
+
+
+def tree_of(sb, dom):
+    return sb.SubproductTree(sb.BaseArray.from_numpy(sc.points(dom)))
+
+
+def check_all_three(sb, dom, tree, counts, seed):
+    """zerofier, one evaluation per coefficient count and a three-column interpolation of `tree` through the checkers"""
+    n = len(dom)
+    sc.check_zerofier(dom, tree.zerofier().to_numpy())
+    for m in counts:
+        coeffs = sc.column("random", m, seed + m)
+        sc.check_evaluate(dom, coeffs, tree.evaluate(sb.BaseArray.from_numpy(coeffs)).to_numpy())
+    values = sc.columns(3, n, seed)
+    got = tree.interpolate(sb.BaseArray.from_numpy(values)).to_numpy()
+    assert got.shape == (3, n)
+    for b in range(3):
+        sc.check_interpolant(dom, values[b], got[b])
+
+
+@pytest.mark.parametrize("n", sc.SMALL_SIZES + sc.TREE_SIZES)
+def test_every_output_on_ragged_domains(sb, n):
+    dom = ragged_domain(n)
+    check_all_three(sb, dom, tree_of(sb, dom), sc.coefficient_counts(n), 31 * n)
+
+
+class AbiTree:
+    """bfs_ptree_build over a domain, freed on exit; `points` is the device copy the tree was built from"""
+
+    def __init__(self, lib, dom):
+        from stark_brainfuck_amd.device import DeviceBuffer
+        self.lib, self.host = lib, sc.points(dom)
+        self.points = DeviceBuffer.from_numpy(self.host)
+        self.handle = ctypes.c_void_p()
+        ok(lib.bfs_ptree_build(self.points.ptr, len(dom), 0, ctypes.byref(self.handle)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        from stark_brainfuck_amd.device import synchronize
+        ok(self.lib.bfs_ptree_free(self.handle, 0))
+        synchronize(0)
+
+
+def strided_input(cols, stride):
+    """the columns `stride` apart on the device, the gaps numbered; (device buffer, host copy)"""
+    from stark_brainfuck_amd.device import DeviceBuffer
+    host = strided(cols, stride, np.arange(1, cols.shape[0] * stride + 1, dtype=np.uint64))
+    return DeviceBuffer.from_numpy(host), host
+
+
+@pytest.mark.parametrize("batch", [1, 3, 7])
+@pytest.mark.parametrize("n", [257, 4100])
+def test_strided_columns_of_every_kind_through_the_c_abi(lib, n, batch):
+    """in_stride = m + 5, out_stride = n + 3: every column against the checker, the words between the columns of the output and
+    around it keep their paint, inputs and points read back as they went up; no coefficients at all give zeros"""
+    dom = ragged_domain(n)
+    out_stride = n + 3
+    with AbiTree(lib, dom) as tree:
+        assert lib.bfs_ptree_size(tree.handle) == n
+        for m in (0, 1, n, n + 129, 2 * n + 5):
+            in_stride = m + 5
+            cols = sc.columns(batch, m, SEED + m)
+            src, host = strided_input(cols, in_stride)
+            out = Arena(batch=batch, stride=out_stride, n=n)
+            ok(lib.bfs_ptree_evaluate(tree.handle, src.ptr if m else None, m, in_stride, batch, out.ptr, out_stride, 0))
+            got = out.rows(out.contained([("coefficients", host, src.to_numpy()), ("points", tree.host, tree.points.to_numpy())]))
+            for b in range(batch):
+                if m == 0:
+                    assert not got[b].any(), b
+                else:
+                    sc.check_evaluate(dom, cols[b], got[b])
+        in_stride = n + 5
+        values = sc.columns(batch, n, SEED + 1)
+        src, host = strided_input(values, in_stride)
+        out = Arena(batch=batch, stride=out_stride, n=n)
+        ok(lib.bfs_ptree_interpolate(tree.handle, src.ptr, in_stride, batch, out.ptr, out_stride, 0))
+        got = out.rows(out.contained([("values", host, src.to_numpy()), ("points", tree.host, tree.points.to_numpy())]))
+        for b in range(batch):
+            sc.check_interpolant(dom, values[b], got[b])
+
+
+@pytest.mark.parametrize("n", [385, 4100])
+def test_extension_columns_limb_by_limb(sb, n):
+    dom = ragged_domain(n)
+    tree = tree_of(sb, dom)
+    for m in (n - 1, n + 129):
+        limbs = sc.columns(3, m, SEED + 2 * m)
+        got = tree.evaluate(sb.XArray.from_numpy(limbs))
+        assert isinstance(got, sb.XArray)
+        got = got.to_numpy()
+        assert got.shape == (3, n)
+        for k in range(3):
+            sc.check_evaluate(dom, limbs[k], got[k])
+    values = sc.columns(3, n, SEED + 3)
+    got = tree.interpolate(sb.XArray.from_numpy(values))
+    assert isinstance(got, sb.XArray)
+    got = got.to_numpy()
+    assert got.shape == (3, n)
+    for k in range(3):
+        sc.check_interpolant(dom, values[k], got[k])
+
+
+def limb_planes(elements):
+    """(3, len) limbs of a list of ExtensionFieldElements, read from the objects"""
+    out = np.zeros((3, len(elements)), dtype=np.uint64)
+    for i, e in enumerate(elements):
+        for k, c in enumerate(e.polynomial.coefficients):
+            out[k, i] = c.value
+    return out
+
+
+@pytest.mark.parametrize("r", [1, 4])
+@pytest.mark.parametrize("k", [8, 12])
+def test_table_shape_at_every_output(sb, k, r):
+    """what Table.interpolate_columns passes: 2^k rows and r randomizer points -- one full half, a sibling of degree r and empty
+    nodes all the way up.  Through SubproductTree, and through the list calls with lifted domain, lifted root, extension values."""
+    dom = sc.table_shape(k, r)
+    n, order = len(dom), dom.order
+    check_all_three(sb, dom, tree_of(sb, dom), (n - 1, n, n + 1, 2 * n + 5), 77 * n)
+    XF = sb.ExtensionField.main()
+    F = XF._base()
+    root = XF.lift(F.primitive_nth_root(order))
+    D = [XF.lift(F(int(x))) for x in sc.points(dom)]
+    z = sb.fast_zerofier(D, root, order)
+    assert all(type(c) is sb.ExtensionFieldElement for c in z.coefficients)
+    planes = limb_planes(z.coefficients)
+    sc.check_zerofier(dom, planes[0])
+    assert not planes[1:].any()
+    values = sc.columns(3, n, 78 * n)
+    poly = sb.fast_interpolate(D, [XF.from_limbs([int(v) for v in values[:, i]]) for i in range(n)], root, order)
+    assert len(poly.coefficients) == n and all(type(c) is sb.ExtensionFieldElement for c in poly.coefficients)
+    planes = limb_planes(poly.coefficients)
+    for l in range(3):
+        sc.check_interpolant(dom, values[l], planes[l])
+    coeffs = sc.columns(3, n + 3, 79 * n)
+    ev = sb.fast_evaluate(sb.Polynomial([XF.from_limbs([int(v) for v in coeffs[:, i]]) for i in range(n + 3)]), D, root, order)
+    assert len(ev) == n and all(type(v) is sb.ExtensionFieldElement for v in ev)
+    planes = limb_planes(ev)
+    for l in range(3):
+        sc.check_evaluate(dom, coeffs[l], planes[l])
+
+
+@pytest.mark.parametrize("n", [257, 4100])
+def test_equal_points_in_different_subtrees(sb, lib, n):
+    """position n - 1 repeats position 0 and position 128 repeats position 127: interpolation is undefined (the C entry reports
+    the zero of the batch inverse and writes nothing, the wrapper raises), the zerofier and evaluation are what they were.  No free
+    points here: a repeated 0 would give the last, partial subtree a constant term of 0, which hides what is done to it"""
+    dom = sc.with_equal(sc.ragged(n, SEED + 1), [(0, n - 1), (127, 128)])
+    batch, in_stride, out_stride = 3, n + 5, n + 3
+    values = sc.columns(batch, n, SEED + 4)
+    with AbiTree(lib, dom) as tree:
+        src, host = strided_input(values, in_stride)
+        out = Arena(batch=batch, stride=out_stride, n=n)
+        assert lib.bfs_ptree_interpolate(tree.handle, src.ptr, in_stride, batch, out.ptr, out_stride, 0) == BFS_ERR_ZERO_IN_BATCH_INVERSE
+        after = out.contained([("values", host, src.to_numpy()), ("points", tree.host, tree.points.to_numpy())])
+        assert (after == np.uint64(PAINT_WORD)).all()
+    tree = tree_of(sb, dom)
+    with pytest.raises(AssertionError):
+        tree.interpolate(sb.BaseArray.from_numpy(values[0]))
+    z = tree.zerofier().to_numpy()
+    sc.check_zerofier(dom, z)
+    sc.check_double_roots(dom, z, (0, 127))
+    for m in (n, n + 129):
+        coeffs = sc.column("random", m, SEED + m)
+        sc.check_evaluate(dom, coeffs, tree.evaluate(sb.BaseArray.from_numpy(coeffs)).to_numpy())
+
+
+def test_one_tree_serves_many_calls(sb):
+    """evaluate, interpolate, evaluate again on one handle with other batch sizes in between: the kept transforms are read only"""
+    n = 1000
+    dom = ragged_domain(n)
+    tree = tree_of(sb, dom)
+    coeffs = sc.column("random", n + 129, SEED + 5)
+    values = sc.columns(3, n, SEED + 6)
+    seven = sc.columns(7, n - 1, SEED + 7)
+    first = tree.evaluate(sb.BaseArray.from_numpy(coeffs)).to_numpy()
+    three = tree.interpolate(sb.BaseArray.from_numpy(values)).to_numpy()
+    wide = tree.evaluate(sb.BaseArray.from_numpy(seven)).to_numpy()
+    one = tree.interpolate(sb.BaseArray.from_numpy(values[0])).to_numpy()
+    again = tree.evaluate(sb.BaseArray.from_numpy(coeffs)).to_numpy()
+    zero = tree.zerofier().to_numpy()
+    sc.check_evaluate(dom, coeffs, first)
+    assert (again == first).all() and (one == three[0]).all()
+    for b in range(3):
+        sc.check_interpolant(dom, values[b], three[b])
+    for b in range(7):
+        sc.check_evaluate(dom, seven[b], wide[b])
+    sc.check_zerofier(dom, zero)

@@ -184,6 +184,12 @@ _OPEN_SIGNATURES = {
                                        ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, u64, vp]),
 }
 
+# include/bfstark_rounds.h: openings across commitments (prefix bfsr_; the header says why); bound together with the three tables above
+_ROUNDS_SIGNATURES = {
+    "bfsr_deep_quotient_rounds": (ci, [vp, u32, u64, u32, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), u32, ctypes.POINTER(u64), u32,
+                                       ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u32), vp]),
+}
+
 
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
@@ -273,6 +279,11 @@ def open_exported_symbols():
     return sorted(_OPEN_SIGNATURES)
 
 
+def rounds_exported_symbols():
+    """names include/bfstark_rounds.h declares"""
+    return sorted(_ROUNDS_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -289,7 +300,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()) + list(_ROUNDS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -3,10 +3,13 @@
 // codewords.  The per-thread arithmetic, with the cost argument, is deep_core.hpp; DESIGN.md "Opening at out-of-domain points".
 // include/bfstark_open.h adds the same two for opening plans: separate columns of their own lengths evaluated in one call, and the
 // quotient of groups of columns that are opened at different points, in one launch.
+// include/bfstark_rounds.h adds the quotient of a plan over the columns of several commitments: the same kernel, launched as often as
+// the plan needs (deep_core.hpp: deep_rounds_split), every launch after the first accumulating into the output.
 // No entry synchronises, copies from the host or allocates outside the stream-ordered pool: the points, weights, constants, column
 // tables and plans of a call travel as kernel arguments.
 #include "../../include/bfstark_ext.h"
 #include "../../include/bfstark_open.h"
+#include "../../include/bfstark_rounds.h"
 #include "deep_core.hpp"
 #include "runtime.hpp"
 
@@ -107,7 +110,8 @@ __global__ void __launch_bounds__(DEEP_Q_T) deep_quotient_kernel(DeepQuotientArg
 static_assert(sizeof(DeepGroupsArgs) + 2 * sizeof(u64) <= 4096, "the plan must fit the kernel-argument block");
 static_assert(sizeof(DeepEvalColumns) + 4 * sizeof(u64) <= 4096, "the column table must fit the kernel-argument block");
 
-template <int NP>
+// ACC: a later launch of an opening across commitments (deep_core.hpp): the sum starts from what `out` holds
+template <int NP, bool ACC>
 __global__ void __launch_bounds__(DEEP_G_T) deep_groups_kernel(DeepGroupsArgs a, u64* out, u64 out_stride) {
     constexpr int E = (int)deep_groups_e(NP);
     const u64 first = (u64)blockIdx.x * (DEEP_G_T * E) + threadIdx.x;
@@ -115,7 +119,17 @@ __global__ void __launch_bounds__(DEEP_G_T) deep_groups_kernel(DeepGroupsArgs a,
 #pragma unroll
     for (int e = 0; e < E; ++e) idx[e] = first + (u64)e * DEEP_G_T;
     Xfe g[E];
-    deep_groups_thread<NP, E>(a, idx, g);
+    if constexpr (ACC) {
+        Xfe start[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const u64 at = idx[e] < a.n ? idx[e] : 0;      // (a thread past the end reads point 0 and stores nothing)
+            start[e] = Xfe{{out[at], out[out_stride + at], out[2 * out_stride + at]}};
+        }
+        deep_groups_thread_from<NP, E>(a, idx, start, g);
+    } else {
+        deep_groups_thread<NP, E>(a, idx, g);
+    }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         if (idx[e] < a.n) { out[idx[e]] = g[e].c[0]; out[out_stride + idx[e]] = g[e].c[1]; out[2 * out_stride + idx[e]] = g[e].c[2]; }
@@ -350,9 +364,81 @@ extern "C" int bfsx_deep_quotient_groups(const bfs_row_column* h_columns, uint32
     const u64 share = (u64)DEEP_G_T * deep_groups_e(n_points);
     const u32 grid = (u32)((n + share - 1) / share);
     BFS_TRY(with_distinct_points(n_points, [&](auto np) -> int {
-        hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
+        hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, false>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
         return BFS_OK;
     }));
     BFS_HIP(hipGetLastError());
+    return BFS_OK;
+}
+
+extern "C" int bfsr_deep_quotient_rounds(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
+                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
+                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
+                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, uint32_t* h_launches, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!h_columns || !h_group_columns || !h_group_pairs || !h_points || !h_pair_point || !h_pair_values || !h_lambda || !d_out) {
+        set_error("bfsr_deep_quotient_rounds: null argument"); return BFS_ERR_BAD_ARG;
+    }
+    if (m < 1 || m > DEEP_R_COLUMNS) { set_error("bfsr_deep_quotient_rounds: 1..%u codewords (got %u)", DEEP_R_COLUMNS, m); return BFS_ERR_BAD_ARG; }
+    if (n_groups < 1 || n_groups > DEEP_R_GROUPS) { set_error("bfsr_deep_quotient_rounds: 1..%u groups (got %u)", DEEP_R_GROUPS, n_groups); return BFS_ERR_BAD_ARG; }
+    if (n_points < 1 || n_points > DEEP_R_POINTS) { set_error("bfsr_deep_quotient_rounds: 1..%u distinct points (got %u)", DEEP_R_POINTS, n_points); return BFS_ERR_BAD_ARG; }
+    if (log_n < 1 || log_n > 24) { set_error("bfsr_deep_quotient_rounds: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
+    const u64 n = 1ull << log_n;
+    if (limb_stride < n || out_stride < n) { set_error("bfsr_deep_quotient_rounds: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
+    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfsr_deep_quotient_rounds: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
+    if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
+    if (!canonical3(h_lambda)) { set_error("bfsr_deep_quotient_rounds: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
+    u32 columns = 0, pairs = 0;
+    for (u32 g = 0; g < n_groups; ++g) {
+        if (h_group_columns[g] < 1 || h_group_columns[g] > m - columns) { set_error("bfsr_deep_quotient_rounds: group %u: an empty group, or more columns than there are", g); return BFS_ERR_BAD_ARG; }
+        if (h_group_columns[g] > DEEP_MAX_COLUMNS) { set_error("bfsr_deep_quotient_rounds: group %u: at most %u columns in a group (got %u)", g, DEEP_MAX_COLUMNS, h_group_columns[g]); return BFS_ERR_BAD_ARG; }
+        if (h_group_pairs[g] < 1 || h_group_pairs[g] > DEEP_MAX_POINTS) { set_error("bfsr_deep_quotient_rounds: group %u: 1..%u points (got %u)", g, DEEP_MAX_POINTS, h_group_pairs[g]); return BFS_ERR_BAD_ARG; }
+        if (pairs + h_group_pairs[g] > DEEP_R_PAIRS) { set_error("bfsr_deep_quotient_rounds: more than %u (group, point) pairs", DEEP_R_PAIRS); return BFS_ERR_BAD_ARG; }
+        u32 seen = 0;
+        for (u32 j = 0; j < h_group_pairs[g]; ++j) {
+            const u32 q = pairs + j, point = h_pair_point[q];
+            if (point >= n_points) { set_error("bfsr_deep_quotient_rounds: pair %u names point %u of %u", q, point, n_points); return BFS_ERR_BAD_ARG; }
+            if ((seen >> point) & 1) { set_error("bfsr_deep_quotient_rounds: group %u opens point %u twice", g, point); return BFS_ERR_BAD_ARG; }
+            seen |= 1u << point;
+            if (!canonical3(h_pair_values + 3 * q)) { set_error("bfsr_deep_quotient_rounds: value %u is not reduced", q); return BFS_ERR_BAD_ARG; }
+        }
+        columns += h_group_columns[g];
+        pairs += h_group_pairs[g];
+    }
+    if (columns != m) { set_error("bfsr_deep_quotient_rounds: the groups hold %u columns, not %u", columns, m); return BFS_ERR_BAD_ARG; }
+    for (u32 p = 0; p < n_points; ++p) {
+        if (!canonical3(h_points + 3 * p)) { set_error("bfsr_deep_quotient_rounds: point %u is not reduced", p); return BFS_ERR_BAD_ARG; }
+    }
+    const u64 out_bytes = (2 * out_stride + n) * 8;
+    const u64* col[DEEP_R_COLUMNS];
+    int is_ext[DEEP_R_COLUMNS];
+    for (u32 c = 0; c < m; ++c) {
+        const bfs_row_column& column = h_columns[c];
+        if (!column.d_values) { set_error("bfsr_deep_quotient_rounds: codeword %u is null", c); return BFS_ERR_BAD_ARG; }
+        if (overlaps(d_out, out_bytes, column.d_values, (column.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfsr_deep_quotient_rounds: d_out overlaps codeword %u", c); return BFS_ERR_BAD_ARG; }
+        col[c] = column.d_values;
+        is_ext[c] = column.is_ext != 0;
+    }
+    DeepRoundsLaunch launches[DEEP_R_GROUPS];
+    const u32 count = deep_rounds_split(h_group_columns, h_group_pairs, n_groups, h_pair_point, launches);
+    if (h_launches) *h_launches = count;
+    DeepGroupsArgs common{};
+    common.limb_stride = limb_stride; common.n = n; common.offset = offset;
+    BFS_TRY(ntt_power_tables(omega, log_n, &common.w_lo, &common.w_hi, &common.lo_bits));
+    const Xfe lambda = xfe_load3(h_lambda);
+    Xfe scale{{1, 0, 0}};                                 // lambda^base of the next pair, across the launches
+    for (u32 l = 0; l < count; ++l) {
+        DeepGroupsArgs a = common;
+        deep_rounds_args(a, launches[l], col, is_ext, h_group_columns, h_group_pairs, h_points, h_pair_point, h_pair_values, lambda, scale);
+        const u64 share = (u64)DEEP_G_T * deep_groups_e(launches[l].n_points);
+        const u32 grid = (u32)((n + share - 1) / share);
+        BFS_TRY(with_distinct_points(launches[l].n_points, [&](auto np) -> int {
+            // the first launch writes d_out and never reads it; every later one starts from what the one before left there
+            if (l == 0) hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, false>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
+            else hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, true>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
+            return BFS_OK;
+        }));
+        BFS_HIP(hipGetLastError());
+    }
     return BFS_OK;
 }

@@ -18,7 +18,8 @@
 // so their products are constants of the launch.  The E * k norms of a thread share ONE base-field inversion (Montgomery's trick).
 //
 // The two entries of include/bfstark_open.h reuse both: evaluation of separate columns of different lengths in one launch, and the
-// quotient of an opening plan (groups of columns, each with its own points); their parts of this file say what is new.
+// quotient of an opening plan (groups of columns, each with its own points); their parts of this file say what is new.  The entry of
+// include/bfstark_rounds.h splits a plan over the columns of several commitments between launches of that kernel (the last part).
 #pragma once
 #include <stddef.h>
 
@@ -254,9 +255,10 @@ inline void deep_group_point(DeepGroupPoint& c, const Xfe& z) {
     c.z0 = full.z0; c.a1 = full.a1; c.a2 = full.a2; c.d_a1 = full.d_a1; c.d_a2 = full.d_a2; c.a1_sq = full.a1_sq;
 }
 
-// the E points idx[e] of one thread (idx[e] >= n: none); NP distinct points
+// the E points idx[e] of one thread (idx[e] >= n: none); NP distinct points; the sum over the pairs starts from start[e] (an earlier
+// launch's share of the same opening, see "openings across commitments" below)
 template <int NP, int E>
-BFS_HD void deep_groups_thread(const DeepGroupsArgs& a, const u64 idx[E], Xfe out[E]) {
+BFS_HD void deep_groups_thread_from(const DeepGroupsArgs& a, const u64 idx[E], const Xfe start[E], Xfe out[E]) {
     Xfe cof[E][NP];
     u64 norm[E][NP], before[E][NP], at[E];
     u64 run = 1;
@@ -284,7 +286,7 @@ BFS_HD void deep_groups_thread(const DeepGroupsArgs& a, const u64 idx[E], Xfe ou
     }
     Xfe g[E];
     BFS_UNROLL
-    for (int e = 0; e < E; ++e) g[e] = Xfe{{0, 0, 0}};
+    for (int e = 0; e < E; ++e) g[e] = start[e];
     u32 c0 = 0, q0 = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma nounroll
@@ -318,6 +320,94 @@ BFS_HD void deep_groups_thread(const DeepGroupsArgs& a, const u64 idx[E], Xfe ou
     }
     BFS_UNROLL
     for (int e = 0; e < E; ++e) out[e] = g[e];
+}
+
+// a whole plan in one launch: the sum starts from zero
+template <int NP, int E>
+BFS_HD void deep_groups_thread(const DeepGroupsArgs& a, const u64 idx[E], Xfe out[E]) {
+    Xfe zero[E];
+    BFS_UNROLL
+    for (int e = 0; e < E; ++e) zero[e] = Xfe{{0, 0, 0}};
+    deep_groups_thread_from<NP, E>(a, idx, zero, out);
+}
+
+// ---- openings across commitments (include/bfstark_rounds.h: bfsr_deep_quotient_rounds) ----
+// A plan over the columns of several commitments is larger than one launch takes: up to 96 columns, 24 groups, 24 distinct points,
+// 48 pairs.  The sum over the groups is split between launches -- field addition is exact, so the split changes no word of g: the first
+// launch writes g, every later one starts from what it finds there (deep_groups_thread_from).  The pairs carry lambda^base as `scale`,
+// so a later launch simply receives its pairs' powers; a launch gets only the distinct points its own groups use, re-indexed in order of
+// first appearance, and with them its own NP and E.  The rule is the one function below, which tests/emu/emu_deep_rounds.cpp runs too.
+constexpr u32 DEEP_R_COLUMNS = 96;
+constexpr u32 DEEP_R_GROUPS = 24;
+constexpr u32 DEEP_R_POINTS = 24;
+constexpr u32 DEEP_R_PAIRS = 48;
+
+struct DeepRoundsLaunch {
+    u32 first_group, n_groups;
+    u32 first_column, n_columns;
+    u32 first_pair, n_pairs;
+    u32 n_points;
+    u32 point[DEEP_G_POINTS];       // the plan's index of the launch's point p < n_points
+};
+
+// Groups in plan order; a launch takes groups while its columns <= 32, its groups <= 8, its pairs <= 16 and the distinct points among
+// its groups <= 8; the first group that would break one of these starts the next launch.  Every group has 1..32 columns and 1..4 pairs
+// (the caller has checked), so a group alone always fits.  launches: room for n_groups entries.  -> the number of launches
+inline u32 deep_rounds_split(const u32* group_columns, const u32* group_pairs, u32 n_groups, const u32* pair_point, DeepRoundsLaunch* launches) {
+    u32 count = 0, c = 0, q = 0;
+    DeepRoundsLaunch cur{};
+    for (u32 g = 0; g < n_groups; ++g) {
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            u32 pts[DEEP_G_POINTS + DEEP_MAX_POINTS], np = cur.n_points;
+            for (u32 p = 0; p < np; ++p) pts[p] = cur.point[p];
+            for (u32 j = 0; j < group_pairs[g]; ++j) {
+                u32 p = 0;
+                while (p < np && pts[p] != pair_point[q + j]) ++p;
+                if (p == np) pts[np++] = pair_point[q + j];
+            }
+            if (cur.n_columns + group_columns[g] <= DEEP_MAX_COLUMNS && cur.n_groups + 1 <= DEEP_G_GROUPS && cur.n_pairs + group_pairs[g] <= DEEP_G_PAIRS &&
+                np <= DEEP_G_POINTS) {
+                cur.n_groups += 1; cur.n_columns += group_columns[g]; cur.n_pairs += group_pairs[g]; cur.n_points = np;
+                for (u32 p = 0; p < np; ++p) cur.point[p] = pts[p];
+                break;
+            }
+            launches[count++] = cur;                       // (never on the second attempt: a group alone fits)
+            cur = DeepRoundsLaunch{};
+            cur.first_group = g; cur.first_column = c; cur.first_pair = q;
+        }
+        c += group_columns[g]; q += group_pairs[g];
+    }
+    launches[count++] = cur;
+    return count;
+}
+
+// the plan's part of launch L's arguments (the caller fills n, strides, offset and the tables of omega).  col / is_ext: the columns of
+// the WHOLE plan in group order; points, pair_point, pair_values: the whole plan's.  scale: lambda^base of L's first pair on entry, of
+// the next launch's first pair on return.
+inline void deep_rounds_args(DeepGroupsArgs& a, const DeepRoundsLaunch& L, const u64* const* col, const int* is_ext, const u32* group_columns,
+                             const u32* group_pairs, const u64* points, const u32* pair_point, const u64* pair_values, const Xfe& lambda, Xfe& scale) {
+    a.n_groups = L.n_groups;
+    a.ext_mask = 0;
+    for (u32 p = 0; p < L.n_points; ++p) deep_group_point(a.pt[p], xfe_load3(points + 3 * (size_t)L.point[p]));
+    u32 c = 0, q = 0;
+    for (u32 g = 0; g < L.n_groups; ++g) {
+        Xfe power{{1, 0, 0}};                             // lambda^r
+        for (u32 r = 0; r < group_columns[L.first_group + g]; ++r, ++c) {
+            a.col[c] = col[L.first_column + c];
+            if (is_ext[L.first_column + c]) a.ext_mask |= 1u << c;
+            lazy_weight_matrix(power, a.weight[c]);
+            power = xfe_mul(power, lambda);
+        }
+        for (u32 j = 0; j < group_pairs[L.first_group + g]; ++j, ++q) {
+            DeepGroupPair& pr = a.pair[q];
+            u32 p = 0;
+            while (L.point[p] != pair_point[L.first_pair + q]) ++p;          // (deep_rounds_split put it there)
+            pr.scale = scale; pr.y = xfe_load3(pair_values + 3 * (size_t)(L.first_pair + q)); pr.point = p;
+            pr.unit = scale.c[0] == 1 && scale.c[1] == 0 && scale.c[2] == 0;
+            scale = xfe_mul(scale, power);                // power = lambda^|columns_g| here
+        }
+        a.col_end[g] = c; a.pair_end[g] = q;
+    }
 }
 
 }  // namespace bfs

@@ -33,7 +33,21 @@ With base[g][j] a running count over the pairs in plan order, raised by |columns
 of first appearance (a list of elements); the plan's shape (a list per group of (tuple(columns), tuple(point indices)), plain ints, so that
 the plan is inside every later Fiat-Shamir hash); the values (a list per group of a list per point of a list per column); from lambda on
 exactly as `open`.
+
+Opening the polynomials of several commitments with one proof (include/bfstark_rounds.h):
+      .open_rounds(commitments, plan, proof_stream)              1..4 Commitments of this PolynomialCommitment; returns values[g][j][r]
+      .verify_rounds(roots, widths, plan, values, proof_stream)  host only; widths = the commitments' row widths
+      .global_column(commitments, r, c)                          row column c of commitments[r] in the plan's numbering
+The commitments are made at any moments of one transcript (each `commit` pushes its root; the caller pushes, pulls and draws challenges in
+between).  Their row columns are numbered through, first[r] = m_0 + .. + m_{r-1}, M = sum m_r <= 96, and the plan is an OpeningPlan over
+the M columns with wider limits (24 groups, 24 distinct points, 48 pairs, 32 columns in any one group); a group may hold columns of
+different commitments.  g is the formula above with M in the place of m.  Proof stream of `open_rounds` (all roots are in the stream
+already): the distinct points in order of first appearance; the shape (tuple(widths), [(tuple(columns), tuple(point indices)) per
+group]), plain ints -- numbering and plan are inside every later Fiat-Shamir hash; the values; [lambda]; the root of the tree over g;
+[t indices]; per index i: for r = 0 .. R - 1 the row tuple of C_r at x_i and its authentication path, then the opening of g as above;
+then Fri.prove over g.  With one commitment the quotient is `open_at`'s and the stream differs by the widths in the shape.
 """
+import collections
 import ctypes
 from hashlib import blake2b
 
@@ -53,6 +67,10 @@ MAX_POINTS_PER_LAUNCH = 4          # bfs_poly_eval_points, bfs_deep_quotient
 MAX_COLUMNS, MAX_EXT_COLUMNS = 32, 16   # bfs_merkle_build_rows
 MAX_COLUMNS_PER_EVALUATION = 96    # bfsx_poly_eval_columns
 MAX_GROUPS, MAX_PLAN_POINTS, MAX_PAIRS = 8, 8, 16   # bfsx_deep_quotient_groups: an opening plan
+MAX_COMMITMENTS = 4                # open_rounds
+PlanLimits = collections.namedtuple("PlanLimits", "groups points pairs columns group_columns")
+PLAN_LIMITS = PlanLimits(MAX_GROUPS, MAX_PLAN_POINTS, MAX_PAIRS, MAX_COLUMNS, MAX_COLUMNS)      # one commitment: one launch
+ROUNDS_LIMITS = PlanLimits(24, 24, 48, 96, MAX_COLUMNS)                                         # bfsr_deep_quotient_rounds
 
 
 def _limbs(z):
@@ -201,20 +219,22 @@ class OpeningPlan:
     """a checked opening plan: which row columns are opened where.  plan: a list of groups (columns_g, points_g) -- columns_g an
     ascending, non-empty list of row columns, every column 0 .. m - 1 in exactly one group; points_g 1..4 pairwise different points
     outside the domain (equal limb triples are one point; the same point may serve several groups).  At most 8 groups, 8 distinct
-    points, 16 (group, point) pairs, 32 columns.  Anything else raises ValueError with the reason -- before any GPU work.
+    points, 16 (group, point) pairs, 32 columns -- or what `limits` (a PlanLimits) says: ROUNDS_LIMITS for a plan over the columns of
+    several commitments (24 groups, 24 distinct points, 48 pairs, 96 columns, 32 in any one group).  Anything else raises ValueError
+    with the reason -- before any GPU work.
 
         points      the distinct points as limb triples, in order of first appearance
         groups      per group (columns, indices into `points`)
         base        base[g][j]: the exponent of lambda at which pair (g, j) starts (a running count of the pairs' columns)
         shape       what the proof stream carries: per group (tuple(columns), tuple(point indices)), plain ints"""
 
-    def __init__(self, plan, in_domain, m=None):
+    def __init__(self, plan, in_domain, m=None, limits=PLAN_LIMITS):
         try:
             groups = [([int(c) for c in columns], [_limbs(z) for z in points]) for columns, points in plan]
         except (TypeError, ValueError):
             raise ValueError("an opening plan is a list of (columns, points) groups")
-        if not 1 <= len(groups) <= MAX_GROUPS:
-            raise ValueError("an opening plan has 1 .. %d groups (got %d)" % (MAX_GROUPS, len(groups)))
+        if not 1 <= len(groups) <= limits.groups:
+            raise ValueError("an opening plan has 1 .. %d groups (got %d)" % (limits.groups, len(groups)))
         self.points, self.groups, self.base = [], [], []
         seen, count = set(), 0
         for g, (columns, points) in enumerate(groups):
@@ -223,6 +243,8 @@ class OpeningPlan:
             if seen & set(columns):
                 raise ValueError("group %d: column %d lies in an earlier group too" % (g, min(seen & set(columns))))
             seen |= set(columns)
+            if len(columns) > limits.group_columns:
+                raise ValueError("group %d: at most %d columns in a group (got %d)" % (g, limits.group_columns, len(columns)))
             if not 1 <= len(points) <= MAX_POINTS_PER_LAUNCH or any(len(z) != 3 for z in points):
                 raise ValueError("group %d: 1 .. %d points of three limbs each" % (g, MAX_POINTS_PER_LAUNCH))
             if len(set(points)) != len(points):
@@ -239,12 +261,12 @@ class OpeningPlan:
         self.pairs = sum(len(indices) for _, indices in self.groups)
         if seen != set(range(self.m)) or (m is not None and self.m != m):
             raise ValueError("the groups must hold every column 0 .. %d exactly once" % ((self.m if m is None else m) - 1))
-        if self.m > MAX_COLUMNS:
-            raise ValueError("at most %d columns (got %d)" % (MAX_COLUMNS, self.m))
-        if len(self.points) > MAX_PLAN_POINTS:
-            raise ValueError("at most %d distinct points (got %d)" % (MAX_PLAN_POINTS, len(self.points)))
-        if self.pairs > MAX_PAIRS:
-            raise ValueError("at most %d (group, point) pairs (got %d)" % (MAX_PAIRS, self.pairs))
+        if self.m > limits.columns:
+            raise ValueError("at most %d columns (got %d)" % (limits.columns, self.m))
+        if len(self.points) > limits.points:
+            raise ValueError("at most %d distinct points (got %d)" % (limits.points, len(self.points)))
+        if self.pairs > limits.pairs:
+            raise ValueError("at most %d (group, point) pairs (got %d)" % (limits.pairs, self.pairs))
         self.shape = [(tuple(columns), tuple(indices)) for columns, indices in self.groups]
 
     def combined_values(self, values, lam):
@@ -383,12 +405,12 @@ class PolynomialCommitment:
         values = [[xf.from_limbs(v) for v in per_point] for per_point in raw]
         proof_stream.push(values)
         lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        self._prove_quotient(committed, self.quotient(committed, pts, raw, lam), proof_stream)
+        self._prove_quotient([committed], self.quotient(committed, pts, raw, lam), proof_stream)
         return values
 
-    def _prove_quotient(self, committed, g, proof_stream):
-        """what follows lambda in every opening: the root of the tree over g, the t consistency indices with their rows and openings of
-        g, then Fri.prove over g"""
+    def _prove_quotient(self, commitments, g, proof_stream):
+        """what follows lambda in every opening: the root of the tree over g, the t consistency indices with their rows (one row and
+        one path per commitment of the list, in its order) and openings of g, then Fri.prove over g"""
         xf, n, t, fri = self.xfield, self.n, self.fri.num_colinearity_tests, self.fri
         coset = fri.coset_leaves
         a = fri.folding_factor if coset else 1
@@ -401,9 +423,10 @@ class PolynomialCommitment:
         leaves = list(dict.fromkeys(i % q for i in indices))
         requests, spans = [], {}
         for i in rows:
-            reqs = committed.row_requests(i)
-            spans["row", i] = (len(requests), len(reqs))
-            requests += reqs
+            for r, committed in enumerate(commitments):
+                reqs = committed.row_requests(i)
+                spans["row", r, i] = (len(requests), len(reqs))
+                requests += reqs
         for c in leaves:
             spans["leaf", c] = (len(requests), a)
             requests += [(g.ptr + 8 * (c + j * q), 3, g.stride) for j in range(a)]
@@ -415,8 +438,9 @@ class PolynomialCommitment:
             return fetched[starts[first]:starts[first + count]]
         known = {}
         for i in indices:
-            proof_stream.push(self._row(committed, i, words(("row", i))))
-            proof_stream.push(committed.tree.open(i))
+            for r, committed in enumerate(commitments):
+                proof_stream.push(self._row(committed, i, words(("row", r, i))))
+                proof_stream.push(committed.tree.open(i))
             c = i % q
             if c not in known:
                 w = [int(v) for v in words(("leaf", c))]
@@ -462,10 +486,11 @@ class PolynomialCommitment:
         powers = [(1, 0, 0)]
         for _ in range(len(pts) * m):
             powers.append(xmul(powers[-1], lam))
-        return self._check_quotient(root, m, lambda i, row: self._quotient_at(i, row, pts, want, powers, m), proof_stream)
+        return self._check_quotient([(root, m)], lambda i, row: self._quotient_at(i, row, pts, want, powers, m), proof_stream)
 
-    def _check_quotient(self, root, m, quotient_at, proof_stream):
-        """what follows lambda in every opening, read back: quotient_at(i, row as limb triples) is g[i] as the statement has it"""
+    def _check_quotient(self, trees, quotient_at, proof_stream):
+        """what follows lambda in every opening, read back.  trees: (root, width) per commitment, in the order their rows were pushed;
+        quotient_at(i, the rows at x_i one behind the other, as limb triples) is g[i] as the statement has it"""
         n, t, fri = self.n, self.fri.num_colinearity_tests, self.fri
         is_element = lambda e: isinstance(e, ExtensionFieldElement)
         g_root = proof_stream.pull()
@@ -477,21 +502,24 @@ class PolynomialCommitment:
         a = fri.folding_factor if coset else 1
         q = n // a
         # a row has its extension columns first; how many there are is read off the first row and must hold for every row
-        shape = None
+        shapes = [None] * len(trees)
         for i in indices:
-            row = proof_stream.pull()
-            if not isinstance(row, tuple) or len(row) != m or not all(is_element(e) or isinstance(e, BaseFieldElement) for e in row):
-                print("opened row is not well formed")
-                return False
-            kinds = [is_element(e) for e in row]
-            if kinds != sorted(kinds, reverse=True) or (shape is not None and kinds != shape):
-                print("opened row is not well formed")
-                return False
-            shape = kinds
-            path = proof_stream.pull()
-            if not self._is_path(path, n) or not Merkle.verify(root, i, path, row):
-                print("merkle authentication path verification fails for an opened row")
-                return False
+            rows = []
+            for r, (root, m) in enumerate(trees):
+                row = proof_stream.pull()
+                if not isinstance(row, tuple) or len(row) != m or not all(is_element(e) or isinstance(e, BaseFieldElement) for e in row):
+                    print("opened row is not well formed")
+                    return False
+                kinds = [is_element(e) for e in row]
+                if kinds != sorted(kinds, reverse=True) or (shapes[r] is not None and kinds != shapes[r]):
+                    print("opened row is not well formed")
+                    return False
+                shapes[r] = kinds
+                path = proof_stream.pull()
+                if not self._is_path(path, n) or not Merkle.verify(root, i, path, row):
+                    print("merkle authentication path verification fails for an opened row")
+                    return False
+                rows += [_limbs(e) for e in row]
             leaf = proof_stream.pull()
             path = proof_stream.pull()
             c = i % q
@@ -503,7 +531,7 @@ class PolynomialCommitment:
                 print("merkle authentication path verification fails for the quotient")
                 return False
             opened = _limbs(leaf[i // q] if coset else leaf)
-            if opened != quotient_at(i, [_limbs(e) for e in row]):
+            if opened != quotient_at(i, rows):
                 print("quotient does not match the opened row")
                 return False
         if not fri.verify(proof_stream, g_root):
@@ -559,7 +587,16 @@ class PolynomialCommitment:
         plan = self.plan(plan, len(committed.polys))
         proof_stream.push([xf.from_limbs(z) for z in plan.points])
         proof_stream.push(plan.shape)
-        # one evaluation call per distinct point set: the coefficient columns of every group that is opened there
+        raw, values = self._plan_values(plan, lambda c: committed.polys[committed.order[c]])
+        proof_stream.push(values)
+        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
+        self._prove_quotient([committed], self.quotient_at(committed, plan, raw, lam), proof_stream)
+        return values
+
+    def _plan_values(self, plan, polynomial):
+        """the values a plan asks for, as limb triples and as elements, both [g][j][r]; polynomial(c): the coefficients behind column c.
+        One evaluation call per distinct point set: the coefficient columns of every group that is opened there"""
+        xf = self.xfield
         point_sets = list(dict.fromkeys(tuple(indices) for _, indices in plan.groups))
         requests, places = [], {}
         for point_set in point_sets:
@@ -567,7 +604,7 @@ class PolynomialCommitment:
             for g, (columns, indices) in enumerate(plan.groups):
                 if tuple(indices) == point_set:
                     for r, c in enumerate(columns):
-                        f = committed.polys[committed.order[c]]
+                        f = polynomial(c)
                         planes = [(f.ptr + 8 * l * f.stride, f.n) for l in range(3)] if isinstance(f, XArray) else [(f.ptr, f.n)]
                         places[g, r] = (len(requests), len(coefficient_columns), len(planes))
                         coefficient_columns += planes
@@ -581,11 +618,7 @@ class PolynomialCommitment:
                 for j in range(len(indices)):
                     v = [got[request][first + l][j] for l in range(planes)]
                     raw[g][j][r] = _combine_planes(v) if planes == 3 else v[0]
-        values = [[[xf.from_limbs(v) for v in per_point] for per_point in per_group] for per_group in raw]
-        proof_stream.push(values)
-        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        self._prove_quotient(committed, self.quotient_at(committed, plan, raw, lam), proof_stream)
-        return values
+        return raw, [[[xf.from_limbs(v) for v in per_point] for per_point in per_group] for per_group in raw]
 
     def verify_at(self, root, plan, values, proof_stream):
         """does the proof in `proof_stream` (read position right behind the commitment's root) show that the polynomials behind `root`
@@ -598,17 +631,22 @@ class PolynomialCommitment:
                 return self.verify_at(root, plan, values, proof_stream)
             finally:
                 leaf_pickle_source.reset(token)
-        is_element = lambda e: isinstance(e, ExtensionFieldElement)
         try:
             plan = self.plan(plan)
         except ValueError as e:
             print("plan cannot be opened: %s" % e)
             return False
+        return self._verify_plan([(root, plan.m)], plan, plan.shape, values, proof_stream)
+
+    def _verify_plan(self, trees, plan, shape, values, proof_stream):
+        """what verify_at and verify_rounds share: points, shape and values against the caller's, then the quotient.  trees: (root,
+        width) per commitment; shape: what the prover pushed behind the points"""
+        is_element = lambda e: isinstance(e, ExtensionFieldElement)
         pushed = proof_stream.pull()
         if not isinstance(pushed, list) or not all(is_element(z) for z in pushed) or [_limbs(z) for z in pushed] != plan.points:
             print("points differ from the caller's plan")
             return False
-        if proof_stream.pull() != plan.shape:
+        if proof_stream.pull() != shape:
             print("groups differ from the caller's plan")
             return False
         claimed = proof_stream.pull()
@@ -625,7 +663,7 @@ class PolynomialCommitment:
             return False
         lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
         combined, powers = plan.combined_values(want, lam)
-        return self._check_quotient(root, plan.m, lambda i, row: self._plan_quotient_at(i, row, plan, combined, powers), proof_stream)
+        return self._check_quotient(trees, lambda i, row: self._plan_quotient_at(i, row, plan, combined, powers), proof_stream)
 
     def _plan_quotient_at(self, i, row, plan, combined, powers):
         """g[i] from the row at x_i: sum_g sum_j (lambda^base[g][j] S_g - Y_{g,j}) / (x_i - z_{g,j})"""
@@ -639,3 +677,100 @@ class PolynomialCommitment:
             for p, b, y in zip(indices, base, ys):
                 g = xadd(g, xmul(xsub(xmul(powers[b], s), y), inverse[p]))
         return g
+
+    # ---------------------------------------------------------------------------------------------------------- openings across commitments
+    @staticmethod
+    def _widths(widths):
+        """the checked list of row widths of 1 .. 4 commitments (ValueError with the reason otherwise)"""
+        try:
+            widths = [int(w) for w in widths]
+        except (TypeError, ValueError):
+            raise ValueError("widths: one row width per commitment")
+        if not 1 <= len(widths) <= MAX_COMMITMENTS:
+            raise ValueError("1 .. %d commitments (got %d)" % (MAX_COMMITMENTS, len(widths)))
+        if not all(1 <= w <= MAX_COLUMNS for w in widths):
+            raise ValueError("a commitment has 1 .. %d columns (got %s)" % (MAX_COLUMNS, widths))
+        return widths
+
+    @staticmethod
+    def global_column(commitments, r, c):
+        """the column of an `open_rounds` plan that is row column c of commitments[r]: the columns of all commitments are numbered
+        through in the order of the list.  commitments: Commitments, or their row widths"""
+        widths = [w if isinstance(w, int) else len(w.polys) for w in commitments]
+        if not 0 <= r < len(widths) or not 0 <= c < widths[r]:
+            raise ValueError("commitment %d has no row column %d" % (r, c))
+        return sum(widths[:r]) + c
+
+    def rounds_plan(self, plan, widths):
+        """the checked OpeningPlan over the columns of commitments of these row widths (the wider limits: ROUNDS_LIMITS)"""
+        m = sum(widths)
+        if isinstance(plan, OpeningPlan):
+            if plan.m != m:
+                raise ValueError("the groups must hold every column 0 .. %d exactly once" % (m - 1))
+            return plan
+        return OpeningPlan(plan, self.in_domain, m, ROUNDS_LIMITS)
+
+    def quotient_rounds(self, commitments, plan, values, lam, launches=None):
+        """the DEEP quotient codeword (XArray) of a plan over the columns of several commitments: bfsr_deep_quotient_rounds, as many
+        launches as the plan needs into one output.  values[g][j][r]: limb triples; launches: a ctypes.c_uint32 that receives their number"""
+        n = self.n
+        where = [(committed, c) for committed in commitments for c in range(len(committed.polys))]
+        cols = (_lib.RowColumn * len(where))()
+        for at, column in enumerate(c for columns, _ in plan.groups for c in columns):      # (the kernel wants the columns in group order)
+            committed, c = where[column]
+            cols[at].d_values, cols[at].is_ext, cols[at].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
+        combined, _ = plan.combined_values(values, lam)
+        u32 = ctypes.c_uint32
+        g = XArray.empty(n, self.xfield)
+        _lib.check(_lib.load().bfsr_deep_quotient_rounds(
+            cols, len(where), n, n.bit_length() - 1, self.offset, self.omega,
+            (u32 * len(plan.groups))(*[len(columns) for columns, _ in plan.groups]), (u32 * len(plan.groups))(*[len(indices) for _, indices in plan.groups]),
+            len(plan.groups), _flat_points(plan.points), len(plan.points), (u32 * plan.pairs)(*[p for _, indices in plan.groups for p in indices]),
+            _flat_points([y for per_group in combined for y in per_group]), (_u64 * 3)(*lam), g.ptr, g.stride,
+            ctypes.byref(launches) if launches is not None else None, current_stream()))
+        return g
+
+    def open_rounds(self, commitments, plan, proof_stream):
+        """proves values of the polynomials of 1 .. 4 commitments of this PolynomialCommitment -- made at any moments of the same
+        transcript -- under ONE plan, one quotient and one low-degree test.  The plan's columns are the row columns of all commitments
+        numbered through (`global_column`); a group may hold columns of different commitments.  Returns values[g][j][r].  The plan is
+        checked before any GPU work (ValueError)."""
+        xf = self.xfield
+        commitments = list(commitments)
+        widths = self._widths([len(committed.polys) for committed in commitments])
+        plan = self.rounds_plan(plan, widths)
+        where = [(committed, c) for committed in commitments for c in range(len(committed.polys))]
+        proof_stream.push([xf.from_limbs(z) for z in plan.points])
+        proof_stream.push((tuple(widths), plan.shape))
+        raw, values = self._plan_values(plan, lambda column: where[column][0].polys[where[column][0].order[where[column][1]]])
+        proof_stream.push(values)
+        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
+        self._prove_quotient(commitments, self.quotient_rounds(commitments, plan, raw, lam), proof_stream)
+        return values
+
+    def verify_rounds(self, roots, widths, plan, values, proof_stream):
+        """does the proof in `proof_stream` (read position where `open_rounds` began to push) show that the polynomials behind `roots`
+        -- commitments of row widths `widths`, in the order `open_rounds` was given them -- take `values` (values[g][j][r]) under
+        `plan`?  The roots are the caller's: it has read each from the transcript where `commit` pushed it.  Host code only; one printed
+        line per refusal."""
+        from .merkle import leaf_pickle_source
+        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
+            token = leaf_pickle_source.set(proof_stream.pickle_of)
+            try:
+                return self.verify_rounds(roots, widths, plan, values, proof_stream)
+            finally:
+                leaf_pickle_source.reset(token)
+        try:
+            roots = list(roots)
+            widths = self._widths(widths)
+            if len(roots) != len(widths) or not all(isinstance(root, (bytes, bytearray)) for root in roots):
+                raise ValueError("one root and one width per commitment (got %d and %d)" % (len(roots), len(widths)))
+        except (TypeError, ValueError) as e:
+            print("commitments cannot be opened: %s" % e)
+            return False
+        try:
+            plan = self.rounds_plan(plan, widths)
+        except ValueError as e:
+            print("plan cannot be opened: %s" % e)
+            return False
+        return self._verify_plan(list(zip(roots, widths)), plan, (tuple(widths), plan.shape), values, proof_stream)

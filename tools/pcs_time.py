@@ -8,6 +8,9 @@ of the same shape, the median of --reps calls per line (ms):
     open            PolynomialCommitment.open as a whole (host clock, ends in the stream synchronise of Fri.prove's read-backs)
     combination     bfs_combination over the same 20 codewords as sources (what the quotient is compared with)
     extension       bfs_gl_ntt of the same 28 columns from 2^20 coefficients to the 2^22 coset (what the evaluation is compared with)
+    rounds          openings across commitments (rounds_leg): the STARK plan through bfsr_deep_quotient_rounds beside repeated measurements of
+                    bfsx_deep_quotient_groups; a 64-column plan over three commitments (two launches) against bfsx_deep_quotient_groups on
+                    its two halves; one open_rounds of the three commitments against three open_at (host clock, proof bytes)
 
 and the shader clock sampled under a loop of quotient launches.  The numbers of profiles/pcs.md come from one run of this.
 
@@ -131,6 +134,8 @@ def main():
         wall.append(1e3 * (time.perf_counter() - t))
     report["open_wall_ms"] = (round(statistics.median(wall), 3), round(min(wall), 3), round(max(wall), 3))
 
+    rounds_leg(report, pc, lib, args, committed, stark, stark_values, lam, rng, XF, P)
+
     # the shader clock half a second into a loop of quotient launches
     import bench
     stop = []
@@ -147,6 +152,90 @@ def main():
     worker.join()
     report["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(report), flush=True)
+
+
+def _wall(fn, reps):
+    fn()
+    wall = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        wall.append(1e3 * (time.perf_counter() - t))
+    return round(statistics.median(wall), 3), round(min(wall), 3), round(max(wall), 3)
+
+
+def rounds_leg(report, pc, lib, args, first, stark, stark_values, lam, rng, XF, P):
+    """openings across commitments (PolynomialCommitment.open_rounds, bfsr_deep_quotient_rounds):
+    (a) the STARK plan above -- one launch -- through the new entry, beside two more measurements of bfsx_deep_quotient_groups (its spread);
+    (b) 64 columns of three commitments in 8 groups of 8, two launches, against bfsx_deep_quotient_groups on the two halves;
+    (c) one open_rounds of the three commitments against three open_at, in time and proof bytes"""
+    N, d, reps = 1 << args.log_n, (1 << args.log_n) // EXPANSION, args.reps
+    u32 = ctypes.c_uint32
+    launches = u32(0)
+    one = pc.rounds_plan(stark, [N_BASE + N_EXT])
+    report["rounds_stark_plan_ms"] = timed(lambda: pc.quotient_rounds([first], one, stark_values, lam, launches), reps)
+    assert launches.value == 1
+    report["rounds_stark_plan_groups_entry_ms"] = [timed(lambda: pc.quotient_at(first, stark, stark_values, lam), reps) for _ in range(2)]
+    report["rounds_stark_plan_again_ms"] = timed(lambda: pc.quotient_rounds([first], one, stark_values, lam, launches), reps)
+
+    # two more commitments: 4 extension + 18 base polynomials, and 22 base polynomials: 20 + 22 + 22 = 64 columns
+    shapes = [(4, 18), (0, 22)]
+    commitments, ps = [first], sb.ProofStream()
+    ps.push(first.root())
+    for n_ext, n_base in shapes:
+        coeffs = DeviceBuffer.from_numpy(rng.integers(0, P, size=(3 * n_ext + n_base) * d, dtype=np.uint64))
+        polys = [sb.XArray(_view(coeffs, 3 * e * d, 3 * d), d, XF) for e in range(n_ext)]
+        polys += [sb.BaseArray(_view(coeffs, (3 * n_ext + b) * d, d), d) for b in range(n_base)]
+        commitments.append(pc.commit(polys, ps))
+    widths = [len(c.polys) for c in commitments]
+    assert sum(widths) == 64
+    z = tuple(int(v) for v in rng.integers(1, P, size=3, dtype=np.uint64))
+    nexts = [tuple(v * pow(pc.omega, 1 << (3 + i), P) % P for v in z) for i in range(4)]
+    raw = [(list(range(8 * g, 8 * g + 8)), [z, nexts[g % 4]]) for g in range(8)]
+    plan = pc.rounds_plan(raw, widths)
+    values = [[[(1 + j, 2 + r, 3) for r in range(8)] for j in range(2)] for _ in range(8)]
+    report["rounds_64_columns_ms"] = timed(lambda: pc.quotient_rounds(commitments, plan, values, lam, launches), reps)
+    assert launches.value == 2
+    where = [(c, k) for c in commitments for k in range(len(c.polys))]
+
+    def half(first_group, g):
+        """bfsx_deep_quotient_groups over four of the eight groups (32 columns, one launch)"""
+        part = pc.plan([(list(range(8 * k, 8 * k + 8)), points) for k, (_, points) in enumerate(raw[first_group:first_group + 4])], 32)
+        cols = (_lib.RowColumn * 32)()
+        for at in range(32):
+            c, k = where[8 * first_group + at]
+            cols[at].d_values, cols[at].is_ext, cols[at].field_id = c.column_ptr(k), int(k < c.n_ext), 1
+        combined, _ = part.combined_values(values[:4], lam)
+        _lib.check(lib.bfsx_deep_quotient_groups(
+            cols, 32, N, args.log_n, pc.offset, pc.omega, (u32 * 4)(*[8] * 4), (u32 * 4)(*[2] * 4), 4, pcs._flat_points(part.points), len(part.points),
+            (u32 * part.pairs)(*[p for _, indices in part.groups for p in indices]), pcs._flat_points([y for per_group in combined for y in per_group]),
+            (u64 * 3)(*lam), g.ptr, g.stride, current_stream()))
+    g_half = sb.XArray.empty(N, XF)
+    report["rounds_64_columns_halves_ms"] = [timed(lambda: half(0, g_half), reps), timed(lambda: half(4, g_half), reps)]
+
+    # (c) one proof against three
+    sizes = {}
+
+    def one_proof():
+        stream = sb.ProofStream()
+        pc.open_rounds(commitments, plan, stream)
+        synchronize()
+        sizes["open_rounds"] = len(stream.serialize())
+
+    def three_proofs():
+        total = 0
+        for c in commitments:
+            m = len(c.polys)
+            own = [(list(range(first_column, min(first_column + 8, m))), [z, nexts[g % 4]]) for g, first_column in enumerate(range(0, m, 8))]
+            stream = sb.ProofStream()
+            pc.open_at(c, own, stream)
+            synchronize()
+            total += len(stream.serialize())
+        sizes["open_at_three"] = total
+    report["open_rounds_wall_ms"] = _wall(one_proof, reps)
+    report["open_at_three_wall_ms"] = _wall(three_proofs, reps)
+    report["open_rounds_again_wall_ms"] = _wall(one_proof, reps)
+    report["proof_bytes"] = sizes
 
 
 def _view(buf, offset, count):

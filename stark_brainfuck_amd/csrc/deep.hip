@@ -5,6 +5,15 @@
 // quotient of groups of columns that are opened at different points, in one launch.
 // include/bfstark_rounds.h adds the quotient of a plan over the columns of several commitments: the same kernel, launched as often as
 // the plan needs (deep_core.hpp: deep_rounds_split), every launch after the first accumulating into the output.
+//
+// The host side is shared as far as the kernels allow.  Both evaluation entries are eval_launches behind their own column checks.  All
+// three quotient entries ask the same of domain and codewords (check_domain, check_codewords).  Both PLAN entries are one driver,
+// deep_quotient_plan, called with the entry's name and limits: deep_core.hpp's one check of a plan, its split, and per launch its one
+// filling of a DeepGroupsArgs.  So a plan within bfsx_deep_quotient_groups' limits is always exactly one launch (every bound of the split
+// is one of them), and a launch gets the points its pairs name in order of first appearance: points in another order, or a point no pair
+// uses, select the instantiation for the points in use and change no word (field arithmetic is exact); an unused point is still
+// checked for being reduced.  bfs_deep_quotient keeps its own argument block and kernel: one group is 1.11-1.17x cheaper there
+// (profiles/pcs.md).
 // No entry synchronises, copies from the host or allocates outside the stream-ordered pool: the points, weights, constants, column
 // tables and plans of a call travel as kernel arguments.
 #include "../../include/bfstark_ext.h"
@@ -136,28 +145,6 @@ __global__ void __launch_bounds__(DEEP_G_T) deep_groups_kernel(DeepGroupsArgs a,
     }
 }
 
-template <class Fn>
-static int with_point_count(u32 k, Fn&& fn) {
-    switch (k) {
-    case 1: return fn(std::integral_constant<int, 1>());
-    case 2: return fn(std::integral_constant<int, 2>());
-    case 3: return fn(std::integral_constant<int, 3>());
-    case 4: return fn(std::integral_constant<int, 4>());
-    default: set_error("the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG;
-    }
-}
-
-template <class Fn>
-static int with_distinct_points(u32 n_points, Fn&& fn) {
-    switch (n_points) {
-    case 5: return fn(std::integral_constant<int, 5>());
-    case 6: return fn(std::integral_constant<int, 6>());
-    case 7: return fn(std::integral_constant<int, 7>());
-    case 8: return fn(std::integral_constant<int, 8>());
-    default: return with_point_count(n_points, fn);
-    }
-}
-
 static bool canonical3(const u64* w) { return w[0] < GL_P && w[1] < GL_P && w[2] < GL_P; }
 
 static bool overlaps(const void* a, u64 a_bytes, const void* b, u64 b_bytes) {
@@ -165,260 +152,82 @@ static bool overlaps(const void* a, u64 a_bytes, const void* b, u64 b_bytes) {
     return x < y + b_bytes && y < x + a_bytes;
 }
 
-}  // namespace bfs
-
-using namespace bfs;
-
-extern "C" int bfs_poly_eval_points(const uint64_t* d_coeffs, uint64_t n_coeffs, uint64_t in_stride, uint32_t batch, const uint64_t* h_points,
-                                    uint32_t k, uint64_t* d_out, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!d_coeffs || !h_points || !d_out) { set_error("bfs_poly_eval_points: null argument"); return BFS_ERR_BAD_ARG; }
-    if (n_coeffs < 1 || n_coeffs > (1ull << 24)) { set_error("bfs_poly_eval_points: n_coeffs must be 1..2^24 (got %llu)", (unsigned long long)n_coeffs); return BFS_ERR_BAD_ARG; }
-    if (batch < 1 || batch > 65535) { set_error("bfs_poly_eval_points: batch must be 1..65535 (got %u)", batch); return BFS_ERR_BAD_ARG; }
-    if (batch > 1 && in_stride < n_coeffs) { set_error("bfs_poly_eval_points: in_stride < n_coeffs"); return BFS_ERR_BAD_ARG; }
-    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfs_poly_eval_points: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
+// what the two evaluation entries share once their columns are checked: the points, the scratch block (the table, then 3 k words per
+// partial sum of a point: `sums` = columns * workgroups of the longest), the table's launch, the entry's own pair of launches
+// -- partial(K, table, partial sums), combine(table, partial sums) -- and the release
+template <class Partial, class Combine>
+static int eval_launches(const char* entry, const u64* h_points, u32 k, u64 sums, hipStream_t stream, Partial&& partial, Combine&& combine) {
+    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("%s: the number of points must be 1..%u (got %u)", entry, DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
     DeepPoints pts{};
     for (u32 j = 0; j < k; ++j) {
-        if (!canonical3(h_points + 3 * j)) { set_error("bfs_poly_eval_points: point %u is not reduced", j); return BFS_ERR_BAD_ARG; }
-        pts.z[j] = Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}};
+        if (!canonical3(h_points + 3 * j)) { set_error("%s: point %u is not reduced", entry, j); return BFS_ERR_BAD_ARG; }
+        pts.z[j] = xfe_load3(h_points + 3 * j);
     }
-    const u32 blocks = (u32)((n_coeffs + DEEP_EVAL_BLOCK - 1) / DEEP_EVAL_BLOCK);
-    const u64 results = (u64)batch * k;
-    if (overlaps(d_out, results * 24, d_coeffs, ((u64)(batch - 1) * in_stride + n_coeffs) * 8)) { set_error("bfs_poly_eval_points: d_out overlaps the coefficients"); return BFS_ERR_BAD_ARG; }
     void* scratch = nullptr;
-    BFS_TRY(device_alloc((DEEP_EVAL_TABLE_WORDS + results * blocks * 3) * sizeof(u64), stream, &scratch));
+    BFS_TRY(device_alloc((DEEP_EVAL_TABLE_WORDS + sums * k * 3) * sizeof(u64), stream, &scratch));
     u64* table = (u64*)scratch;
-    u64* partial = table + DEEP_EVAL_TABLE_WORDS;
+    u64* sums_at = table + DEEP_EVAL_TABLE_WORDS;
     hipLaunchKernelGGL(deep_eval_table_kernel, dim3(k), dim3(DEEP_EVAL_T), 0, stream, pts, table);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        (void)with_point_count(k, [&](auto kk) -> int {
-            hipLaunchKernelGGL((deep_eval_partial_kernel<decltype(kk)::value>), dim3(blocks, batch), dim3(DEEP_EVAL_T), 0, stream, d_coeffs, n_coeffs, in_stride,
-                               (const u64*)table, partial);
-            return BFS_OK;
-        });
+        (void)deep_with_count<DEEP_MAX_POINTS>(k, [&](auto kk) -> int { partial(kk, (const u64*)table, sums_at); return BFS_OK; });
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(deep_eval_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, (const u64*)partial, blocks, k, (const u64*)table, d_out);
+        combine((const u64*)table, (const u64*)sums_at);
         e = hipGetLastError();
     }
     (void)device_release(scratch, stream);                // stream-ordered: the launches above are ahead of whoever gets the block next
-    if (e != hipSuccess) { set_error("bfs_poly_eval_points: %s", hipGetErrorString(e)); return BFS_ERR_HIP; }
+    if (e != hipSuccess) { set_error("%s: %s", entry, hipGetErrorString(e)); return BFS_ERR_HIP; }
     return BFS_OK;
 }
 
-extern "C" int bfs_deep_quotient(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
-                                 const uint64_t* h_points, const uint64_t* h_values, uint32_t k, const uint64_t h_lambda[3], uint64_t* d_out,
-                                 uint64_t out_stride, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!h_columns || !h_points || !h_values || !h_lambda || !d_out) { set_error("bfs_deep_quotient: null argument"); return BFS_ERR_BAD_ARG; }
-    if (m < 1 || m > DEEP_MAX_COLUMNS) { set_error("bfs_deep_quotient: 1..%u codewords (got %u)", DEEP_MAX_COLUMNS, m); return BFS_ERR_BAD_ARG; }
-    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfs_deep_quotient: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
-    if (log_n < 1 || log_n > 24) { set_error("bfs_deep_quotient: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
+// what the three quotient entries ask of the domain and of lambda
+static int check_domain(const char* entry, u32 log_n, u64 limb_stride, u64 out_stride, u64 offset, u64 omega, const u64* h_lambda) {
+    if (log_n < 1 || log_n > 24) { set_error("%s: log_n must be 1..24 (got %u)", entry, log_n); return BFS_ERR_BAD_ARG; }
     const u64 n = 1ull << log_n;
-    if (limb_stride < n || out_stride < n) { set_error("bfs_deep_quotient: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
-    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfs_deep_quotient: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
+    if (limb_stride < n || out_stride < n) { set_error("%s: a stride shorter than the domain", entry); return BFS_ERR_BAD_ARG; }
+    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("%s: offset or omega is not a reduced non-zero value", entry); return BFS_ERR_BAD_ARG; }
     if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
-    if (!canonical3(h_lambda)) { set_error("bfs_deep_quotient: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
-    DeepQuotientArgs a{};
-    a.m = m; a.limb_stride = limb_stride; a.n = n; a.offset = offset;
-    const Xfe lambda{{h_lambda[0], h_lambda[1], h_lambda[2]}};
-    const u64 out_bytes = (2 * out_stride + n) * 8;
-    Xfe power{{1, 0, 0}};                                 // lambda^p
+    if (!canonical3(h_lambda)) { set_error("%s: lambda is not reduced", entry); return BFS_ERR_BAD_ARG; }
+    return BFS_OK;
+}
+
+// ... and of the codewords: none null, none under the output
+static int check_codewords(const char* entry, const bfs_row_column* h_columns, u32 m, u64 limb_stride, u64 n, const u64* d_out, u64 out_stride) {
     for (u32 p = 0; p < m; ++p) {
         const bfs_row_column& c = h_columns[p];
-        if (!c.d_values) { set_error("bfs_deep_quotient: codeword %u is null", p); return BFS_ERR_BAD_ARG; }
-        if (overlaps(d_out, out_bytes, c.d_values, (c.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfs_deep_quotient: d_out overlaps codeword %u", p); return BFS_ERR_BAD_ARG; }
-        a.col[p] = c.d_values;
-        if (c.is_ext) a.ext_mask |= 1u << p;
-        lazy_weight_matrix(power, a.weight[p]);
-        power = xfe_mul(power, lambda);
+        if (!c.d_values) { set_error("%s: codeword %u is null", entry, p); return BFS_ERR_BAD_ARG; }
+        if (overlaps(d_out, (2 * out_stride + n) * 8, c.d_values, (c.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("%s: d_out overlaps codeword %u", entry, p); return BFS_ERR_BAD_ARG; }
     }
-    Xfe scale{{1, 0, 0}};                                 // lambda^(j m)
-    for (u32 j = 0; j < k; ++j) {
-        if (!canonical3(h_points + 3 * j) || !canonical3(h_values + 3 * j)) { set_error("bfs_deep_quotient: point or value %u is not reduced", j); return BFS_ERR_BAD_ARG; }
-        deep_point_consts(a.pt[j], Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}}, scale,
-                          Xfe{{h_values[3 * j], h_values[3 * j + 1], h_values[3 * j + 2]}});
-        scale = xfe_mul(scale, power);
-    }
-    BFS_TRY(ntt_power_tables(omega, log_n, &a.w_lo, &a.w_hi, &a.lo_bits));
-    const u32 grid = (u32)((n + DEEP_Q_T * DEEP_Q_E - 1) / (DEEP_Q_T * DEEP_Q_E));
-    BFS_TRY(with_point_count(k, [&](auto kk) -> int {
-        hipLaunchKernelGGL((deep_quotient_kernel<decltype(kk)::value>), dim3(grid), dim3(DEEP_Q_T), 0, stream, a, d_out, out_stride);
-        return BFS_OK;
-    }));
-    BFS_HIP(hipGetLastError());
     return BFS_OK;
 }
 
-extern "C" int bfsx_poly_eval_columns(const bfsx_eval_column* h_columns, uint32_t count, const uint64_t* h_points, uint32_t k, uint64_t* d_out,
-                                      void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!h_columns || !h_points || !d_out) { set_error("bfsx_poly_eval_columns: null argument"); return BFS_ERR_BAD_ARG; }
-    if (count < 1 || count > DEEP_EVAL_MAX_COLUMNS) { set_error("bfsx_poly_eval_columns: 1..%u columns (got %u)", DEEP_EVAL_MAX_COLUMNS, count); return BFS_ERR_BAD_ARG; }
-    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfsx_poly_eval_columns: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
-    DeepPoints pts{};
-    for (u32 j = 0; j < k; ++j) {
-        if (!canonical3(h_points + 3 * j)) { set_error("bfsx_poly_eval_columns: point %u is not reduced", j); return BFS_ERR_BAD_ARG; }
-        pts.z[j] = Xfe{{h_points[3 * j], h_points[3 * j + 1], h_points[3 * j + 2]}};
-    }
-    const u64 results = (u64)count * k;
-    DeepEvalColumns cols{};
-    u32 row_blocks = 0;
-    for (u32 b = 0; b < count; ++b) {
-        const bfsx_eval_column& c = h_columns[b];
-        if (!c.d_coeffs) { set_error("bfsx_poly_eval_columns: column %u is null", b); return BFS_ERR_BAD_ARG; }
-        if (c.n_coeffs < 1 || c.n_coeffs > (1ull << 24)) { set_error("bfsx_poly_eval_columns: column %u: n_coeffs must be 1..2^24 (got %llu)", b, (unsigned long long)c.n_coeffs); return BFS_ERR_BAD_ARG; }
-        if (overlaps(d_out, results * 24, c.d_coeffs, c.n_coeffs * 8)) { set_error("bfsx_poly_eval_columns: d_out overlaps column %u", b); return BFS_ERR_BAD_ARG; }
-        cols.col[b] = c.d_coeffs;
-        cols.n[b] = (u32)c.n_coeffs;
-        if (deep_eval_blocks(c.n_coeffs) > row_blocks) row_blocks = deep_eval_blocks(c.n_coeffs);
-    }
-    void* scratch = nullptr;
-    BFS_TRY(device_alloc((DEEP_EVAL_TABLE_WORDS + results * row_blocks * 3) * sizeof(u64), stream, &scratch));
-    u64* table = (u64*)scratch;
-    u64* partial = table + DEEP_EVAL_TABLE_WORDS;
-    hipLaunchKernelGGL(deep_eval_table_kernel, dim3(k), dim3(DEEP_EVAL_T), 0, stream, pts, table);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        (void)with_point_count(k, [&](auto kk) -> int {
-            hipLaunchKernelGGL((deep_eval_columns_partial_kernel<decltype(kk)::value>), dim3(row_blocks, count), dim3(DEEP_EVAL_T), 0, stream, cols,
-                               (const u64*)table, partial);
-            return BFS_OK;
-        });
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(deep_eval_columns_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, cols, (const u64*)partial, row_blocks, k,
-                           (const u64*)table, d_out);
-        e = hipGetLastError();
-    }
-    (void)device_release(scratch, stream);                // stream-ordered: the launches above are ahead of whoever gets the block next
-    if (e != hipSuccess) { set_error("bfsx_poly_eval_columns: %s", hipGetErrorString(e)); return BFS_ERR_HIP; }
-    return BFS_OK;
-}
-
-extern "C" int bfsx_deep_quotient_groups(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
-                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
-                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
-                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// THE driver of both plan entries: the plan against the entry's limits (deep_plan_check), the domain, the words, the codewords; then the
+// split into launches (deep_rounds_split: always one launch within DEEP_G_LIMITS) and per launch deep_rounds_args and the kernel
+static int deep_quotient_plan(const char* entry, const DeepPlanLimits& limits, const bfs_row_column* h_columns, u32 m, u64 limb_stride, u32 log_n,
+                              u64 offset, u64 omega, const u32* h_group_columns, const u32* h_group_pairs, u32 n_groups, const u64* h_points,
+                              u32 n_points, const u32* h_pair_point, const u64* h_pair_values, const u64* h_lambda, u64* d_out, u64 out_stride,
+                              u32* h_launches, hipStream_t stream) {
     if (!h_columns || !h_group_columns || !h_group_pairs || !h_points || !h_pair_point || !h_pair_values || !h_lambda || !d_out) {
-        set_error("bfsx_deep_quotient_groups: null argument"); return BFS_ERR_BAD_ARG;
+        set_error("%s: null argument", entry); return BFS_ERR_BAD_ARG;
     }
-    if (m < 1 || m > DEEP_MAX_COLUMNS) { set_error("bfsx_deep_quotient_groups: 1..%u codewords (got %u)", DEEP_MAX_COLUMNS, m); return BFS_ERR_BAD_ARG; }
-    if (n_groups < 1 || n_groups > DEEP_G_GROUPS) { set_error("bfsx_deep_quotient_groups: 1..%u groups (got %u)", DEEP_G_GROUPS, n_groups); return BFS_ERR_BAD_ARG; }
-    if (n_points < 1 || n_points > DEEP_G_POINTS) { set_error("bfsx_deep_quotient_groups: 1..%u distinct points (got %u)", DEEP_G_POINTS, n_points); return BFS_ERR_BAD_ARG; }
-    if (log_n < 1 || log_n > 24) { set_error("bfsx_deep_quotient_groups: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
+    char why[96];
+    if (!deep_plan_check(limits, m, h_group_columns, h_group_pairs, n_groups, n_points, h_pair_point, why)) { set_error("%s: %s", entry, why); return BFS_ERR_BAD_ARG; }
+    BFS_TRY(check_domain(entry, log_n, limb_stride, out_stride, offset, omega, h_lambda));
     const u64 n = 1ull << log_n;
-    if (limb_stride < n || out_stride < n) { set_error("bfsx_deep_quotient_groups: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
-    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfsx_deep_quotient_groups: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
-    if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
-    if (!canonical3(h_lambda)) { set_error("bfsx_deep_quotient_groups: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
-    u32 columns = 0, pairs = 0;
-    for (u32 g = 0; g < n_groups; ++g) {
-        if (h_group_columns[g] < 1 || h_group_columns[g] > m - columns) { set_error("bfsx_deep_quotient_groups: group %u: an empty group, or more columns than there are", g); return BFS_ERR_BAD_ARG; }
-        if (h_group_pairs[g] < 1 || h_group_pairs[g] > DEEP_MAX_POINTS) { set_error("bfsx_deep_quotient_groups: group %u: 1..%u points (got %u)", g, DEEP_MAX_POINTS, h_group_pairs[g]); return BFS_ERR_BAD_ARG; }
-        columns += h_group_columns[g];
-        pairs += h_group_pairs[g];
+    for (u32 p = 0; p < n_points; ++p) {                  // (every point of the plan, whether a pair names it or not)
+        if (!canonical3(h_points + 3 * p)) { set_error("%s: point %u is not reduced", entry, p); return BFS_ERR_BAD_ARG; }
     }
-    if (columns != m) { set_error("bfsx_deep_quotient_groups: the groups hold %u columns, not %u", columns, m); return BFS_ERR_BAD_ARG; }
-    if (pairs > DEEP_G_PAIRS) { set_error("bfsx_deep_quotient_groups: at most %u (group, point) pairs (got %u)", DEEP_G_PAIRS, pairs); return BFS_ERR_BAD_ARG; }
-    DeepGroupsArgs a{};
-    a.n_groups = n_groups; a.limb_stride = limb_stride; a.n = n; a.offset = offset;
-    for (u32 p = 0; p < n_points; ++p) {
-        if (!canonical3(h_points + 3 * p)) { set_error("bfsx_deep_quotient_groups: point %u is not reduced", p); return BFS_ERR_BAD_ARG; }
-        deep_group_point(a.pt[p], xfe_load3(h_points + 3 * p));
+    u32 pairs = 0;
+    for (u32 g = 0; g < n_groups; ++g) pairs += h_group_pairs[g];
+    for (u32 q = 0; q < pairs; ++q) {
+        if (!canonical3(h_pair_values + 3 * q)) { set_error("%s: value %u is not reduced", entry, q); return BFS_ERR_BAD_ARG; }
     }
-    const Xfe lambda = xfe_load3(h_lambda);
-    const u64 out_bytes = (2 * out_stride + n) * 8;
-    u32 c = 0, q = 0;
-    Xfe scale{{1, 0, 0}};                                 // lambda^base of the next pair
-    for (u32 g = 0; g < n_groups; ++g) {
-        Xfe power{{1, 0, 0}};                             // lambda^r
-        for (u32 r = 0; r < h_group_columns[g]; ++r, ++c) {
-            const bfs_row_column& col = h_columns[c];
-            if (!col.d_values) { set_error("bfsx_deep_quotient_groups: codeword %u is null", c); return BFS_ERR_BAD_ARG; }
-            if (overlaps(d_out, out_bytes, col.d_values, (col.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfsx_deep_quotient_groups: d_out overlaps codeword %u", c); return BFS_ERR_BAD_ARG; }
-            a.col[c] = col.d_values;
-            if (col.is_ext) a.ext_mask |= 1u << c;
-            lazy_weight_matrix(power, a.weight[c]);
-            power = xfe_mul(power, lambda);
-        }
-        u32 seen = 0;
-        for (u32 j = 0; j < h_group_pairs[g]; ++j, ++q) {
-            const u32 point = h_pair_point[q];
-            if (point >= n_points) { set_error("bfsx_deep_quotient_groups: pair %u names point %u of %u", q, point, n_points); return BFS_ERR_BAD_ARG; }
-            if ((seen >> point) & 1) { set_error("bfsx_deep_quotient_groups: group %u opens point %u twice", g, point); return BFS_ERR_BAD_ARG; }
-            seen |= 1u << point;
-            if (!canonical3(h_pair_values + 3 * q)) { set_error("bfsx_deep_quotient_groups: value %u is not reduced", q); return BFS_ERR_BAD_ARG; }
-            DeepGroupPair& pr = a.pair[q];
-            pr.scale = scale; pr.y = xfe_load3(h_pair_values + 3 * q); pr.point = point;
-            pr.unit = scale.c[0] == 1 && scale.c[1] == 0 && scale.c[2] == 0;
-            scale = xfe_mul(scale, power);                // power = lambda^|columns_g| here
-        }
-        a.col_end[g] = c; a.pair_end[g] = q;
-    }
-    BFS_TRY(ntt_power_tables(omega, log_n, &a.w_lo, &a.w_hi, &a.lo_bits));
-    const u64 share = (u64)DEEP_G_T * deep_groups_e(n_points);
-    const u32 grid = (u32)((n + share - 1) / share);
-    BFS_TRY(with_distinct_points(n_points, [&](auto np) -> int {
-        hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, false>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
-        return BFS_OK;
-    }));
-    BFS_HIP(hipGetLastError());
-    return BFS_OK;
-}
-
-extern "C" int bfsr_deep_quotient_rounds(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
-                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
-                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
-                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, uint32_t* h_launches, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!h_columns || !h_group_columns || !h_group_pairs || !h_points || !h_pair_point || !h_pair_values || !h_lambda || !d_out) {
-        set_error("bfsr_deep_quotient_rounds: null argument"); return BFS_ERR_BAD_ARG;
-    }
-    if (m < 1 || m > DEEP_R_COLUMNS) { set_error("bfsr_deep_quotient_rounds: 1..%u codewords (got %u)", DEEP_R_COLUMNS, m); return BFS_ERR_BAD_ARG; }
-    if (n_groups < 1 || n_groups > DEEP_R_GROUPS) { set_error("bfsr_deep_quotient_rounds: 1..%u groups (got %u)", DEEP_R_GROUPS, n_groups); return BFS_ERR_BAD_ARG; }
-    if (n_points < 1 || n_points > DEEP_R_POINTS) { set_error("bfsr_deep_quotient_rounds: 1..%u distinct points (got %u)", DEEP_R_POINTS, n_points); return BFS_ERR_BAD_ARG; }
-    if (log_n < 1 || log_n > 24) { set_error("bfsr_deep_quotient_rounds: log_n must be 1..24 (got %u)", log_n); return BFS_ERR_BAD_ARG; }
-    const u64 n = 1ull << log_n;
-    if (limb_stride < n || out_stride < n) { set_error("bfsr_deep_quotient_rounds: a stride shorter than the domain"); return BFS_ERR_BAD_ARG; }
-    if (offset == 0 || offset >= GL_P || omega >= GL_P) { set_error("bfsr_deep_quotient_rounds: offset or omega is not a reduced non-zero value"); return BFS_ERR_BAD_ARG; }
-    if (gl_pow(omega, n) != 1 || gl_pow(omega, n / 2) == 1) { set_error("omega does not have the right order"); return BFS_ERR_NOT_ROOT; }
-    if (!canonical3(h_lambda)) { set_error("bfsr_deep_quotient_rounds: lambda is not reduced"); return BFS_ERR_BAD_ARG; }
-    u32 columns = 0, pairs = 0;
-    for (u32 g = 0; g < n_groups; ++g) {
-        if (h_group_columns[g] < 1 || h_group_columns[g] > m - columns) { set_error("bfsr_deep_quotient_rounds: group %u: an empty group, or more columns than there are", g); return BFS_ERR_BAD_ARG; }
-        if (h_group_columns[g] > DEEP_MAX_COLUMNS) { set_error("bfsr_deep_quotient_rounds: group %u: at most %u columns in a group (got %u)", g, DEEP_MAX_COLUMNS, h_group_columns[g]); return BFS_ERR_BAD_ARG; }
-        if (h_group_pairs[g] < 1 || h_group_pairs[g] > DEEP_MAX_POINTS) { set_error("bfsr_deep_quotient_rounds: group %u: 1..%u points (got %u)", g, DEEP_MAX_POINTS, h_group_pairs[g]); return BFS_ERR_BAD_ARG; }
-        if (pairs + h_group_pairs[g] > DEEP_R_PAIRS) { set_error("bfsr_deep_quotient_rounds: more than %u (group, point) pairs", DEEP_R_PAIRS); return BFS_ERR_BAD_ARG; }
-        u32 seen = 0;
-        for (u32 j = 0; j < h_group_pairs[g]; ++j) {
-            const u32 q = pairs + j, point = h_pair_point[q];
-            if (point >= n_points) { set_error("bfsr_deep_quotient_rounds: pair %u names point %u of %u", q, point, n_points); return BFS_ERR_BAD_ARG; }
-            if ((seen >> point) & 1) { set_error("bfsr_deep_quotient_rounds: group %u opens point %u twice", g, point); return BFS_ERR_BAD_ARG; }
-            seen |= 1u << point;
-            if (!canonical3(h_pair_values + 3 * q)) { set_error("bfsr_deep_quotient_rounds: value %u is not reduced", q); return BFS_ERR_BAD_ARG; }
-        }
-        columns += h_group_columns[g];
-        pairs += h_group_pairs[g];
-    }
-    if (columns != m) { set_error("bfsr_deep_quotient_rounds: the groups hold %u columns, not %u", columns, m); return BFS_ERR_BAD_ARG; }
-    for (u32 p = 0; p < n_points; ++p) {
-        if (!canonical3(h_points + 3 * p)) { set_error("bfsr_deep_quotient_rounds: point %u is not reduced", p); return BFS_ERR_BAD_ARG; }
-    }
-    const u64 out_bytes = (2 * out_stride + n) * 8;
+    BFS_TRY(check_codewords(entry, h_columns, m, limb_stride, n, d_out, out_stride));
     const u64* col[DEEP_R_COLUMNS];
     int is_ext[DEEP_R_COLUMNS];
-    for (u32 c = 0; c < m; ++c) {
-        const bfs_row_column& column = h_columns[c];
-        if (!column.d_values) { set_error("bfsr_deep_quotient_rounds: codeword %u is null", c); return BFS_ERR_BAD_ARG; }
-        if (overlaps(d_out, out_bytes, column.d_values, (column.is_ext ? 2 * limb_stride + n : n) * 8)) { set_error("bfsr_deep_quotient_rounds: d_out overlaps codeword %u", c); return BFS_ERR_BAD_ARG; }
-        col[c] = column.d_values;
-        is_ext[c] = column.is_ext != 0;
-    }
+    for (u32 c = 0; c < m; ++c) { col[c] = h_columns[c].d_values; is_ext[c] = h_columns[c].is_ext != 0; }
     DeepRoundsLaunch launches[DEEP_R_GROUPS];
     const u32 count = deep_rounds_split(h_group_columns, h_group_pairs, n_groups, h_pair_point, launches);
     if (h_launches) *h_launches = count;
@@ -432,13 +241,116 @@ extern "C" int bfsr_deep_quotient_rounds(const bfs_row_column* h_columns, uint32
         deep_rounds_args(a, launches[l], col, is_ext, h_group_columns, h_group_pairs, h_points, h_pair_point, h_pair_values, lambda, scale);
         const u64 share = (u64)DEEP_G_T * deep_groups_e(launches[l].n_points);
         const u32 grid = (u32)((n + share - 1) / share);
-        BFS_TRY(with_distinct_points(launches[l].n_points, [&](auto np) -> int {
+        (void)deep_with_count<DEEP_G_POINTS>(launches[l].n_points, [&](auto np) -> int {
             // the first launch writes d_out and never reads it; every later one starts from what the one before left there
             if (l == 0) hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, false>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
             else hipLaunchKernelGGL((deep_groups_kernel<decltype(np)::value, true>), dim3(grid), dim3(DEEP_G_T), 0, stream, a, d_out, out_stride);
             return BFS_OK;
-        }));
+        });
         BFS_HIP(hipGetLastError());
     }
     return BFS_OK;
+}
+
+}  // namespace bfs
+
+using namespace bfs;
+
+extern "C" int bfs_poly_eval_points(const uint64_t* d_coeffs, uint64_t n_coeffs, uint64_t in_stride, uint32_t batch, const uint64_t* h_points,
+                                    uint32_t k, uint64_t* d_out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_coeffs || !h_points || !d_out) { set_error("bfs_poly_eval_points: null argument"); return BFS_ERR_BAD_ARG; }
+    if (n_coeffs < 1 || n_coeffs > (1ull << 24)) { set_error("bfs_poly_eval_points: n_coeffs must be 1..2^24 (got %llu)", (unsigned long long)n_coeffs); return BFS_ERR_BAD_ARG; }
+    if (batch < 1 || batch > 65535) { set_error("bfs_poly_eval_points: batch must be 1..65535 (got %u)", batch); return BFS_ERR_BAD_ARG; }
+    if (batch > 1 && in_stride < n_coeffs) { set_error("bfs_poly_eval_points: in_stride < n_coeffs"); return BFS_ERR_BAD_ARG; }
+    const u32 blocks = deep_eval_blocks(n_coeffs);
+    const u64 results = (u64)batch * k;
+    if (overlaps(d_out, results * 24, d_coeffs, ((u64)(batch - 1) * in_stride + n_coeffs) * 8)) { set_error("bfs_poly_eval_points: d_out overlaps the coefficients"); return BFS_ERR_BAD_ARG; }
+    return eval_launches("bfs_poly_eval_points", h_points, k, (u64)batch * blocks, stream,
+        [&](auto kk, const u64* table, u64* partial) {
+            hipLaunchKernelGGL((deep_eval_partial_kernel<decltype(kk)::value>), dim3(blocks, batch), dim3(DEEP_EVAL_T), 0, stream, d_coeffs, n_coeffs, in_stride, table, partial);
+        },
+        [&](const u64* table, const u64* partial) {
+            hipLaunchKernelGGL(deep_eval_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, partial, blocks, k, table, d_out);
+        });
+}
+
+extern "C" int bfsx_poly_eval_columns(const bfsx_eval_column* h_columns, uint32_t count, const uint64_t* h_points, uint32_t k, uint64_t* d_out,
+                                      void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!h_columns || !h_points || !d_out) { set_error("bfsx_poly_eval_columns: null argument"); return BFS_ERR_BAD_ARG; }
+    if (count < 1 || count > DEEP_EVAL_MAX_COLUMNS) { set_error("bfsx_poly_eval_columns: 1..%u columns (got %u)", DEEP_EVAL_MAX_COLUMNS, count); return BFS_ERR_BAD_ARG; }
+    const u64 results = (u64)count * k;
+    DeepEvalColumns cols{};
+    u32 row_blocks = 0;
+    for (u32 b = 0; b < count; ++b) {
+        const bfsx_eval_column& c = h_columns[b];
+        if (!c.d_coeffs) { set_error("bfsx_poly_eval_columns: column %u is null", b); return BFS_ERR_BAD_ARG; }
+        if (c.n_coeffs < 1 || c.n_coeffs > (1ull << 24)) { set_error("bfsx_poly_eval_columns: column %u: n_coeffs must be 1..2^24 (got %llu)", b, (unsigned long long)c.n_coeffs); return BFS_ERR_BAD_ARG; }
+        if (overlaps(d_out, results * 24, c.d_coeffs, c.n_coeffs * 8)) { set_error("bfsx_poly_eval_columns: d_out overlaps column %u", b); return BFS_ERR_BAD_ARG; }
+        cols.col[b] = c.d_coeffs;
+        cols.n[b] = (u32)c.n_coeffs;
+        if (deep_eval_blocks(c.n_coeffs) > row_blocks) row_blocks = deep_eval_blocks(c.n_coeffs);
+    }
+    return eval_launches("bfsx_poly_eval_columns", h_points, k, (u64)count * row_blocks, stream,
+        [&](auto kk, const u64* table, u64* partial) {
+            hipLaunchKernelGGL((deep_eval_columns_partial_kernel<decltype(kk)::value>), dim3(row_blocks, count), dim3(DEEP_EVAL_T), 0, stream, cols, table, partial);
+        },
+        [&](const u64* table, const u64* partial) {
+            hipLaunchKernelGGL(deep_eval_columns_combine_kernel, dim3((u32)results), dim3(DEEP_EVAL_T), 0, stream, cols, partial, row_blocks, k, table, d_out);
+        });
+}
+
+// one group at up to four points: its own argument block and kernel (fewer registers than the plan's kernel, profiles/pcs.md)
+extern "C" int bfs_deep_quotient(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset, uint64_t omega,
+                                 const uint64_t* h_points, const uint64_t* h_values, uint32_t k, const uint64_t h_lambda[3], uint64_t* d_out,
+                                 uint64_t out_stride, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* entry = "bfs_deep_quotient";
+    if (!h_columns || !h_points || !h_values || !h_lambda || !d_out) { set_error("bfs_deep_quotient: null argument"); return BFS_ERR_BAD_ARG; }
+    if (m < 1 || m > DEEP_MAX_COLUMNS) { set_error("bfs_deep_quotient: 1..%u codewords (got %u)", DEEP_MAX_COLUMNS, m); return BFS_ERR_BAD_ARG; }
+    if (k < 1 || k > DEEP_MAX_POINTS) { set_error("bfs_deep_quotient: the number of points must be 1..%u (got %u)", DEEP_MAX_POINTS, k); return BFS_ERR_BAD_ARG; }
+    BFS_TRY(check_domain(entry, log_n, limb_stride, out_stride, offset, omega, h_lambda));
+    const u64 n = 1ull << log_n;
+    BFS_TRY(check_codewords(entry, h_columns, m, limb_stride, n, d_out, out_stride));
+    DeepQuotientArgs a{};
+    a.m = m; a.limb_stride = limb_stride; a.n = n; a.offset = offset;
+    const Xfe lambda = xfe_load3(h_lambda);
+    Xfe power{{1, 0, 0}};                                 // lambda^p
+    for (u32 p = 0; p < m; ++p) {
+        a.col[p] = h_columns[p].d_values;
+        if (h_columns[p].is_ext) a.ext_mask |= 1u << p;
+        lazy_weight_matrix(power, a.weight[p]);
+        power = xfe_mul(power, lambda);
+    }
+    Xfe scale{{1, 0, 0}};                                 // lambda^(j m)
+    for (u32 j = 0; j < k; ++j) {
+        if (!canonical3(h_points + 3 * j) || !canonical3(h_values + 3 * j)) { set_error("bfs_deep_quotient: point or value %u is not reduced", j); return BFS_ERR_BAD_ARG; }
+        deep_point_consts(a.pt[j], xfe_load3(h_points + 3 * j), scale, xfe_load3(h_values + 3 * j));
+        scale = xfe_mul(scale, power);
+    }
+    BFS_TRY(ntt_power_tables(omega, log_n, &a.w_lo, &a.w_hi, &a.lo_bits));
+    const u32 grid = (u32)((n + DEEP_Q_T * DEEP_Q_E - 1) / (DEEP_Q_T * DEEP_Q_E));
+    (void)deep_with_count<DEEP_MAX_POINTS>(k, [&](auto kk) -> int {
+        hipLaunchKernelGGL((deep_quotient_kernel<decltype(kk)::value>), dim3(grid), dim3(DEEP_Q_T), 0, stream, a, d_out, out_stride);
+        return BFS_OK;
+    });
+    BFS_HIP(hipGetLastError());
+    return BFS_OK;
+}
+
+extern "C" int bfsx_deep_quotient_groups(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
+                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
+                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
+                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, void* stream) {
+    return deep_quotient_plan("bfsx_deep_quotient_groups", DEEP_G_LIMITS, h_columns, m, limb_stride, log_n, offset, omega, h_group_columns, h_group_pairs,
+                              n_groups, h_points, n_points, h_pair_point, h_pair_values, h_lambda, d_out, out_stride, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int bfsr_deep_quotient_rounds(const bfs_row_column* h_columns, uint32_t m, uint64_t limb_stride, uint32_t log_n, uint64_t offset,
+                                         uint64_t omega, const uint32_t* h_group_columns, const uint32_t* h_group_pairs, uint32_t n_groups,
+                                         const uint64_t* h_points, uint32_t n_points, const uint32_t* h_pair_point, const uint64_t* h_pair_values,
+                                         const uint64_t h_lambda[3], uint64_t* d_out, uint64_t out_stride, uint32_t* h_launches, void* stream) {
+    return deep_quotient_plan("bfsr_deep_quotient_rounds", DEEP_R_LIMITS, h_columns, m, limb_stride, log_n, offset, omega, h_group_columns, h_group_pairs,
+                              n_groups, h_points, n_points, h_pair_point, h_pair_values, h_lambda, d_out, out_stride, h_launches, (hipStream_t)stream);
 }

@@ -20,8 +20,16 @@
 // The two entries of include/bfstark_open.h reuse both: evaluation of separate columns of different lengths in one launch, and the
 // quotient of an opening plan (groups of columns, each with its own points); their parts of this file say what is new.  The entry of
 // include/bfstark_rounds.h splits a plan over the columns of several commitments between launches of that kernel (the last part).
+//
+// The host side of a plan is here ONCE, for both plan entries of deep.hip and for their emulations under tests/emu: deep_plan_check
+// (is the plan within the entry's limits), deep_rounds_split (which groups go into which launch) and deep_rounds_args (the only
+// function that fills a DeepGroupsArgs).  deep_with_count turns a run-time number of points into a template argument for all of them.
 #pragma once
 #include <stddef.h>
+#include <stdio.h>
+
+#include <type_traits>
+#include <vector>
 
 #include "lazy.hpp"
 
@@ -50,6 +58,28 @@ BFS_HD Xfe xfe_pow_small(Xfe a, u64 e) {
         if (e) a = xfe_mul(a, a);
     }
     return acc;
+}
+
+// fn(std::integral_constant<int, count>()) for 1 <= count <= MAX (the caller has checked the range): a run-time number of points as a
+// template argument.  Only 1 .. MAX are instantiated
+template <int MAX, class Fn>
+inline int deep_with_count(u32 count, Fn&& fn) {
+    if constexpr (MAX > 1) {
+        if (count < (u32)MAX) return deep_with_count<MAX - 1>(count, fn);
+    }
+    return fn(std::integral_constant<int, MAX>());
+}
+
+// the two-level powers of omega that the quotient kernels index (runtime.hpp: ntt_power_tables), in host memory for the emulations:
+// a.w_lo[i] = omega^i, a.w_hi[i] = omega^(i << a.lo_bits); `words` owns them.  A: DeepQuotientArgs or DeepGroupsArgs
+template <class A>
+inline void deep_host_omega_tables(A& a, u64 omega, u32 log_n, std::vector<u64>& words) {
+    a.lo_bits = (log_n + 1) / 2;
+    const u64 lo = 1ull << a.lo_bits, hi = 1ull << (log_n - a.lo_bits);
+    words.resize(lo + hi);
+    for (u64 i = 0; i < lo; ++i) words[i] = gl_pow(omega, i);
+    for (u64 i = 0; i < hi; ++i) words[lo + i] = gl_pow(omega, i << a.lo_bits);
+    a.w_lo = words.data(); a.w_hi = words.data() + lo;
 }
 
 // entry t < T of point j's part of the table (and, for t < S, step weight t)
@@ -342,6 +372,40 @@ constexpr u32 DEEP_R_GROUPS = 24;
 constexpr u32 DEEP_R_POINTS = 24;
 constexpr u32 DEEP_R_PAIRS = 48;
 
+struct DeepPlanLimits {
+    u32 columns, groups, points, pairs;
+};
+constexpr DeepPlanLimits DEEP_G_LIMITS{DEEP_MAX_COLUMNS, DEEP_G_GROUPS, DEEP_G_POINTS, DEEP_G_PAIRS};      // bfsx_deep_quotient_groups: one launch
+constexpr DeepPlanLimits DEEP_R_LIMITS{DEEP_R_COLUMNS, DEEP_R_GROUPS, DEEP_R_POINTS, DEEP_R_PAIRS};        // bfsr_deep_quotient_rounds
+
+// THE check of a plan as the entries receive it (host only): within `lim`, every group with 1..32 columns and 1..4 pairs, the sizes
+// adding up to m, every pair naming one of the n_points points and no point twice in a group.  false: `why` says what is wrong
+inline bool deep_plan_check(const DeepPlanLimits& lim, u32 m, const u32* group_columns, const u32* group_pairs, u32 n_groups, u32 n_points,
+                            const u32* pair_point, char (&why)[96]) {
+    const auto refuse = [&](const char* what, u32 a, u32 b) { snprintf(why, sizeof why, what, a, b); return false; };
+    if (m < 1 || m > lim.columns) return refuse("1..%u codewords (got %u)", lim.columns, m);
+    if (n_groups < 1 || n_groups > lim.groups) return refuse("1..%u groups (got %u)", lim.groups, n_groups);
+    if (n_points < 1 || n_points > lim.points) return refuse("1..%u distinct points (got %u)", lim.points, n_points);
+    u32 columns = 0, pairs = 0;
+    for (u32 g = 0; g < n_groups; ++g) {
+        if (group_columns[g] < 1 || group_columns[g] > m - columns) return refuse("group %u: an empty group, or more columns than there are (%u)", g, m);
+        if (group_columns[g] > DEEP_MAX_COLUMNS) return refuse("group %u: at most 32 columns in a group (got %u)", g, group_columns[g]);
+        if (group_pairs[g] < 1 || group_pairs[g] > DEEP_MAX_POINTS) return refuse("group %u: 1..4 points (got %u)", g, group_pairs[g]);
+        if (group_pairs[g] > lim.pairs - pairs) return refuse("at most %u (group, point) pairs (group %u goes beyond)", lim.pairs, g);
+        u32 seen = 0;
+        for (u32 j = 0; j < group_pairs[g]; ++j) {
+            const u32 point = pair_point[pairs + j];
+            if (point >= n_points) return refuse("pair %u names point %u, which is none of the plan's", pairs + j, point);
+            if ((seen >> point) & 1) return refuse("group %u opens point %u twice", g, point);
+            seen |= 1u << point;
+        }
+        columns += group_columns[g];
+        pairs += group_pairs[g];
+    }
+    if (columns != m) return refuse("the groups hold %u columns, not %u", columns, m);
+    return true;
+}
+
 struct DeepRoundsLaunch {
     u32 first_group, n_groups;
     u32 first_column, n_columns;
@@ -352,7 +416,8 @@ struct DeepRoundsLaunch {
 
 // Groups in plan order; a launch takes groups while its columns <= 32, its groups <= 8, its pairs <= 16 and the distinct points among
 // its groups <= 8; the first group that would break one of these starts the next launch.  Every group has 1..32 columns and 1..4 pairs
-// (the caller has checked), so a group alone always fits.  launches: room for n_groups entries.  -> the number of launches
+// (deep_plan_check), so a group alone always fits.  Every bound here is one of the one-launch limits (DEEP_G_LIMITS), so a plan within
+// those is always exactly ONE launch.  launches: room for n_groups entries.  -> the number of launches
 inline u32 deep_rounds_split(const u32* group_columns, const u32* group_pairs, u32 n_groups, const u32* pair_point, DeepRoundsLaunch* launches) {
     u32 count = 0, c = 0, q = 0;
     DeepRoundsLaunch cur{};
@@ -383,7 +448,8 @@ inline u32 deep_rounds_split(const u32* group_columns, const u32* group_pairs, u
 
 // the plan's part of launch L's arguments (the caller fills n, strides, offset and the tables of omega).  col / is_ext: the columns of
 // the WHOLE plan in group order; points, pair_point, pair_values: the whole plan's.  scale: lambda^base of L's first pair on entry, of
-// the next launch's first pair on return.
+// the next launch's first pair on return.  The launch's points are those its pairs name, in order of first appearance (L.point): a
+// point of the plan that no pair uses reaches no kernel, and the kernel's NP is the number of points in use.
 inline void deep_rounds_args(DeepGroupsArgs& a, const DeepRoundsLaunch& L, const u64* const* col, const int* is_ext, const u32* group_columns,
                              const u32* group_pairs, const u64* points, const u32* pair_point, const u64* pair_values, const Xfe& lambda, Xfe& scale) {
     a.n_groups = L.n_groups;

@@ -46,9 +46,17 @@ already): the distinct points in order of first appearance; the shape (tuple(wid
 group]), plain ints -- numbering and plan are inside every later Fiat-Shamir hash; the values; [lambda]; the root of the tree over g;
 [t indices]; per index i: for r = 0 .. R - 1 the row tuple of C_r at x_i and its authentication path, then the opening of g as above;
 then Fri.prove over g.  With one commitment the quotient is `open_at`'s and the stream differs by the widths in the shape.
+
+The three openings are ONE prover and ONE verifier over an OpeningPlan (PolynomialCommitment._open, ._verify_quotient): `open` is the plan
+of one group of all columns (built without the rule against a point given twice, which `open` never had), `open_at` a plan over one
+commitment, `open_rounds` a plan over the columns of several.  They differ in what they push behind the points (nothing; the shape; the
+widths and the shape), in the shape of the values in the stream (`open` has no group level) and in the library entry that builds g
+(bfs_deep_quotient, which is cheaper for one group; bfsx_deep_quotient_groups; bfsr_deep_quotient_rounds) -- ._quotient marshals the plan
+for all three.  The verifiers differ in how they compare points, header and values with the caller's.
 """
 import collections
 import ctypes
+import functools
 from hashlib import blake2b
 
 import numpy as np
@@ -59,7 +67,7 @@ from .algebra import BaseFieldElement
 from .arrays import BaseArray, XArray, raw_ntt
 from .device import DeviceBuffer, current_stream, gather
 from .extension_field import ExtensionFieldElement
-from .merkle import CosetMerkle, Merkle
+from .merkle import CosetMerkle, Merkle, leaf_pickle_source
 from .ntt import _base_value
 
 _u64 = ctypes.c_uint64
@@ -120,18 +128,6 @@ def _eval_requests(requests):
             for j in range(k):
                 w = at + 3 * (b * k + j)
                 results[r][first + b][j0 + j] = tuple(words[w:w + 3])
-    return results
-
-
-def _eval_jobs(jobs, points):
-    """jobs: (ptr, n, stride, batch) coefficient arrays -> per job [[limb triple of column b at point j] per column] per point: all
-    columns of all jobs in one bfsx_poly_eval_columns call per four points"""
-    columns = [(ptr + 8 * b * stride, n) for ptr, n, stride, batch in jobs for b in range(batch)]
-    got = _eval_requests([(columns, points)])[0]
-    results, at = [], 0
-    for ptr, n, stride, batch in jobs:
-        results.append([[got[at + b][j] for b in range(batch)] for j in range(len(points))])
-        at += batch
     return results
 
 
@@ -221,14 +217,15 @@ class OpeningPlan:
     outside the domain (equal limb triples are one point; the same point may serve several groups).  At most 8 groups, 8 distinct
     points, 16 (group, point) pairs, 32 columns -- or what `limits` (a PlanLimits) says: ROUNDS_LIMITS for a plan over the columns of
     several commitments (24 groups, 24 distinct points, 48 pairs, 96 columns, 32 in any one group).  Anything else raises ValueError
-    with the reason -- before any GPU work.
+    with the reason -- before any GPU work.  distinct=False (the one group of `open`) takes the points as they come: a point given twice is
+    two points of the plan.
 
         points      the distinct points as limb triples, in order of first appearance
         groups      per group (columns, indices into `points`)
         base        base[g][j]: the exponent of lambda at which pair (g, j) starts (a running count of the pairs' columns)
         shape       what the proof stream carries: per group (tuple(columns), tuple(point indices)), plain ints"""
 
-    def __init__(self, plan, in_domain, m=None, limits=PLAN_LIMITS):
+    def __init__(self, plan, in_domain, m=None, limits=PLAN_LIMITS, distinct=True):
         try:
             groups = [([int(c) for c in columns], [_limbs(z) for z in points]) for columns, points in plan]
         except (TypeError, ValueError):
@@ -238,23 +235,26 @@ class OpeningPlan:
         self.points, self.groups, self.base = [], [], []
         seen, count = set(), 0
         for g, (columns, points) in enumerate(groups):
-            if not columns or columns != sorted(set(columns)) or columns[0] < 0:
+            own = set(columns)
+            if not columns or columns != sorted(own) or columns[0] < 0:
                 raise ValueError("group %d: columns must be an ascending, non-empty list of row columns" % g)
-            if seen & set(columns):
-                raise ValueError("group %d: column %d lies in an earlier group too" % (g, min(seen & set(columns))))
-            seen |= set(columns)
+            if seen & own:
+                raise ValueError("group %d: column %d lies in an earlier group too" % (g, min(seen & own)))
+            seen |= own
             if len(columns) > limits.group_columns:
                 raise ValueError("group %d: at most %d columns in a group (got %d)" % (g, limits.group_columns, len(columns)))
             if not 1 <= len(points) <= MAX_POINTS_PER_LAUNCH or any(len(z) != 3 for z in points):
                 raise ValueError("group %d: 1 .. %d points of three limbs each" % (g, MAX_POINTS_PER_LAUNCH))
-            if len(set(points)) != len(points):
+            if distinct and len(set(points)) != len(points):
                 raise ValueError("group %d: a point appears twice" % g)
+            indices = []
             for z in points:
                 if in_domain(z):
                     raise ValueError("cannot open at a point of the FRI domain: %s" % (z,))
-                if z not in self.points:
+                if not distinct or z not in self.points:
                     self.points.append(z)
-            self.groups.append((columns, [self.points.index(z) for z in points]))
+                indices.append(len(self.points) - 1 if not distinct else self.points.index(z))
+            self.groups.append((columns, indices))
             self.base.append([count + j * len(columns) for j in range(len(points))])
             count += len(points) * len(columns)
         self.m, self.exponents = len(seen), count
@@ -283,6 +283,22 @@ class OpeningPlan:
                     acc = xadd(acc, xmul(powers[self.base[g][j] + r], y))
                 combined[-1].append(acc)
         return combined, powers
+
+
+def _reads_leaf_pickles(verifier):
+    """a verifier whose last argument is the proof stream: while it runs, Merkle.verify takes the pickle of an opened leaf from the stream
+    that holds it (merkle.leaf_pickle_source) -- unless an outer verifier has said so already"""
+    @functools.wraps(verifier)
+    def entry(self, *args, **kwargs):
+        proof_stream = kwargs["proof_stream"] if "proof_stream" in kwargs else args[-1]
+        if leaf_pickle_source.get() is not None or not hasattr(proof_stream, "pickle_of"):
+            return verifier(self, *args, **kwargs)
+        token = leaf_pickle_source.set(proof_stream.pickle_of)
+        try:
+            return verifier(self, *args, **kwargs)
+        finally:
+            leaf_pickle_source.reset(token)
+    return entry
 
 
 class PolynomialCommitment:
@@ -318,18 +334,6 @@ class PolynomialCommitment:
     @staticmethod
     def _indices(t, seed, n):
         return [int.from_bytes(blake2b(seed + bytes(i)).digest(), "big") % n for i in range(t)]      # BrainfuckStark.sample_indices
-
-    @staticmethod
-    def _combined_values(values, lam):
-        """Y_j = sum_p lambda^(j m + p) y_{p,j}, p in row order"""
-        out, power = [], (1, 0, 0)
-        for per_point in values:
-            acc = (0, 0, 0)
-            for y in per_point:
-                acc = xadd(acc, xmul(power, y))
-                power = xmul(power, lam)
-            out.append(acc)
-        return out
 
     # ---------------------------------------------------------------------------------------------------------- prover
     def commit(self, polys, proof_stream):
@@ -370,43 +374,74 @@ class PolynomialCommitment:
             committed._rows[i] = tuple(ext + [BaseFieldElement(int(v), base) for v in words[3 * committed.n_ext:]])
         return committed._rows[i]
 
-    def quotient(self, committed, points, values, lam):
-        """the DEEP quotient codeword (XArray) of the commitment's columns: bfs_deep_quotient"""
-        n, m = self.n, len(committed.polys)
-        cols = (_lib.RowColumn * m)()
-        for c in range(m):
-            cols[c].d_values, cols[c].is_ext, cols[c].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
-        combined = self._combined_values(values, lam)
+    # every opening is an OpeningPlan over the row columns of a list of commitments, numbered through: `open` one group of all columns of
+    # one commitment, `open_at` a plan over one commitment, `open_rounds` a plan over several
+    def _one_group(self, points, m):
+        """the plan of `open`, `verify` and `quotient`: all m columns at `points` as they come (a point given twice stays two points;
+        whether a point lies in the domain is for the caller to ask, as it was: `open` and `verify` do, `quotient` never did)"""
+        return OpeningPlan([(range(m), points)], lambda z: False, m, PlanLimits(1, MAX_POINTS_PER_LAUNCH, MAX_POINTS_PER_LAUNCH, m, m), distinct=False)
+
+    @staticmethod
+    def _where(commitments):
+        """per column of the through numbering: (its commitment, its row column there)"""
+        return [(committed, c) for committed in commitments for c in range(len(committed.polys))]
+
+    def _quotient(self, entry, arguments, commitments, plan, values, lam, tail=()):
+        """the DEEP quotient codeword (XArray) of a plan by one of the three entries.  values[g][j][r]: limb triples; arguments(plan, Y):
+        how the entry takes the plan between omega and lambda; tail: what it takes between the output and the stream"""
+        n, where = self.n, self._where(commitments)
+        cols = (_lib.RowColumn * len(where))()
+        for at, column in enumerate(c for columns, _ in plan.groups for c in columns):      # (the kernels want the columns in group order)
+            committed, c = where[column]
+            cols[at].d_values, cols[at].is_ext, cols[at].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
+        combined, _ = plan.combined_values(values, lam)
         g = XArray.empty(n, self.xfield)
-        _lib.check(_lib.load().bfs_deep_quotient(cols, m, n, n.bit_length() - 1, self.offset, self.omega,
-                                                 (_u64 * (3 * len(points)))(*[v for z in points for v in z]),
-                                                 (_u64 * (3 * len(points)))(*[v for y in combined for v in y]), len(points),
-                                                 (_u64 * 3)(*lam), g.ptr, g.stride, current_stream()))
+        _lib.check(entry(cols, len(where), n, n.bit_length() - 1, self.offset, self.omega, *arguments(plan, combined), (_u64 * 3)(*lam), g.ptr, g.stride,
+                         *tail, current_stream()))
         return g
+
+    @staticmethod
+    def _group_arguments(plan, combined):
+        """bfs_deep_quotient: the points of the one group and its Y_j"""
+        return _flat_points(plan.points), _flat_points(combined[0]), len(plan.points)
+
+    @staticmethod
+    def _plan_arguments(plan, combined):
+        """both plan entries: group sizes, the distinct points, per pair its point and its Y"""
+        u32, groups = ctypes.c_uint32, len(plan.groups)
+        return ((u32 * groups)(*[len(columns) for columns, _ in plan.groups]), (u32 * groups)(*[len(indices) for _, indices in plan.groups]), groups,
+                _flat_points(plan.points), len(plan.points), (u32 * plan.pairs)(*[p for _, indices in plan.groups for p in indices]),
+                _flat_points([y for per_group in combined for y in per_group]))
+
+    def quotient(self, committed, points, values, lam):
+        """the DEEP quotient codeword (XArray) of the commitment's columns: bfs_deep_quotient (its own kernel: one group costs less there,
+        profiles/pcs.md).  points: limb triples; values[j][p]: limb triples"""
+        return self._quotient(_lib.load().bfs_deep_quotient, self._group_arguments, [committed], self._one_group(points, len(committed.polys)), [values], lam)
+
+    def _open(self, commitments, plan, header, quotient, proof_stream, pushed=lambda values: values):
+        """THE prover: the plan's points, `header` (what this opening pushes behind them), the values (evaluated here; pushed(values) is
+        what the stream gets), lambda, g = quotient(commitments, plan, values as limb triples, lambda), and what follows lambda in every
+        opening.  -> values[g][j][r]"""
+        xf = self.xfield
+        proof_stream.push([xf.from_limbs(z) for z in plan.points])
+        for part in header:
+            proof_stream.push(part)
+        raw, values = self._plan_values(plan, commitments)
+        proof_stream.push(pushed(values))
+        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
+        self._prove_quotient(commitments, quotient(commitments, plan, raw, lam), proof_stream)
+        return values
 
     def open(self, committed, points, proof_stream):
         """proves the values of every committed polynomial at `points` (1..4 ExtensionFieldElements outside the FRI domain); returns
         them: a list per point of a list per polynomial IN ROW ORDER -- extension polynomials first, then base polynomials, each group in
         the order `commit` was given them (Commitment.order[c] = position of row column c in that list)"""
-        xf = self.xfield
         assert 1 <= len(points) <= MAX_POINTS_PER_LAUNCH, "1 .. 4 points per opening"
         for z in points:
             if self.in_domain(z):
                 raise ValueError("cannot open at a point of the FRI domain: %s" % (z,))
-        pts = [_limbs(z) for z in points]
-        point_objects = [xf.from_limbs(z) for z in pts]
-        proof_stream.push(point_objects)
-        raw = [[None] * len(committed.polys) for _ in pts]
-        in_row_order = [committed.polys[position] for position in committed.order]
-        jobs = [(f.ptr, f.n, f.stride, 3) if isinstance(f, XArray) else (f.ptr, f.n, f.n, 1) for f in in_row_order]
-        for c, (f, got) in enumerate(zip(in_row_order, _eval_jobs(jobs, pts))):
-            for j, v in enumerate(got):
-                raw[j][c] = _combine_planes(v) if isinstance(f, XArray) else v[0]
-        values = [[xf.from_limbs(v) for v in per_point] for per_point in raw]
-        proof_stream.push(values)
-        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        self._prove_quotient([committed], self.quotient(committed, pts, raw, lam), proof_stream)
-        return values
+        one = functools.partial(self._quotient, _lib.load().bfs_deep_quotient, self._group_arguments)
+        return self._open([committed], self._one_group(points, len(committed.polys)), [], one, proof_stream, lambda values: values[0])[0]
 
     def _prove_quotient(self, commitments, g, proof_stream):
         """what follows lambda in every opening: the root of the tree over g, the t consistency indices with their rows (one row and
@@ -454,17 +489,11 @@ class PolynomialCommitment:
             fri.prove(g, proof_stream, known_leafs=known or None, round0_tree=g_tree)
 
     # ---------------------------------------------------------------------------------------------------------- verifier (host only)
+    @_reads_leaf_pickles
     def verify(self, root, points, values, proof_stream):
         """does the proof in `proof_stream` (read position right behind the commitment's root) show that the polynomials behind `root`
         take `values` (what `open` returned: a list per point of a list per polynomial in row order) at `points`?
         Host code only: Python ints, hashlib and Fri.verify; one printed line per refusal."""
-        from .merkle import leaf_pickle_source
-        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
-            token = leaf_pickle_source.set(proof_stream.pickle_of)
-            try:
-                return self.verify(root, points, values, proof_stream)
-            finally:
-                leaf_pickle_source.reset(token)
         is_element = lambda e: isinstance(e, ExtensionFieldElement)
         pts = [_limbs(z) for z in points]
         if not 1 <= len(pts) <= MAX_POINTS_PER_LAUNCH or any(self.in_domain(z) for z in pts):
@@ -482,11 +511,14 @@ class PolynomialCommitment:
                 or [[_limbs(v) for v in c] for c in claimed] != want):
             print("values differ from the caller's")
             return False
+        return self._verify_quotient([(root, m)], self._one_group(pts, m), [want], proof_stream)
+
+    def _verify_quotient(self, trees, plan, want, proof_stream):
+        """THE verifier, once points, header and values are the caller's: lambda, then what follows it (_check_quotient) against the
+        plan's formula.  want[g][j][r]: limb triples"""
         lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
-        powers = [(1, 0, 0)]
-        for _ in range(len(pts) * m):
-            powers.append(xmul(powers[-1], lam))
-        return self._check_quotient([(root, m)], lambda i, row: self._quotient_at(i, row, pts, want, powers, m), proof_stream)
+        combined, powers = plan.combined_values(want, lam)
+        return self._check_quotient(trees, lambda i, row: self._plan_quotient_at(i, row, plan, combined, powers), proof_stream)
 
     def _check_quotient(self, trees, quotient_at, proof_stream):
         """what follows lambda in every opening, read back.  trees: (root, width) per commitment, in the order their rows were pushed;
@@ -544,20 +576,6 @@ class PolynomialCommitment:
         return (isinstance(path, list) and len(path) == leaves.bit_length() - 1
                 and all(isinstance(node, (bytes, bytearray)) for node in path))
 
-    def _quotient_at(self, i, row, pts, values, powers, m):
-        """g[i] from the row at x_i: sum_j (lambda^(j m) S - Y_j) / (x_i - z_j).  values[j][p]: y_{p,j}"""
-        x = self.offset * pow(self.omega, i, P) % P
-        s = (0, 0, 0)
-        for p in range(m):
-            s = xadd(s, xmul(powers[p], row[p]))
-        g = (0, 0, 0)
-        for j, z in enumerate(pts):
-            y = (0, 0, 0)
-            for p in range(m):
-                y = xadd(y, xmul(powers[j * m + p], values[j][p]))
-            g = xadd(g, xmul(xsub(xmul(powers[j * m], s), y), xinv(xsub((x, 0, 0), z))))
-        return g
-
     # ---------------------------------------------------------------------------------------------------------- opening plans
     def plan(self, plan, m=None):
         """the checked OpeningPlan of a list of (columns, points) groups (ValueError with the reason otherwise)"""
@@ -565,38 +583,20 @@ class PolynomialCommitment:
 
     def quotient_at(self, committed, plan, values, lam):
         """the DEEP quotient codeword (XArray) of an opening plan: bfsx_deep_quotient_groups.  values[g][j][r]: limb triples"""
-        n, m = self.n, len(committed.polys)
-        cols = (_lib.RowColumn * m)()
-        for at, c in enumerate(c for columns, _ in plan.groups for c in columns):         # (the kernel wants the columns in group order)
-            cols[at].d_values, cols[at].is_ext, cols[at].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
-        combined, _ = plan.combined_values(values, lam)
-        u32 = ctypes.c_uint32
-        g = XArray.empty(n, self.xfield)
-        _lib.check(_lib.load().bfsx_deep_quotient_groups(
-            cols, m, n, n.bit_length() - 1, self.offset, self.omega,
-            (u32 * len(plan.groups))(*[len(columns) for columns, _ in plan.groups]), (u32 * len(plan.groups))(*[len(indices) for _, indices in plan.groups]),
-            len(plan.groups), _flat_points(plan.points), len(plan.points), (u32 * plan.pairs)(*[p for _, indices in plan.groups for p in indices]),
-            _flat_points([y for per_group in combined for y in per_group]), (_u64 * 3)(*lam), g.ptr, g.stride, current_stream()))
-        return g
+        return self._quotient(_lib.load().bfsx_deep_quotient_groups, self._plan_arguments, [committed], plan, values, lam)
 
     def open_at(self, committed, plan, proof_stream):
         """proves, for every group (columns_g, points_g) of `plan` (see OpeningPlan), the values of the row columns columns_g at the
         points points_g; returns them as values[g][j][r] = f_{columns_g[r]}(points_g[j]).  Commitment.column_of(position) is the row
         column of the polynomial at `position` of the list `commit` was given.  The plan is checked before any GPU work (ValueError)."""
-        xf = self.xfield
         plan = self.plan(plan, len(committed.polys))
-        proof_stream.push([xf.from_limbs(z) for z in plan.points])
-        proof_stream.push(plan.shape)
-        raw, values = self._plan_values(plan, lambda c: committed.polys[committed.order[c]])
-        proof_stream.push(values)
-        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        self._prove_quotient([committed], self.quotient_at(committed, plan, raw, lam), proof_stream)
-        return values
+        return self._open([committed], plan, [plan.shape], functools.partial(self._quotient, _lib.load().bfsx_deep_quotient_groups, self._plan_arguments),
+                          proof_stream)
 
-    def _plan_values(self, plan, polynomial):
-        """the values a plan asks for, as limb triples and as elements, both [g][j][r]; polynomial(c): the coefficients behind column c.
-        One evaluation call per distinct point set: the coefficient columns of every group that is opened there"""
-        xf = self.xfield
+    def _plan_values(self, plan, commitments):
+        """the values a plan over the columns of `commitments` asks for, as limb triples and as elements, both [g][j][r].  One evaluation
+        call per distinct point set: the coefficient columns of every group that is opened there"""
+        xf, where = self.xfield, self._where(commitments)
         point_sets = list(dict.fromkeys(tuple(indices) for _, indices in plan.groups))
         requests, places = [], {}
         for point_set in point_sets:
@@ -604,7 +604,8 @@ class PolynomialCommitment:
             for g, (columns, indices) in enumerate(plan.groups):
                 if tuple(indices) == point_set:
                     for r, c in enumerate(columns):
-                        f = polynomial(c)
+                        committed, row_column = where[c]
+                        f = committed.polys[committed.order[row_column]]
                         planes = [(f.ptr + 8 * l * f.stride, f.n) for l in range(3)] if isinstance(f, XArray) else [(f.ptr, f.n)]
                         places[g, r] = (len(requests), len(coefficient_columns), len(planes))
                         coefficient_columns += planes
@@ -620,17 +621,11 @@ class PolynomialCommitment:
                     raw[g][j][r] = _combine_planes(v) if planes == 3 else v[0]
         return raw, [[[xf.from_limbs(v) for v in per_point] for per_point in per_group] for per_group in raw]
 
+    @_reads_leaf_pickles
     def verify_at(self, root, plan, values, proof_stream):
         """does the proof in `proof_stream` (read position right behind the commitment's root) show that the polynomials behind `root`
         take `values` (what `open_at` returned: values[g][j][r]) under `plan`?  Host code only: Python ints, hashlib and Fri.verify; one
         printed line per refusal."""
-        from .merkle import leaf_pickle_source
-        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
-            token = leaf_pickle_source.set(proof_stream.pickle_of)
-            try:
-                return self.verify_at(root, plan, values, proof_stream)
-            finally:
-                leaf_pickle_source.reset(token)
         try:
             plan = self.plan(plan)
         except ValueError as e:
@@ -661,9 +656,7 @@ class PolynomialCommitment:
                 or [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in claimed] != want):
             print("values differ from the caller's")
             return False
-        lam = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
-        combined, powers = plan.combined_values(want, lam)
-        return self._check_quotient(trees, lambda i, row: self._plan_quotient_at(i, row, plan, combined, powers), proof_stream)
+        return self._verify_quotient(trees, plan, want, proof_stream)
 
     def _plan_quotient_at(self, i, row, plan, combined, powers):
         """g[i] from the row at x_i: sum_g sum_j (lambda^base[g][j] S_g - Y_{g,j}) / (x_i - z_{g,j})"""
@@ -713,53 +706,25 @@ class PolynomialCommitment:
     def quotient_rounds(self, commitments, plan, values, lam, launches=None):
         """the DEEP quotient codeword (XArray) of a plan over the columns of several commitments: bfsr_deep_quotient_rounds, as many
         launches as the plan needs into one output.  values[g][j][r]: limb triples; launches: a ctypes.c_uint32 that receives their number"""
-        n = self.n
-        where = [(committed, c) for committed in commitments for c in range(len(committed.polys))]
-        cols = (_lib.RowColumn * len(where))()
-        for at, column in enumerate(c for columns, _ in plan.groups for c in columns):      # (the kernel wants the columns in group order)
-            committed, c = where[column]
-            cols[at].d_values, cols[at].is_ext, cols[at].field_id = committed.column_ptr(c), int(c < committed.n_ext), 1
-        combined, _ = plan.combined_values(values, lam)
-        u32 = ctypes.c_uint32
-        g = XArray.empty(n, self.xfield)
-        _lib.check(_lib.load().bfsr_deep_quotient_rounds(
-            cols, len(where), n, n.bit_length() - 1, self.offset, self.omega,
-            (u32 * len(plan.groups))(*[len(columns) for columns, _ in plan.groups]), (u32 * len(plan.groups))(*[len(indices) for _, indices in plan.groups]),
-            len(plan.groups), _flat_points(plan.points), len(plan.points), (u32 * plan.pairs)(*[p for _, indices in plan.groups for p in indices]),
-            _flat_points([y for per_group in combined for y in per_group]), (_u64 * 3)(*lam), g.ptr, g.stride,
-            ctypes.byref(launches) if launches is not None else None, current_stream()))
-        return g
+        return self._quotient(_lib.load().bfsr_deep_quotient_rounds, self._plan_arguments, commitments, plan, values, lam,
+                              tail=(ctypes.byref(launches) if launches is not None else None,))
 
     def open_rounds(self, commitments, plan, proof_stream):
         """proves values of the polynomials of 1 .. 4 commitments of this PolynomialCommitment -- made at any moments of the same
         transcript -- under ONE plan, one quotient and one low-degree test.  The plan's columns are the row columns of all commitments
         numbered through (`global_column`); a group may hold columns of different commitments.  Returns values[g][j][r].  The plan is
         checked before any GPU work (ValueError)."""
-        xf = self.xfield
         commitments = list(commitments)
         widths = self._widths([len(committed.polys) for committed in commitments])
         plan = self.rounds_plan(plan, widths)
-        where = [(committed, c) for committed in commitments for c in range(len(committed.polys))]
-        proof_stream.push([xf.from_limbs(z) for z in plan.points])
-        proof_stream.push((tuple(widths), plan.shape))
-        raw, values = self._plan_values(plan, lambda column: where[column][0].polys[where[column][0].order[where[column][1]]])
-        proof_stream.push(values)
-        lam = tuple(xf.sample(proof_stream.prover_fiat_shamir()).limbs())
-        self._prove_quotient(commitments, self.quotient_rounds(commitments, plan, raw, lam), proof_stream)
-        return values
+        return self._open(commitments, plan, [(tuple(widths), plan.shape)], self.quotient_rounds, proof_stream)
 
+    @_reads_leaf_pickles
     def verify_rounds(self, roots, widths, plan, values, proof_stream):
         """does the proof in `proof_stream` (read position where `open_rounds` began to push) show that the polynomials behind `roots`
         -- commitments of row widths `widths`, in the order `open_rounds` was given them -- take `values` (values[g][j][r]) under
         `plan`?  The roots are the caller's: it has read each from the transcript where `commit` pushed it.  Host code only; one printed
         line per refusal."""
-        from .merkle import leaf_pickle_source
-        if leaf_pickle_source.get() is None and hasattr(proof_stream, "pickle_of"):
-            token = leaf_pickle_source.set(proof_stream.pickle_of)
-            try:
-                return self.verify_rounds(roots, widths, plan, values, proof_stream)
-            finally:
-                leaf_pickle_source.reset(token)
         try:
             roots = list(roots)
             widths = self._widths(widths)

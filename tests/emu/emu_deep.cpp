@@ -38,13 +38,7 @@ extern "C" int emu_deep_eval(const u64* coeffs, u64 n, u64 in_stride, unsigned b
     std::vector<u64> table(DEEP_EVAL_TABLE_WORDS, 0);
     for (u32 j = 0; j < k; ++j)
         for (u32 t = 0; t < DEEP_EVAL_T; ++t) deep_eval_table_entry(Xfe{{points[3 * j], points[3 * j + 1], points[3 * j + 2]}}, j, t, table.data());
-    switch (k) {
-    case 1: eval_k<1>(coeffs, n, in_stride, batch, table.data(), out); break;
-    case 2: eval_k<2>(coeffs, n, in_stride, batch, table.data(), out); break;
-    case 3: eval_k<3>(coeffs, n, in_stride, batch, table.data(), out); break;
-    default: eval_k<4>(coeffs, n, in_stride, batch, table.data(), out); break;
-    }
-    return 0;
+    return deep_with_count<DEEP_MAX_POINTS>(k, [&](auto kk) { eval_k<decltype(kk)::value>(coeffs, n, in_stride, batch, table.data(), out); return 0; });
 }
 
 template <int K>
@@ -81,16 +75,7 @@ extern "C" int emu_deep_quotient(const u64* const* columns, const int* is_ext, u
         deep_point_consts(a.pt[j], Xfe{{points[3 * j], points[3 * j + 1], points[3 * j + 2]}}, scale, Xfe{{values[3 * j], values[3 * j + 1], values[3 * j + 2]}});
         scale = xfe_mul(scale, power);
     }
-    a.lo_bits = (log_n + 1) / 2;                          // the two-level table of the launch
-    std::vector<u64> lo(1ull << a.lo_bits), hi(1ull << (log_n - a.lo_bits));
-    for (u64 i = 0; i < lo.size(); ++i) lo[i] = gl_pow(omega, i);
-    for (u64 i = 0; i < hi.size(); ++i) hi[i] = gl_pow(omega, i << a.lo_bits);
-    a.w_lo = lo.data(); a.w_hi = hi.data();
-    switch (k) {
-    case 1: quotient_k<1>(a, out, out_stride); break;
-    case 2: quotient_k<2>(a, out, out_stride); break;
-    case 3: quotient_k<3>(a, out, out_stride); break;
-    default: quotient_k<4>(a, out, out_stride); break;
-    }
-    return 0;
+    std::vector<u64> omegas;
+    deep_host_omega_tables(a, omega, log_n, omegas);
+    return deep_with_count<DEEP_MAX_POINTS>(k, [&](auto kk) { quotient_k<decltype(kk)::value>(a, out, out_stride); return 0; });
 }

@@ -110,14 +110,17 @@ def protocol_points(o, N, k, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def model_proof(N, mode, k, zero=False, forced=False, seed=0):
-    """the model's commitment and opening -- computed once per case, shared, never changed"""
+def model_proof(N, mode, k, zero=False, forced=False, seed=0, repeated=False):
+    """the model's commitment and opening -- computed once per case, shared, never changed.  repeated: the first point k times (the
+    model has no rule against a point that is given twice)"""
     from oracle import ref_oracle as o
     a, coset, bits = MODES[mode]
     omega = o.primitive_nth_root(N)
     ext, base = polynomials(o, N, zero)
     committed = model.commit(o, ext, base, N, OFFSET, omega)
     points = protocol_points(o, N, k, seed)
+    if repeated:
+        points = points[:1] * k
     forced_values = None
     if forced:
         forced_values = model.true_values(committed, points)

@@ -251,6 +251,21 @@ def test_objects_that_recur_in_the_stream_are_the_same_objects(sb, N, mode, seed
     assert _verdict(sb, N, mode, data, root, proof["points"], values) is True
 
 
+def test_a_point_given_twice_is_opened_twice(sb, oracle):
+    """points = [z, z]: `open` does not refuse them (an OpeningPlan would), proves both, and `verify` accepts -- the bytes are the
+    model's, which has no such rule either"""
+    import test_pcs_host as host
+    N, mode = 64, "default"
+    proof = cases.model_proof(N, mode, 2, repeated=True)
+    assert proof["points"][0] == proof["points"][1]
+    pc, data, root, values = _prove(sb, N, mode, proof)
+    assert values == proof["values"] and values[0] == values[1]
+    assert data == proof["bytes"]
+    assert _verdict(sb, N, mode, data, root, proof["points"], values) is True
+    assert model.verify(oracle, streams.load(oracle, data), root, proof["points"], values, N, cases.OFFSET, proof["omega"], cases.T, 2, False,
+                        host._fri_verify(sb, N, mode)) == (True, "accepted")
+
+
 @pytest.mark.parametrize("N,mode", [(256, "default"), (256, "coset8")], ids=["256-default", "256-coset8"])
 def test_tampered_streams_and_other_statements_are_refused(sb, N, mode):
     import test_pcs_host as host

@@ -172,6 +172,34 @@ def test_quotient_refuses_bad_arguments(sb, lib):
     assert rc(a5=case["omega"] * case["omega"] % P) == 2          # BFS_ERR_NOT_ROOT
 
 
+def test_points_in_another_order_and_an_unused_point_change_no_word(sb, lib, oracle):
+    """the entry gives a launch the points its pairs name, in order of first appearance: the plan's points in another order, or with a
+    point that no pair names behind them, give the same words (field arithmetic is exact) and nothing beside them.  An unused point
+    is still checked: unreduced, it is refused"""
+    from stark_brainfuck_amd.device import current_stream
+    N = 64
+    case = cases.plan_tables(N)
+    buffers = [_upload(c) for c in case["columns"]]
+    points, pair_point = list(case["plan"].points), cases.kernel_arguments(case)["pair_point"]
+    assert len(points) == 3 and pair_point == [0, 1, 0, 2, 0]
+
+    def call(points, pair_point):
+        arena = Arena(batch=3, stride=N + 40, n=N)
+        args = _quotient_call(case, buffers, arena.ptr, N + 40, current_stream())          # (pair_values stay: the pairs keep their order)
+        args[9], args[10], args[11] = _flat(points), len(points), (u32 * len(pair_point))(*pair_point)
+        return lib.bfsx_deep_quotient_groups(*args), arena
+    order = [2, 0, 1]                                 # place i of the permuted array holds point order[i]
+    spare = cases.random_points(oracle, 4242, 1)[0]
+    assert spare not in points and all(v < P for v in spare)
+    for other_points, other_pairs in (([points[p] for p in order], [order.index(p) for p in pair_point]), (points + [spare], pair_point)):
+        rc, arena = call(other_points, other_pairs)
+        assert rc == 0
+        assert np.array_equal(arena.rows(arena.contained()), case["g"])
+    rc, arena = call(points + [(P, 0, 0)], pair_point)
+    assert rc == 6
+    assert np.array_equal(arena.contained(), arena.image)          # a refused call enqueues nothing
+
+
 # ------------------------------------------------------------------------------------------------ 3. stream order
 def test_both_entries_keep_to_their_stream(sb):
     """tests/pcs_groups_stream_child.py, once, in a child process under its own time limit"""

@@ -104,6 +104,16 @@ def test_a_zero_polynomial_is_opened(sb, oracle):
     assert _package_verdict(sb, 64, "default", proof["bytes"], proof["root"], proof["points"], proof["values"]) is True
 
 
+def test_a_point_given_twice_is_opened_twice(sb, oracle):
+    """`open` and `verify` have no rule against points = [z, z] (an OpeningPlan has): two quotient terms over the same denominator,
+    values[0] == values[1].  Both verifiers accept the model's proof; tests/test_gpu_pcs.py holds the prover to the same bytes"""
+    proof = cases.model_proof(64, "default", 2, repeated=True)
+    assert proof["points"][0] == proof["points"][1] and proof["values"][0] == proof["values"][1]
+    assert _model_verdict(sb, oracle, proof) == (True, "accepted")
+    assert _package_verdict(sb, 64, "default", proof["bytes"], proof["root"], proof["points"], proof["values"]) is True
+    assert _package_verdict(sb, 64, "default", proof["bytes"], proof["root"], proof["points"][:1], proof["values"][:1]) is False      # (another statement)
+
+
 # ------------------------------------------------------------------------------------------------ 3. refuse
 def _bump(sb, element):
     limbs = element.limbs()

@@ -106,6 +106,20 @@ def test_the_split_is_the_rules_in_plan_order_within_every_limit(emu, name):
         assert broken[name] and sum(broken[k] for k in ("by_columns", "by_groups", "by_pairs", "by_points")) == (2 if name == "by_points" else 1)
 
 
+@pytest.mark.parametrize("name", ["plan_max", "plan_tables"])
+def test_a_plan_within_the_one_launch_limits_is_one_launch_with_its_points_in_order(emu, name):
+    """bfsx_deep_quotient_groups goes through the same split: every bound of the split is one of its limits, so its plans -- the one at
+    every limit at once among them -- are one launch of all groups, columns and pairs, the points 0 .. n_points - 1 as the plan has them"""
+    import pcs_groups_cases as gcases
+    plan = getattr(gcases, name)(64)["plan"]
+    if name == "plan_max":
+        assert (plan.m, len(plan.groups), len(plan.points), sum(len(i) for _, i in plan.groups)) == (32, 8, 8, 16)
+    launches = emulated_split(emu, plan)
+    assert len(launches) == 1
+    assert launches[0] == {"groups": list(range(len(plan.groups))), "first_column": 0, "columns": plan.m, "first_pair": 0,
+                           "pairs": sum(len(i) for _, i in plan.groups), "points": list(range(len(plan.points)))}
+
+
 def test_the_split_refuses_what_the_entry_refuses(emu):
     z = [(1 + i, 2, 3) for i in range(25)]
     assert emulated_split(emu, gmodel.Plan([([c], [z[0]]) for c in range(24)])) is not None

@@ -14,6 +14,7 @@ class InstructionTable(Table):
 
     def __init__(self, field, length, num_randomizers, generator, order):
         super().__init__(field, 3, 5, length, num_randomizers, generator, order)
+        self.permutation_terminal = self.evaluation_terminal = None      # after extend() / extend_device(): limb triples
 
     def pad(self):
         rows, last = self._rows_and_last()

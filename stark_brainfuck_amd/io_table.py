@@ -12,6 +12,7 @@ class IOTable(Table):
 
     def __init__(self, field, length, generator, order):
         super().__init__(field, 1, 2, length, 0, generator, order)
+        self.evaluation_terminal = None      # after extend() / extend_device(): limb triple
 
     def pad(self):
         self.length, _ = self._rows_and_last()

@@ -13,6 +13,7 @@ class MemoryTable(Table):
 
     def __init__(self, field, length, num_randomizers, generator, order):
         super().__init__(field, 4, 5, length, num_randomizers, generator, order)
+        self.permutation_terminal = None      # after extend() / extend_device(): limb triple
 
     @staticmethod
     def derive_matrix(processor_matrix):

@@ -16,6 +16,11 @@ class ProcessorTable(Table):
 
     def __init__(self, field, length, num_randomizers, generator, order):
         super().__init__(field, 7, 11, length, num_randomizers, generator, order)
+        self._reads = self._writes = None                # row masks of the input / output evaluations (_scans)
+        # after extend() / extend_device(): the final values of the four extension columns, as limb triples ...
+        self.instruction_permutation_terminal = self.memory_permutation_terminal = None
+        self.input_evaluation_terminal = self.output_evaluation_terminal = None
+        self.evaluation_terminal_identities = None       # ... and what the reference's objects of the last two are made of (_identity)
 
     def pad(self):
         rows, last = self._rows_and_last()

@@ -2,8 +2,8 @@
 steps on the GPU:
 
   interpolate_columns + lde / ldex   (:112-148)  INTT over the omicron subgroup, rank-one randomizer correction
-                                                 (bfs_poly_randomize), coset NTT onto the FRI domain -- per table one
-                                                 batched call over all columns, codewords stay in HBM
+                                                 (bfs_poly_randomize), coset NTT onto the FRI domain -- `lde_tables`, one
+                                                 batched call over the columns of all tables, codewords stay in HBM
   extend                             (per table)  the running products / evaluations as scan specs (`_scans`): `extend_device`
                                                  runs them as prefix scans on the trace columns in HBM (bfs_xfe_scan_device),
                                                  `extend` on the host primitive (bfs_xfe_scan) for the reference's call surface
@@ -18,16 +18,20 @@ when `extend` (not `extend_device`) made them.
 """
 import ctypes
 import itertools
+import os
 from collections import namedtuple
+from concurrent.futures import Future, ThreadPoolExecutor
 from os import urandom          # module-level on purpose: tests patch `table.urandom` for determinism
-from .randomness import source as random_source
 
 import numpy as np
 
 from . import _lib, air
 from .algebra import BaseFieldElement
 from .arrays import raw_ntt
-from .device import DeviceBuffer, current_stream
+from .device import DeviceBuffer, DeviceView, GatherBatch, current_stream, pinned_empty
+from .extension_field import ExtensionField
+from .multivariate import MPolynomial
+from .randomness import source as random_source
 
 _ARRAY_GENERATION = itertools.count(1)      # keys of Table's per-matrix caches: never reused
 
@@ -40,6 +44,20 @@ LDE_GROUP_MIN_LOG_N = 20
 
 def _val(x):
     return x.value if hasattr(x, "value") else int(x)
+
+
+def _triple(v):
+    """an extension element as a tuple of three integers: from an element object (limbs()) or from any sequence of three"""
+    return tuple(v.limbs()) if hasattr(v, "limbs") else tuple(int(x) for x in v)
+
+
+def _air_arguments(table, challenges, terminals):
+    """the 11 challenges, the 5 terminals and `table`'s AIR parameter (None for a table without one) as the blocks of limbs the AIR entry
+    points of the library take -> (ch, tm, pr)"""
+    challenges = [_triple(c) for c in challenges]
+    params = table.air_params(challenges)
+    return ((_u64 * 33)(*[v for c in challenges for v in c]), (_u64 * 15)(*[v for t in terminals for v in _triple(t)]),
+            (_u64 * 3)(*params[0]) if params else None)
 
 
 _INVERSES = {}
@@ -107,8 +125,6 @@ _THREAD_ROWS = 1 << 14
 
 def _scan_pool():
     if "scan" not in _POOLS:
-        import os
-        from concurrent.futures import ThreadPoolExecutor
         _POOLS["scan"] = ThreadPoolExecutor(max_workers=max(2, min(9, os.cpu_count() or 2)), thread_name_prefix="bfs-scan")
     return _POOLS["scan"]
 
@@ -120,7 +136,6 @@ def extend_all(tables, challenges, initials):
             t.extend(challenges, initials)
         return
     if "tables" not in _POOLS:
-        from concurrent.futures import ThreadPoolExecutor
         _POOLS["tables"] = ThreadPoolExecutor(max_workers=5, thread_name_prefix="bfs-extend")
     for future in [_POOLS["tables"].submit(t.extend, challenges, initials) for t in tables]:
         future.result()
@@ -133,24 +148,28 @@ def _cache_key(t):
 def prepare_extension(tables):
     """the challenge-independent part of extend_tables_device -- row masks computed and queued for upload -- done ahead of time; returns
     a token for extend_tables_device (or None when there is nothing to prepare)"""
-    lib, stream = _lib.load(), current_stream()
-    masks = []
-    for t in tables:
-        if t.height:
-            masks += [np.ascontiguousarray(m, dtype=np.uint8) for m in t._scan_masks() if m is not None]
+    d_masks = _upload_masks([m for t in tables if t.height for m in t._scan_masks()])
+    if d_masks is None:
+        return None
+    return {"d_masks": d_masks, "keys": [_cache_key(t) for t in tables]}
+
+
+def _upload_masks(masks):
+    """row masks of scans (None entries: every row, nothing to upload) as bytes, back to back in one device buffer; None without a mask"""
+    masks = [np.ascontiguousarray(m, dtype=np.uint8) for m in masks if m is not None]
     if not masks:
         return None
-    host = staging_empty(((sum(m.size for m in masks) + 7) // 8,)).view(np.uint8)
-    np.concatenate(masks, out=host[:sum(m.size for m in masks)])
+    size = sum(m.size for m in masks)
+    host = staging_empty(((size + 7) // 8,)).view(np.uint8)
+    np.concatenate(masks, out=host[:size])
     d_masks = DeviceBuffer(host.size // 8)
-    _lib.check(lib.bfs_memcpy_h2d(d_masks.ptr, host.ctypes.data, host.size, stream))
-    return {"d_masks": d_masks, "host": host, "keys": [_cache_key(t) for t in tables]}
+    _lib.check(_lib.load().bfs_memcpy_h2d(d_masks.ptr, host.ctypes.data, host.size, current_stream()))
+    return d_masks
 
 
 def extend_tables_device(tables, all_challenges, all_initials, prepared=None):
     """Table.extend_device for several tables with ONE upload (all row masks), ONE read-back of the terminals and one gather for
     the values the tables look up afterwards -- a proof has nine scans over five tables, and every separate copy is a round trip."""
-    from .device import GatherBatch
     lib, stream = _lib.load(), current_stream()
     plans, masks = [], []
     use_prepared = prepared is not None and prepared["keys"] == [_cache_key(t) for t in tables]
@@ -162,14 +181,9 @@ def extend_tables_device(tables, all_challenges, all_initials, prepared=None):
         assert t.height == 0 or t._base_device is not None, "extend_device() follows lde()"
         plans.append((t, specs))
         if t.height and not use_prepared:
-            masks += [np.ascontiguousarray(sp["mask"], dtype=np.uint8) for sp in specs if sp["mask"] is not None]
-    d_masks = None
-    if use_prepared:
-        d_masks = prepared["d_masks"]           # (same tables, same padded matrices: the masks are already on their way)
-    elif masks:
-        host = np.concatenate(masks)
-        d_masks = DeviceBuffer((host.size + 7) // 8)
-        _lib.check(lib.bfs_memcpy_h2d(d_masks.ptr, host.ctypes.data, host.size, stream))
+            masks += [sp["mask"] for sp in specs]
+    # (prepared for the same tables and the same padded matrices: the masks are in HBM already)
+    d_masks = prepared["d_masks"] if use_prepared else _upload_masks(masks)
     total = sum(len(specs) for _, specs in plans)
     d_terminals = DeviceBuffer(3 * max(total, 1))
     mask_at, slot, batch_specs = 0, 0, []
@@ -206,48 +220,45 @@ def extend_tables_device(tables, all_challenges, all_initials, prepared=None):
                         lambda k, row, t=t: tuple(int(v) for v in batch.words(read_tickets[(t, k, row)])))
 
 
+def _draw_randomizers(table, extension):
+    """the values `table`'s interpolants take at the point omega, one per base column or one limb triple per extension column, from
+    24 random bytes per column in column order (table.py:119-125 of the reference) -- or None for a table without randomizer or rows"""
+    if not (table.height and table.num_randomizers):
+        return None
+    if extension:
+        return [v for _ in range(table.full_width - table.base_width) for v in sample_ext(random_source(urandom)(3 * 8))]
+    return [sample_base(random_source(urandom)(3 * 8)) for _ in range(table.base_width)]
+
+
 def lde_tables(tables, domain, extension=False):
-    """Table.lde (extension=False) or Table.ldex (True) of several tables with ONE transform onto the FRI domain: every table still
-    interpolates its own columns (its own subgroup), into a shared coefficient buffer, but the coset evaluation -- the same
-    N-point transform for all of them -- runs once over all columns (three launches instead of three per table; on short traces the
-    launches are the cost).  Randomizers are drawn table by table, column by column, as the separate calls draw them."""
+    """The low-degree extension of the base columns (extension=False) or the extension columns (True) of several tables -- Table.lde /
+    Table.ldex are the calls with one table -- with ONE transform onto the FRI domain: every table interpolates its own columns (its
+    own subgroup) into its rows of a shared coefficient buffer, and the coset evaluation -- the same N-point transform for all of them
+    -- runs once over all columns (three launches instead of three per table; on short traces the launches are the cost).
+    Randomizers are drawn table by table, column by column.  A table without rows gets zero codewords, one without columns an empty
+    buffer; either may be true of every table."""
     lib, stream = _lib.load(), current_stream()
     n = domain.length
     log_n = n.bit_length() - 1
     widths = [3 * (t.full_width - t.base_width) if extension else t.base_width for t in tables]
-    total, hmax = sum(widths), max(t.height for t in tables)
-    if total == 0 or hmax == 0:
-        for t in tables:
-            t.ldex(domain) if extension else t.lde(domain)
-        return
+    total, hmax = sum(widths), max([t.height for t in tables], default=0)
     randomized = any(t.height and t.num_randomizers for t in tables)
     stride = hmax + 1
     n_in = hmax + 1 if randomized else hmax
     assert n_in <= n, "interpolant does not fit the FRI domain"
-    coeffs = DeviceBuffer(total * stride)
-    _lib.check(lib.bfs_memset(coeffs.ptr, 0, coeffs.nbytes, stream))
-    out = DeviceBuffer(total * n)
     omega, offset = domain.omega.value, domain.offset.value
+    out = DeviceBuffer(total * n)
+    coeffs = None          # stays None when no table has a row or none has a column: nothing to transform
+    if total and hmax:
+        coeffs = DeviceBuffer(total * stride)
+        _lib.check(lib.bfs_memset(coeffs.ptr, 0, coeffs.nbytes, stream))
     at, inputs = 0, []
     for t, w in zip(tables, widths):
         h = t.height
         d_in = None
         if h and w:
-            if extension:
-                if getattr(t, "_ext_device", None) is not None:      # after extend_device(): already in HBM, (column, limb) planes
-                    d_in = t._ext_device
-                else:
-                    cols = staging_empty((w, h))
-                    np.concatenate(t.ext_columns, axis=0, out=cols)
-                    d_in = DeviceBuffer.from_numpy(cols.reshape(-1))
-            else:
-                d_in = DeviceBuffer.from_numpy(t.base_array().reshape(-1))
-            rand = None
-            if t.num_randomizers:
-                if extension:
-                    rand = [v for _ in range(w // 3) for v in sample_ext(random_source(urandom)(3 * 8))]
-                else:
-                    rand = [sample_base(random_source(urandom)(3 * 8)) for _ in range(w)]
+            d_in = t._ext_planes() if extension else DeviceBuffer.from_numpy(t.base_array().reshape(w * h))
+            rand = _draw_randomizers(t, extension)
             mine = coeffs.ptr + 8 * at * stride
             raw_ntt(d_in.ptr, h, h, mine, stride, h.bit_length() - 1, w, _inv(t.omicron.value), 1, _inv(h), stream)
             if rand is not None:
@@ -255,13 +266,15 @@ def lde_tables(tables, domain, extension=False):
         inputs.append(d_in)
         at += w
     masks = None
-    if extension:      # see Table.ext_sharing_moduli: a per-polynomial summary of the support
+    if extension and coeffs is not None:      # see Table.ext_sharing_moduli: a per-polynomial summary of the support
         # (read back BEFORE the big transform is queued: the read waits for what is in front of it on the stream, and the transform --
         # most of this function's GPU time -- then runs while the caller goes on with host work)
         raw = (_u64 * total)()
         _lib.check(lib.bfs_poly_support(coeffs.ptr, stride, n_in, total, raw, stream))
         masks = [int(v) for v in raw]
-    if log_n < LDE_GROUP_MIN_LOG_N:
+    if coeffs is None:
+        _lib.check(lib.bfs_memset(out.ptr, 0, out.nbytes, stream))
+    elif log_n < LDE_GROUP_MIN_LOG_N:
         raw_ntt(coeffs.ptr, n_in, stride, out.ptr, n, log_n, total, omega, offset, 1, stream)
     else:
         # large domains: one call per run of tables with the same coefficient count (csrc/prover.cpp: lde_all_tables does the same on the
@@ -273,18 +286,16 @@ def lde_tables(tables, domain, extension=False):
             if cols:
                 raw_ntt(coeffs.ptr + 8 * first * stride, min(max(count, 1), n_in), stride, out.ptr + 8 * first * n, n, log_n, cols, omega, offset, 1, stream)
             first += cols
-    from .device import DeviceView
     at = 0
     for t, w, d_in in zip(tables, widths, inputs):
         view = DeviceView(out, at * n, w * n)
         t._n = n
         if extension:
             t.ext_codewords = view
-            t._coefficients = masks[at:at + w] if t.height else None
+            t._coefficients = masks[at:at + w] if masks is not None and t.height else None
         else:
             t.base_codewords = view
             t._base_device = d_in          # the trace columns stay in HBM for extend_device()
-        t._last_input = None
         at += w
 
 
@@ -330,7 +341,6 @@ def staging_empty(shape):
     """uint64 array for data on its way to HBM: pinned memory from the library's pool when there is a GPU, plain numpy otherwise"""
     if _POOLS.get("pinned", True):
         try:
-            from .device import pinned_empty
             return pinned_empty(shape)
         except Exception:
             _POOLS["pinned"] = False
@@ -416,6 +426,13 @@ class Table:
         self._coefficients = None    # host copy of the last interpolants (ext_sharing_moduli)
         self._base_device = None     # DeviceBuffer, base_width * height: the trace columns as uploaded by lde()
         self._ext_device = None      # DeviceBuffer, (full_width - base_width) * 3 * height: extension columns made by extend_device()
+        self._n = None               # length of the domain the codewords are on (ext_codeword_ptr)
+        self._array = None           # base columns of `matrix` as a uint64 array (base_width, rows): base_array()
+        self._array_for = None       # the matrix object `_array` was made from ...
+        self._array_rows = -1        # ... and its row count then
+        self._array_key = None       # generation number of `_array`: key of what is derived from it
+        self._masks = None           # row masks of the scans (_scan_masks) ...
+        self._mask_key = None        # ... and the `_array_key` they were computed for
 
     @staticmethod
     def roundup_npo2(integer):
@@ -462,7 +479,7 @@ class Table:
     # per MATRIX OBJECT.  The cache holds a reference to that object and compares with `is`, and hands out a generation number that is
     # never reused as its key: id() of a freed matrix can come back for the next one of the same height (round-3 advice).
     def _array_current(self):
-        return getattr(self, "_array_for", None) is self.matrix and getattr(self, "_array_rows", -1) == len(self.matrix)
+        return self._array_for is self.matrix and self._array_rows == len(self.matrix)
 
     def _set_array(self, arr):
         self._array, self._array_for, self._array_rows = arr, self.matrix, len(self.matrix)
@@ -476,7 +493,7 @@ class Table:
         only, not on the challenges, so the prover computes and uploads them while the GPU is busy with the base columns' low-degree
         extension (prepare_extension) instead of between the first commitment and the scans"""
         key = self._array_key if self._array_current() else None
-        if getattr(self, "_mask_key", None) != key or key is None:
+        if self._mask_key != key or key is None:
             self._masks, self._mask_key = self._make_scan_masks(), key
         return self._masks
 
@@ -577,48 +594,34 @@ class Table:
         columns, mask = args[1], args[2]
         rows = next((len(c) for c in columns if c is not None), 0 if mask is None else len(mask))
         if rows < _THREAD_ROWS:                  # short traces: waking a worker costs more than the scan
-            from concurrent.futures import Future
             done = Future()
             done.set_result(Table.scan(*args))
             return done
         return _scan_pool().submit(Table.scan, *args)
 
-    # ---- interpolation + low-degree extension (table.py:112-148)
-    def _extend_columns(self, domain, columns, randomizers, keep_coefficients=False):
-        """columns: uint64 array (ncol, height); randomizers: ncol values at the point omega (or None).
-        Returns the codewords over `domain` as one DeviceBuffer of ncol * N words."""
-        lib, stream = _lib.load(), current_stream()
+    # ---- interpolation + low-degree extension (table.py:112-148): lde_tables above, called with one table
+    def lde(self, domain):
+        lde_tables([self], domain)
+        return self.base_codewords
+
+    def ldex(self, domain, xfield=None):
+        lde_tables([self], domain, extension=True)
+        return self.ext_codewords
+
+    def _ext_planes(self):
+        """the extension columns as limb planes in HBM, (3 * (full_width - base_width), height): where extend_device() left them, or
+        extend()'s ext_columns -- one (3, rows) array per column -- uploaded"""
+        if self._ext_device is not None:
+            return self._ext_device
+        cols = staging_empty((3 * (self.full_width - self.base_width), self.height))
+        np.concatenate(self.ext_columns, axis=0, out=cols)
+        return DeviceBuffer.from_numpy(cols.reshape(-1))
+
+    def _domain_arguments(self, domain):
+        """what the kernels over `domain` need to know of it and of this table's place in it: log2 of its length, the table's unit
+        distance, height and 1 / omicron, the domain's offset and generator -- in the order the library takes them"""
         n = domain.length
-        self._n = n
-        log_n = n.bit_length() - 1
-        ncol, h = (columns.count // self.height if self.height else 0) if isinstance(columns, DeviceBuffer) else columns.shape[0], self.height
-        out = DeviceBuffer(ncol * n)
-        self._coefficients = None
-        if ncol == 0:
-            return out
-        if h == 0:
-            _lib.check(lib.bfs_memset(out.ptr, 0, out.nbytes, stream))
-            return out
-        omega, offset = domain.omega.value, domain.offset.value
-        coeffs = DeviceBuffer(ncol * (h + 1))
-        _lib.check(lib.bfs_memset(coeffs.ptr, 0, coeffs.nbytes, stream))
-        d_in = columns if isinstance(columns, DeviceBuffer) else DeviceBuffer.from_numpy(columns.reshape(-1))
-        self._last_input = d_in
-        omicron_inv = _inv(self.omicron.value)
-        raw_ntt(d_in.ptr, h, h, coeffs.ptr, h + 1, h.bit_length() - 1, ncol, omicron_inv, 1, _inv(h), stream)
-        n_in = h
-        self._coefficients = None
-        if randomizers is not None:
-            vals = (_u64 * ncol)(*[int(v) for v in randomizers])
-            _lib.check(lib.bfs_poly_randomize(coeffs.ptr, h + 1, h, ncol, omega, vals, stream))
-            n_in = h + 1
-        assert n_in <= n, "interpolant does not fit the FRI domain"
-        raw_ntt(coeffs.ptr, n_in, h + 1, out.ptr, n, log_n, ncol, omega, offset, 1, stream)
-        if keep_coefficients:      # see ext_sharing_moduli: only a per-polynomial summary of the support comes back
-            masks = (_u64 * ncol)()
-            _lib.check(lib.bfs_poly_support(coeffs.ptr, h + 1, n_in, ncol, masks, stream))
-            self._coefficients = [int(v) for v in masks]
-        return out
+        return n.bit_length() - 1, self.unit_distance(n), self.height, _inv(self.omicron.value), domain.offset.value, domain.omega.value
 
     def ext_sharing_moduli(self, n):
         """Object identity inside the reference's extension codewords.  Its recursive ntt() adds `evens + w^i * odds`
@@ -644,35 +647,6 @@ class Table:
                 out.append(n >> v if v else None)
         return out
 
-    def lde(self, domain):
-        cols = self.base_array().reshape(self.base_width, self.height)
-        rand = None
-        if self.height != 0 and self.num_randomizers:
-            rand = [sample_base(random_source(urandom)(3 * 8)) for _ in range(self.base_width)]
-        self._last_input = None
-        self.base_codewords = self._extend_columns(domain, cols, rand)
-        self._base_device = self._last_input          # the trace columns stay in HBM for extend_device()
-        self._last_input = None
-        return self.base_codewords
-
-    def ldex(self, domain, xfield=None):
-        width = self.full_width - self.base_width
-        if self.height and getattr(self, "_ext_device", None) is not None:   # after extend_device(): already in HBM, (column, limb) planes
-            cols = self._ext_device
-        elif self.height:      # ext_columns: one (3, rows) array per extension column -> (column, limb) planes
-            cols = staging_empty((3 * width, self.height))
-            np.concatenate(self.ext_columns, axis=0, out=cols)
-        else:
-            cols = np.zeros((width * 3, 0), dtype=np.uint64)
-        rand = None
-        if self.height != 0 and self.num_randomizers:
-            rand = []
-            for _ in range(width):
-                rand.extend(sample_ext(random_source(urandom)(3 * 8)))
-        self.ext_codewords = self._extend_columns(domain, cols, rand, keep_coefficients=True)
-        self._last_input = None
-        return self.ext_codewords
-
     def ext_codeword_ptr(self, column):
         """device pointer of extension column `column` (full-width numbering): three limb planes of N words"""
         return self.ext_codewords.ptr + 8 * 3 * (column - self.base_width) * self._n
@@ -688,14 +662,8 @@ class Table:
         n = domain.length
         nq = lib.bfs_air_num_quotients(self.table_index)
         out = DeviceBuffer(nq * 3 * n)
-        ch = (_u64 * 33)(*[v for c in challenges for v in c])
-        tm = (_u64 * 15)(*[v for t in terminals for v in t])
-        params = self.air_params(challenges)
-        pr = (_u64 * 3)(*params[0]) if params else None
-        omicron_inv = _inv(self.omicron.value)
         _lib.check(lib.bfs_air_quotients(self.table_index, self.base_codewords.ptr, self.ext_codewords.ptr, out.ptr,
-                                         n.bit_length() - 1, self.unit_distance(n), self.height, omicron_inv,
-                                         domain.offset.value, domain.omega.value, ch, tm, pr, stream))
+                                         *self._domain_arguments(domain), *_air_arguments(self, challenges, terminals), stream))
         return out
 
     def combine_into(self, domain, challenges, terminals, weights, accumulator, randomizer=None, randomizer_weight=None, inverses=None, rows=None):
@@ -716,13 +684,8 @@ class Table:
             ws = (_lib.CombWeight * len(weights))()
             for w, (wa, wb, shift) in zip(ws, weights):
                 w.wa, w.wb, w.shift = (_u64 * 3)(*wa), (_u64 * 3)(*wb), shift
-        ch = (_u64 * 33)(*[v for c in challenges for v in c])
-        tm = (_u64 * 15)(*[v for t in terminals for v in t])
-        params = self.air_params(challenges)
-        pr = (_u64 * 3)(*params[0]) if params else None
-        omicron_inv = _inv(self.omicron.value)
-        _lib.check(lib.bfs_air_combine_rows(self.table_index, self.base_codewords.ptr, self.ext_codewords.ptr, n.bit_length() - 1,
-                                            self.unit_distance(n), self.height, omicron_inv, domain.offset.value, domain.omega.value, ch, tm, pr,
+        _lib.check(lib.bfs_air_combine_rows(self.table_index, self.base_codewords.ptr, self.ext_codewords.ptr,
+                                            *self._domain_arguments(domain), *_air_arguments(self, challenges, terminals),
                                             ws, randomizer.ptr if randomizer is not None else None,
                                             (_u64 * 3)(*randomizer_weight) if randomizer is not None else None, accumulator.ptr,
                                             (ctypes.c_void_p * 3)(*inverses) if inverses is not None else None, first, count, stream))
@@ -807,14 +770,9 @@ class Table:
 
     # ---- the constraints as the reference presents them: lists of MPolynomial (table.py:145-146, 173-174, 248-249)
     def _constraints_ext(self, kind, challenges, terminals=None):
-        from .extension_field import ExtensionField
-        from .multivariate import MPolynomial
         xfield = challenges[0].field if hasattr(challenges[0], "field") else ExtensionField.main()
-
-        def triple(v):
-            return tuple(v.limbs()) if hasattr(v, "limbs") else tuple(v)
-        ch = [triple(c) for c in challenges]
-        tm = [triple(t) for t in terminals] if terminals is not None else [air.X0] * 5
+        ch = [_triple(c) for c in challenges]
+        tm = [_triple(t) for t in terminals] if terminals is not None else [air.X0] * 5
         nvars = 2 * self.full_width if kind == "transition" else self.full_width
         memo, out = {}, []
         for e in dict(self.air.all())[kind]:
@@ -833,7 +791,6 @@ class Table:
 
     # ---- the base AIR as the reference presents it (processor_table.py:123-201, instruction_table.py:27-56, memory_table.py:46-112)
     def _constraints_base(self, kind):
-        from .multivariate import MPolynomial
         nvars = 2 * self.base_width if kind == "transition" else self.base_width
         zeros, memo, out = [air.X0] * 11, {}, []
         for e in dict(self.air.base())[kind]:
@@ -870,26 +827,18 @@ class Table:
                 d_base = keep[-1].ptr
         else:
             assert terminals is not None, "the full AIR needs the terminals"
-
-            def triple(v):
-                return tuple(v.limbs()) if hasattr(v, "limbs") else tuple(int(x) for x in v)
-            challenges = [triple(c) for c in challenges]
-            ch = (_u64 * 33)(*[v for c in challenges for v in c])
-            tm = (_u64 * 15)(*[v for t in terminals for v in triple(t)])
-            params = self.air_params(challenges)
-            pr = (_u64 * 3)(*params[0]) if params else None
+            ch, tm, pr = _air_arguments(self, challenges, terminals)
             rows = self.height
-            xw = self.full_width - self.base_width
             if rows and self._ext_device is not None:            # after extend_device(): both sets of columns are in HBM already
                 assert self._base_device is not None and self._base_device.count >= self.base_width * rows
-                d_base, d_ext = self._base_device.ptr, self._ext_device.ptr
+                keep.append(self._base_device)
             elif rows:
                 assert self.ext_columns is not None, "the full AIR is checked after extend() or extend_device()"
                 arr = np.ascontiguousarray(self.base_array())
                 assert arr.shape[1] == rows, "the full AIR is checked on the padded table"
-                cols = np.empty((3 * xw, rows), dtype=np.uint64)
-                np.concatenate(self.ext_columns, axis=0, out=cols)
-                keep += [DeviceBuffer.from_numpy(arr.reshape(-1)), DeviceBuffer.from_numpy(cols.reshape(-1))]
+                keep.append(DeviceBuffer.from_numpy(arr.reshape(-1)))
+            if rows:
+                keep.append(self._ext_planes())
                 d_base, d_ext = keep[0].ptr, keep[1].ptr
             else:
                 d_base = None
@@ -926,13 +875,11 @@ class Table:
         lib = _lib.load()
         bw, xw = self.base_width, self.full_width - self.base_width
         nb, nt, nz = (len(c) for _, c in self.air.all())
-        params = self.air_params(challenges)
         out = (_u64 * (3 * (nb + nt + nz)))()
         _lib.check(lib.bfs_air_evaluate(
             self.table_index, (_u64 * bw)(*[p[0] for p in point[:bw]]), (_u64 * bw)(*[p[0] for p in next_point[:bw]]),
             (_u64 * (3 * xw))(*[v for p in point[bw:] for v in p]), (_u64 * (3 * xw))(*[v for p in next_point[bw:] for v in p]),
-            (_u64 * 33)(*[v for c in challenges for v in c]), (_u64 * 15)(*[v for t in terminals for v in t]),
-            (_u64 * 3)(*params[0]) if params else None, out))
+            *_air_arguments(self, challenges, terminals), out))
         vals = [tuple(out[3 * q:3 * q + 3]) for q in range(nb + nt + nz)]
         return vals[:nb], vals[nb:nb + nt], vals[nb + nt:]
 

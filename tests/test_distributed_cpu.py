@@ -81,12 +81,13 @@ def test_assignment_is_a_partition():
 def _base_codewords_by_the_oracle(name):
     """the 17 columns of the reference's first commitment (brainfuck_stark.py:162-180) for golden `name`, recomputed on the CPU:
     the product's host code pads the trace and samples the randomizers from the golden's byte stream, the oracle interpolates
-    (INTT over the omicron subgroup + the rank-one randomizer correction) and evaluates on the FRI coset.  Returns
+    (INTT over the omicron subgroup + the rank-one randomizer correction) and evaluates on the FRI coset (lde_by_the_oracle).  Returns
     (golden, planes, [uint64 array (planes, n)], salts)."""
     import hashlib
     import json
     import sys
     sys.path.insert(0, ROOT)
+    from lde_by_the_oracle import column_codeword
     from oracle import ref_oracle as o
     from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
     from stark_brainfuck_amd.table import sample_base, sample_ext_many
@@ -98,7 +99,6 @@ def _base_codewords_by_the_oracle(name):
     def urandom(k):
         pos[0] += k
         return buf[pos[0] - k:pos[0]]
-    P = o.P
     program = VirtualMachine.compile(g["program"])
     running_time, inputs, outputs = VirtualMachine.run(program, input_data=list(g["input"]))
     pm, mm, im, inm, om = VirtualMachine.simulate(program, input_data=list(inputs))
@@ -120,17 +120,8 @@ def _base_codewords_by_the_oracle(name):
             if h == 0:
                 columns.append(np.zeros((1, n), dtype=np.uint64))
             else:
-                f0 = o.intt(t.omicron.value, np.ascontiguousarray(cols[c]))
-                coeffs = np.zeros(h + 1, dtype=np.uint64)
-                coeffs[:h] = f0
-                if rand is not None:
-                    acc = 0
-                    for v in f0[::-1]:
-                        acc = (acc * omega + int(v)) % P                              # f0(omega)
-                    cc = (rand[c] - acc) * pow((pow(omega, h, P) - 1) % P, P - 2, P) % P
-                    coeffs[0] = (int(coeffs[0]) - cc) % P                             # f = f0 + c (X^h - 1)
-                    coeffs[h] = cc
-                columns.append(o.fast_coset_evaluate(coeffs, offset, omega, n).reshape(1, n))
+                codeword, _ = column_codeword(o, cols[c], t.omicron.value, rand[c] if rand is not None else None, offset, omega, n)
+                columns.append(codeword.reshape(1, n))
             planes.append(1)
     salts = urandom(24 * n)
     return g, planes, columns, salts

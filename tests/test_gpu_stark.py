@@ -557,6 +557,132 @@ def test_one_transform_for_all_tables_equals_one_per_table(code, inputs, monkeyp
     assert any(a.any() for a in base_a) and any(a.any() for a in ext_a)
 
 
+# per table (height, randomizers per column, base columns = extension columns); the last base column of a table with two is all zero
+LDE_SHAPES = [(8, 1, 2), (0, 1, 1), (1, 0, 1), (1, 1, 1), (2, 0, 1), (16, 1, 1)]
+# ("grouped": the oracle takes 0.1 .. 0.4 s per transform of 2^20 points, so one column per table: 4 + 12 transforms)
+LDE_CASES = {"small": (6, LDE_SHAPES), "every_table_empty": (6, [(0, 1, 2), (0, 0, 1)]),
+             "grouped": (20, [(8, 1, 1), (0, 1, 1), (1, 1, 1), (2, 0, 1), (16, 0, 1)])}
+LDE_EXPECTED = {}        # case -> what the oracle makes of it, computed by the first test that asks ("grouped" has one test: not kept)
+LDE_P = (1 << 64) - (1 << 32) + 1
+
+
+def _lde_case(case):
+    """-> (tables with random trace columns and one running evaluation over each as its extension, the domain)"""
+    from stark_brainfuck_amd.algebra import BaseField
+    from stark_brainfuck_amd.fri import Fri
+    from stark_brainfuck_amd.table import Table
+
+    class Columns(Table):
+        def _scans(self, all_challenges, all_initials):          # io_table.py:77-110 over every column
+            return [dict(kind=1, cols=[c], mask=None, constants=[all_challenges[c], (1, 0, 0)], initial=(0, 0, 0), before=False)
+                    for c in range(self.base_width)]
+
+        def _after_extend(self, terminals, all_challenges, read):
+            pass
+    log_n, shapes = LDE_CASES[case]
+    field, order = BaseField.main(), 1 << 32
+    tables = []
+    for k, (height, randomizers, width) in enumerate(shapes):
+        t = Columns(field, width, 2 * width, height, randomizers, field.primitive_nth_root(order), order)
+        values = np.random.default_rng(0x1DE + k).integers(0, LDE_P, size=(height, width), dtype=np.uint64)
+        if width == 2:
+            values[:, 1] = 0
+        t.matrix = values.tolist()
+        assert t.height == height
+        tables.append(t)
+    return tables, Fri.Domain(field.generator(), field.primitive_nth_root(1 << log_n), 1 << log_n)
+
+
+def _lde_expected(case, o, tables, domain, ext_columns):
+    """per table (base codewords (width, n), extension codewords (3 * width, n), sharing moduli) and the number of random bytes, by
+    lde_by_the_oracle on the tables' matrices and on `ext_columns` (per table the (3 * width, height) limb planes of its extension
+    columns), the randomizers read from the stream of this case as Table.lde / ldex of the reference read them: all base columns first,
+    24 bytes per column, then the extension columns, 24 bytes for the three limbs of each"""
+    from lde_by_the_oracle import column_codeword, sharing_modulus
+    if case in LDE_EXPECTED:
+        assert all(np.array_equal(a, b) for a, b in zip(LDE_EXPECTED[case]["ext_columns"], ext_columns)), "other extension columns than before"
+        return LDE_EXPECTED[case]
+    n, offset, omega = domain.length, domain.offset.value, domain.omega.value
+    stream = Stream(b"lde-oracle-" + case.encode())
+    drawn = {}
+    for extension in (False, True):
+        for t in tables:
+            if t.height and t.num_randomizers:
+                blocks = [stream(24) for _ in range(t.base_width)]
+                drawn[t, extension] = [int.from_bytes(b[8 * i:8 * i + 8] if extension else b, "big") % LDE_P
+                                       for b in blocks for i in range(3 if extension else 1)]
+    per_table = []
+    for t, planes in zip(tables, ext_columns):
+        w, h = t.base_width, t.height
+        if h == 0:
+            per_table.append((np.zeros((w, n), dtype=np.uint64), np.zeros((3 * w, n), dtype=np.uint64), [None] * w))
+            continue
+        trace = np.array(t.matrix, dtype=np.uint64).T
+        base = [column_codeword(o, trace[c], t.omicron.value, drawn[t, False][c] if (t, False) in drawn else None, offset, omega, n)[0]
+                for c in range(w)]
+        ext = [column_codeword(o, planes[c], t.omicron.value, drawn[t, True][c] if (t, True) in drawn else None, offset, omega, n)
+               for c in range(3 * w)]
+        per_table.append((np.stack(base), np.stack([e[0] for e in ext]),
+                          [sharing_modulus([e[1] for e in ext[3 * c:3 * c + 3]], n) for c in range(w)]))
+    expected = {"per_table": per_table, "bytes": stream.pos, "ext_columns": ext_columns}
+    if case != "grouped":
+        LDE_EXPECTED[case] = expected
+    return expected
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case, batched, on_device", [(case, batched, on_device) for case in ("small", "every_table_empty")
+                                                      for batched in (True, False) for on_device in (True, False)] + [("grouped", True, True)])
+def test_low_degree_extension_against_the_oracle(case, batched, on_device, monkeypatch, oracle):
+    """table.lde_tables (batched) and Table.lde / Table.ldex table by table, the extension columns from extend_tables_device (on_device:
+    in HBM) or from the host's extend (ext_columns), against the oracle: every codeword word, the trace columns kept in HBM, the sharing
+    moduli and the number of random bytes.  Heights 0, 1, 2, 8 and 16 with and without a randomizer in one call on 2^6 points (17
+    coefficients at most), an all-zero column with a randomizer (c (X^8 - 1): elements 8 apart share their objects), a call in which no
+    table has a row, and the two batched calls on 2^20 points, where lde_tables transforms run by run (coefficient counts 9, 0, 2, 2 and
+    16: four runs)."""
+    from stark_brainfuck_amd import table
+    from stark_brainfuck_amd.table import LDE_GROUP_MIN_LOG_N, extend_tables_device, lde_tables
+    tables, domain = _lde_case(case)
+    n = domain.length
+    assert (n.bit_length() - 1 >= LDE_GROUP_MIN_LOG_N) == (case == "grouped")
+    stream = Stream(b"lde-oracle-" + case.encode())
+    monkeypatch.setattr(table, "urandom", stream)
+    if batched:
+        lde_tables(tables, domain)
+    else:
+        for t in tables:
+            assert t.lde(domain) is t.base_codewords
+    base = [t.base_codewords.to_numpy(t.base_width * n).reshape(t.base_width, n) for t in tables]
+    kept = [None if t._base_device is None else t._base_device.to_numpy(t.base_width * t.height).reshape(t.base_width, t.height)
+            for t in tables]
+    challenges = tuple((3 + 7 * k + (1 << 40), 5 + k + (1 << 33), 11 * k + (1 << 35)) for k in range(11))
+    if on_device:
+        extend_tables_device(tables, challenges, [])
+        ext_columns = [t._ext_device.to_numpy(3 * t.base_width * t.height).reshape(3 * t.base_width, t.height) for t in tables]
+    else:
+        for t in tables:
+            t.extend(challenges, [])
+        ext_columns = [np.concatenate(t.ext_columns, axis=0) for t in tables]
+    assert all((t._ext_device is not None) == on_device and (t.ext_columns is not None) != on_device for t in tables)
+    if batched:
+        lde_tables(tables, domain, extension=True)
+    else:
+        for t in tables:
+            assert t.ldex(domain) is t.ext_codewords
+    want = _lde_expected(case, oracle, tables, domain, ext_columns)
+    assert stream.pos == want["bytes"] == 2 * 24 * sum(t.base_width for t in tables if t.height and t.num_randomizers)
+    for k, (t, (want_base, want_ext, want_moduli)) in enumerate(zip(tables, want["per_table"])):
+        assert np.array_equal(base[k], want_base), k
+        assert np.array_equal(t.ext_codewords.to_numpy(3 * t.base_width * n).reshape(3 * t.base_width, n), want_ext), k
+        if t.height:
+            assert np.array_equal(kept[k], np.array(t.matrix, dtype=np.uint64).T), k
+        else:
+            assert kept[k] is None and t._base_device is None and t._coefficients is None, k
+        assert t.ext_sharing_moduli(n) == want_moduli, k
+    if case == "small":
+        assert want["per_table"][0][2] == [None, n // 8] and want["per_table"][2][2] == [1]
+
+
 @pytest.mark.gpu
 def test_trace_padding_on_the_device():
     """bfs_trace_pad (csrc/scan.hip): the trace tables go up as the virtual machine wrote them (row-major, unpadded) and are padded,

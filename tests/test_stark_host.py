@@ -690,6 +690,41 @@ def test_native_constraint_evaluation_matches_the_expression_graphs():
             assert [[tuple(v) for v in part] for part in again] == [[tuple(v) for v in part] for part in got], (trial, type(table).__name__)
 
 
+def test_air_arguments_are_the_same_blocks_for_elements_and_triples():
+    """table._air_arguments (what all_quotients, combine_into, air_violations and evaluate_all_constraints hand to the library): challenges
+    and terminals given as ExtensionFieldElement objects, as tuples or as lists of integers make the same 33 + 15 words, in order; a
+    table with an AIR parameter (the input and output tables: challenge^(height - length)) gets its three words, the others None"""
+    import random
+    from stark_brainfuck_amd.air import xpow
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    from stark_brainfuck_amd.table import _air_arguments, _triple
+    from stark_brainfuck_amd.vm import VirtualMachine
+    P = (1 << 64) - (1 << 32) + 1
+    program = VirtualMachine.compile(",.,.,.")
+    running_time, inputs, outputs = VirtualMachine.run(program, input_data=["a", "b", "c"])
+    stark = BrainfuckStark(running_time, 8, program, inputs, outputs)
+    rnd = random.Random(20261020)
+    triples = [(rnd.randrange(P), rnd.randrange(P), rnd.randrange(P)) for _ in range(16)]
+    triples[3], triples[12] = (0, 0, 0), (P - 1, 0, 1)
+    elements = [stark.xfield.from_limbs(list(t)) for t in triples]
+    assert [_triple(e) for e in elements] == triples == [_triple(list(t)) for t in triples]
+    for table in stark.tables:
+        if table.air_params(triples[:11]):
+            table.length, table.height = 3, 4         # as IOTable.pad leaves them for three symbols
+        blocks = [_air_arguments(table, ch, tm) for ch, tm in ((triples[:11], triples[11:]), (elements[:11], elements[11:]),
+                                                               (tuple(list(t) for t in triples[:11]), [list(t) for t in triples[11:]]),
+                                                               (elements[:11], triples[11:]))]
+        ch, tm, pr = blocks[0]
+        assert list(ch) == [v for t in triples[:11] for v in t] and list(tm) == [v for t in triples[11:] for v in t]
+        assert len(ch) == 33 and len(tm) == 15
+        if table in (stark.input_table, stark.output_table):
+            assert list(pr) == list(xpow(triples[table.challenge_index], 1)) == list(triples[table.challenge_index])
+        else:
+            assert pr is None
+        for other in blocks[1:]:
+            assert [None if b is None else list(b) for b in other] == [list(ch), list(tm), None if pr is None else list(pr)]
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_verify_on_the_host_accepts_reference_proofs_and_rejects_tampering(name):
     """the verifier mirror (brainfuck_stark.py:343-579) on proofs written by the reference itself, WITHOUT a GPU: since round 4 the

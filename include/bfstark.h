@@ -386,7 +386,9 @@ int bfs_xfe_sample_fill(const uint8_t seed[32], uint64_t* d_out, uint64_t count,
  * (rows x row_stride words, the first `width` of a row are used): d_out receives the padded table COLUMN-major (width x height
  * words, residues reduced mod p), the masks one byte per row for the scans of the table's extension:
  *   kind 0 processor   (width >= 7): d_mask0 = current instruction != 0, d_mask1 = it is ',', d_mask2 = it is '.'
- *   kind 1 instruction (width >= 2): d_mask0 = rows of the running product, d_mask1 = rows of the running evaluation
+ *   kind 1 instruction (width >= 2): d_mask0 = rows of the running product (not padding, the address of the row above repeated),
+ *                                    d_mask1 = rows of the running evaluation (the first row of every address; the address "above"
+ *                                    row 0 is p - 1, instruction_table.py:184, so a table starting with p - 1 keeps row 0 out)
  *   kind 2 memory      (width >= 4): d_mask0 = non-dummy rows
  *   kind 3 / 4 input / output: padding rows are zero rows, no masks.
  * Masks a kind does not have are not written.  Stream-ordered; at most five tables per call.
@@ -562,6 +564,9 @@ int bfs_vm_trace_copy(void* trace, int which, uint64_t* out);
  *       kind 0: state <- state * (c0 - c1 x1[i] - c2 x2[i] - c3 x3[i])      kind 1: state <- state * c0 + c1 x1[i] + c2 x2[i] + c3 x3[i]
  *     on masked rows; out[i], out[n + i], out[2n + i] = limbs of the state before (record_before != 0) or after row i's update;
  *     terminal = final state.
+ *     The column words must be canonical (< p), here and for bfs_xfe_scan_device / bfs_xfe_scan_device_many: the row updates multiply
+ *     them as they stand.  bfs_trace_pad delivers its columns so (it reduces every word).  Constants and the initial state are
+ *     reduced mod p on entry; every output word is < p.
  */
 int bfs_xfe_scan(int kind, const uint64_t* x1, const uint64_t* x2, const uint64_t* x3, const uint8_t* mask, uint64_t n,
                  const uint64_t constants[12], const uint64_t initial[3], int record_before, uint64_t* out, uint64_t terminal[3]);

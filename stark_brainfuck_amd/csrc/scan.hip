@@ -8,8 +8,10 @@
 //   kind 1 (running evaluation):  s -> s * c0 + (c1 x1[i] + c2 x2[i] + c3 x3[i])
 // and maps compose associatively, so the column is a prefix scan: per-block aggregates (scan_reduce_kernel), one workgroup
 // scanning the <= 256 block aggregates (scan_spine_kernel), then every thread replays its rows from its own starting value
-// (scan_apply_kernel).  Same semantics as the host primitive bfs_xfe_scan (hostscan.cpp), which the tests compare it with;
-// the trace columns are already in HBM for the low-degree extension, and the extension columns never visit the host.
+// (scan_apply_kernel).  Same semantics as the host primitive bfs_xfe_scan (hostscan.cpp).  The tests compare both with two models
+// on plain integers: tests/scan_model.py (the primitive as include/bfstark.h defines it) and tests/extend_model.py (the reference's
+// loops, itself pinned on the reference's own output in tests/golden/extend.json).  The trace columns are already in HBM for the
+// low-degree extension, and the extension columns never visit the host.
 #include <string.h>
 
 #include <vector>
@@ -350,7 +352,7 @@ __global__ void trace_pad_kernel(const PadTables a) {
             same = v[0] == above;
         }
         T.d_mask0[r] = v[1] != 0 && same;                       // product rows
-        T.d_mask1[r] = !same;                                   // evaluation rows
+        T.d_mask1[r] = !same && !(r == 0 && v[0] == GL_P - 1);  // evaluation rows: the address "above" row 0 is -1 (instruction_table.py:184)
     } else if (T.kind == 2) {
         T.d_mask0[r] = v[3] == 0;                               // non-dummy rows
     }

@@ -4,7 +4,7 @@ import numpy as np
 
 from . import air
 from .air import X0
-from .table import Table
+from .table import Table, P
 
 
 class InstructionTable(Table):
@@ -33,9 +33,13 @@ class InstructionTable(Table):
         m = self.base_array()
         addr, ci = m[0], m[1]
         same = np.concatenate([[False], addr[1:] == addr[:-1]]) if len(addr) else np.zeros(0, dtype=bool)
-        # the running product absorbs a row when it is not padding and repeats the previous row's address (:197-205);
-        # the running evaluation absorbs the first row of every address (:209-214); both are recorded AFTER the row's update
-        return [(ci != 0) & same, ~same]
+        # the running product absorbs a row when it is not padding and repeats the previous row's address (:197-205, never row 0);
+        # the running evaluation absorbs the first row of every address (:209-214), where the address "above" row 0 is -1 (:184): a
+        # table that starts with the address p - 1 keeps row 0 out; both are recorded AFTER the row's update
+        first = ~same
+        if len(addr) and int(addr[0]) == P - 1:
+            first[0] = False
+        return [(ci != 0) & same, first]
 
     def _after_extend(self, terminals, all_challenges, read):
         self.permutation_terminal, self.evaluation_terminal = terminals

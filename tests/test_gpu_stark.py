@@ -728,7 +728,9 @@ def test_trace_padding_on_the_device():
             masks = [[int(v != 0) for v in out[2]], [int(v == ord(",")) for v in out[2]], [int(v == ord(".")) for v in out[2]]]
         elif kind == 1:
             same = [r > 0 and out[0][r] == out[0][r - 1] for r in range(height)]
-            masks = [[int(out[1][r] != 0 and same[r]) for r in range(height)], [int(not s) for s in same]]
+            # (the reference's loop starts with the address -1 "above" row 0, instruction_table.py:184: such a row 0 is not evaluated)
+            masks = [[int(out[1][r] != 0 and same[r]) for r in range(height)],
+                     [int(not s and not (r == 0 and out[0][0] == P - 1)) for r, s in enumerate(same)]]
         elif kind == 2:
             masks = [[int(v == 0) for v in out[3]]]
         return out, masks

@@ -191,6 +191,14 @@ _ROUNDS_SIGNATURES = {
 }
 
 
+# include/bfstark_compose.h: the composition polynomial of prove_deep (prefix bfsc_; the header says why); bound together with the four tables above
+_COMPOSE_SIGNATURES = {
+    "bfsc_air_compose": (ci, [ci, vp, vp, u32, u64, u64, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                              u32, ci, vp, vp]),
+    "bfsc_difference_compose": (ci, [vp, vp, u32, u64, u64, ctypes.POINTER(u64), u32, ci, vp, vp]),
+}
+
+
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
     _fields_ = [("d_base", vp), ("nwords", u32), ("stride", u32), ("out_offset", u64)]
@@ -284,6 +292,11 @@ def rounds_exported_symbols():
     return sorted(_ROUNDS_SIGNATURES)
 
 
+def compose_exported_symbols():
+    """names include/bfstark_compose.h declares"""
+    return sorted(_COMPOSE_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -300,7 +313,8 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()) + list(_ROUNDS_SIGNATURES.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()) + list(_ROUNDS_SIGNATURES.items())
+                              + list(_COMPOSE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

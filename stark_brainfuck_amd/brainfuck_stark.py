@@ -27,8 +27,8 @@ from .randomness import source as random_source
 
 from . import _lib, air, arrays, salted_merkle as salted_mod, table as table_mod
 from .algebra import BaseField, BaseFieldElement
-from .arrays import XArray
-from .device import GatherBatch, current_stream, gather, synchronize
+from .arrays import BaseArray, XArray, raw_ntt
+from .device import DeviceView, GatherBatch, current_stream, gather, synchronize
 from .evaluation_argument import EvaluationArgument, ProgramEvaluationArgument
 from .extension_field import ExtensionField, ExtensionFieldElement
 from .fri import MAX_GRINDING_BITS, Fri
@@ -37,6 +37,7 @@ from .io_table import InputTable, OutputTable
 from .ip import ProofStream
 from .memory_table import MemoryTable
 from .merkle import CosetMerkle, Merkle, leaf_pickle_source
+from .pcs import PolynomialCommitment
 from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
@@ -77,6 +78,39 @@ def _seed_or_stream(draw, nbytes):
     if draw is os.urandom or getattr(draw, "expand_on_device", False):
         return draw(32), None
     return None, draw(nbytes)
+
+
+def deep_opening_plan(tables, z):
+    """The one opening of prove_deep / verify_deep at the drawn point z (a limb triple), from public data alone: the tables' heights,
+    widths and subgroup generators.  The columns are those of the three commitments numbered through (PolynomialCommitment.
+    global_column): every table's base columns in table order, then every table's extension columns, then H.
+      * one group per table with rows: its base columns, then its extension columns, at [z, z * omicron] -- at [z] alone for a table of
+        height 1, whose next row is its own row (omicron = 1);
+      * one group of the columns of all tables without rows at [z], if there is such a table (their polynomials are zero);
+      * a last group (H) at [z].
+    -> namespace: groups (the plan as `open_rounds` takes it), widths (the commitments' row widths), table_group (per table the index
+    of its group, None for a table without rows), empty_group (index or None), h_group"""
+    z = tuple(int(v) for v in z)
+    num_base = sum(t.base_width for t in tables)
+    base_at, ext_at = 0, num_base
+    groups, table_group, empty = [], [], []
+    for t in tables:
+        bw, xw = t.base_width, t.full_width - t.base_width
+        columns = list(range(base_at, base_at + bw)) + list(range(ext_at, ext_at + xw))
+        base_at, ext_at = base_at + bw, ext_at + xw
+        if t.height == 0:
+            empty += columns
+            table_group.append(None)
+        else:
+            table_group.append(len(groups))
+            groups.append((columns, [z] if t.height == 1 else [z, air.xscale(z, t.omicron.value)]))
+    empty_group = None
+    if empty:
+        empty_group = len(groups)
+        groups.append((sorted(empty), [z]))
+    groups.append(([ext_at], [z]))
+    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, 1), table_group=table_group, empty_group=empty_group,
+                           h_group=len(groups) - 1)
 
 
 class _TermLayout:
@@ -721,6 +755,9 @@ class BrainfuckStark:
         else:
             p.randomizer_polynomial = XArray.from_numpy(sample_ext_many(blob, count, 9), xf)
         p.randomizer_codeword = p.domain.xevaluate(p.randomizer_polynomial, xf, as_array=True)
+        self._pad_tables(p)
+
+    def _pad_tables(self, p):          # the matrices onto the tables, padded (host work, no randomness); the proof stream if none was given
         for table, matrix in zip(self.tables, p.matrices):
             table.matrix = matrix
         for table in (self.processor_table, self.memory_table, self.instruction_table, self.input_table, self.output_table):
@@ -876,6 +913,209 @@ class BrainfuckStark:
 
     def _stage_serialize(self, p):
         p.proof = p.proof_stream.serialize()
+
+    # ---- proving by out-of-domain openings ("Proving by out-of-domain openings"): commitments in rounds through
+    # pcs.PolynomialCommitment, the quotients composed into ONE polynomial H, everything opened at one drawn point z with one FRI proof.
+    # A second protocol beside prove() / verify(), through Python stages only; the reference has no counterpart.
+    def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None):
+        """A proof of the same claim as prove()'s in the form current STARKs use (DEEP-ALI): C0 commits to the 16 base columns, C1 -- after
+        the 11 challenges -- to the 9 extension columns, C2 -- after the terminals and one weight per quotient -- to the composition
+        polynomial H = sum beta_q quotient_q, computed on every expansion_factor-th point of the domain (bfsc_air_compose) and
+        interpolated to N / expansion_factor coefficients; then z is drawn and one `open_rounds` opens every table's columns at z and at
+        its next row z * omicron, and H at z.  verify_deep() checks the opening and the one identity that ties H(z) to the opened rows.
+        The Fri modes of the constructor apply as they are.  Returns the proof bytes; for a false trace too (verify_deep refuses them).
+
+        NOT zero-knowledge: the commitments are not hiding (pcs.py: unsalted row trees, plain values in the proof) and no randomizer
+        polynomial is mixed in; the one trace randomizer per column only keeps the interpolants' shape of prove()."""
+        assert len(processor_matrix) + len(program) == len(instruction_matrix)
+        gc.freeze()          # (as prove(): the trace matrices' objects are not walked by collections during the proof)
+        try:
+            self.timing, stream, mark = {}, current_stream(), time.perf_counter()
+            p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
+                                domain=self.fri.domain, n=self.fri.domain.length, stream=stream, pc=PolynomialCommitment(self.fri), commitments=[])
+            for name, stage in (("pad", self._deep_stage_pad), ("base_lde", self._deep_stage_base_lde), ("base_commit", self._deep_stage_base_commit),
+                                ("extend", self._stage_extend), ("ext_lde", self._deep_stage_ext_lde), ("ext_commit", self._deep_stage_ext_commit),
+                                ("composition", self._deep_stage_composition), ("composition_commit", self._deep_stage_composition_commit),
+                                ("opening", self._deep_stage_opening), ("serialize", self._stage_serialize)):
+                stage(p)
+                if self.stage_timing:
+                    synchronize(stream)
+                now = time.perf_counter()
+                self.timing[name], mark = now - mark, now
+            return p.proof
+        finally:
+            gc.unfreeze()
+
+    def _deep_stage_pad(self, p):          # padding as _stage_pad; no randomizer polynomial is drawn
+        p.draw = random_source(urandom)
+        self._pad_tables(p)
+
+    def _deep_polys(self, coefficients, stride, extension):
+        """the interpolants lde_tables left in `coefficients` as views, in table order: a table's own coefficient count each, one zero
+        coefficient for a table without rows"""
+        polys, at = [], 0
+        for t in self.tables:
+            count = max(t.transform_coefficients(), 1)
+            if extension:
+                for c in range(t.full_width - t.base_width):
+                    polys.append(XArray(DeviceView(coefficients, (at + 3 * c) * stride, 3 * stride), count, self.xfield, stride=stride))
+                at += 3 * (t.full_width - t.base_width)
+            else:
+                polys += [BaseArray(DeviceView(coefficients, (at + c) * stride, stride), count, BrainfuckStark.field) for c in range(t.base_width)]
+                at += t.base_width
+        return polys
+
+    def _deep_stage_base_lde(self, p):
+        p.base_codewords, p.base_coefficients, stride = lde_tables(self.tables, p.domain, keep_coefficients=True)
+        p.base_polys = self._deep_polys(p.base_coefficients, stride, False)
+        p.prepared_extension = prepare_extension(self.tables)
+
+    def _deep_stage_base_commit(self, p):          # C0: the codewords as lde_tables wrote them are the commitment's rows
+        p.commitments.append(p.pc.commit_evaluated(p.base_polys, p.base_codewords, p.proof_stream))
+
+    def _deep_stage_ext_lde(self, p):
+        p.ext_codewords, p.ext_coefficients, stride = lde_tables(self.tables, p.domain, extension=True, keep_coefficients=True)
+        p.ext_polys = self._deep_polys(p.ext_coefficients, stride, True)
+
+    def _deep_stage_ext_commit(self, p):          # C1
+        p.commitments.append(p.pc.commit_evaluated(p.ext_polys, p.ext_codewords, p.proof_stream))
+
+    def deep_weight_count(self):
+        """one weight per quotient: the tables' (boundary, transition, terminal within a table), then the permutation arguments'"""
+        return sum(t.num_quotients() for t in self.tables) + len(self.permutation_arguments)
+
+    def compose_into(self, out, log_step, weights, challenges, terminals):
+        """H on every 2^log_step-th point of the FRI domain into `out` (XArray of N >> log_step elements): bfsc_air_compose per table with
+        rows, bfsc_difference_compose per permutation argument; the first call writes, the others add.  weights: (deep_weight_count(), 3)
+        uint64; weights of a table without rows are skipped."""
+        lib, domain, n = _lib.load(), self.fri.domain, self.fri.domain.length
+        assert out.n == n >> log_step and out.stride == out.n
+        weights = np.ascontiguousarray(weights, dtype=np.uint64)
+        as_limbs = lambda w: np.ascontiguousarray(w).reshape(-1).ctypes.data_as(ctypes.POINTER(_u64))
+        at, accumulate = 0, 0
+        for t in self.tables:
+            nq = t.num_quotients()
+            if t.height:
+                mine = np.ascontiguousarray(weights[at:at + nq])
+                _lib.check(lib.bfsc_air_compose(t.table_index, t.base_codewords.ptr, t.ext_codewords.ptr, *t._domain_arguments(domain),
+                                                *table_mod._air_arguments(t, challenges, terminals), as_limbs(mine), log_step, accumulate, out.ptr,
+                                                current_stream()))
+                accumulate = 1
+            at += nq
+        for j, pa in enumerate(self.permutation_arguments):
+            lt, rt = self.tables[pa.lhs[0]], self.tables[pa.rhs[0]]
+            mine = np.ascontiguousarray(weights[at + j])
+            _lib.check(lib.bfsc_difference_compose(lt.ext_codeword_ptr(pa.lhs[1]), rt.ext_codeword_ptr(pa.rhs[1]), n.bit_length() - 1, domain.offset.value,
+                                                   domain.omega.value, as_limbs(mine), log_step, accumulate, out.ptr, current_stream()))
+            accumulate = 1
+
+    def _deep_stage_composition(self, p):
+        """terminals, weights, H on the d = N / expansion_factor points offset * omega^(e k), and its d coefficients: a coset inverse
+        transform of length d with root omega^e and the domain's offset"""
+        from . import debug_checks
+        for t in self._terminal_objects(p.terminals):
+            p.proof_stream.push(t)
+        p.weights = BrainfuckStark._sample_weights(self.deep_weight_count(), p.proof_stream.prover_fiat_shamir(), as_array=True)
+        n, e, lib = p.n, self.expansion_factor, _lib.load()
+        d = n // e
+        offset, omega = p.domain.offset.value, p.domain.omega.value
+        p.h_values = XArray.empty(d, self.xfield)
+        self.compose_into(p.h_values, e.bit_length() - 1, p.weights, p.challenges, p.terminals)
+        p.h_coefficients = XArray.empty(d, self.xfield)
+        raw_ntt(p.h_values.ptr, d, d, p.h_coefficients.ptr, d, d.bit_length() - 1, 3, table_mod._inv(pow(omega, e, P_GOLDILOCKS)), 1, table_mod._inv(d), p.stream)
+        _lib.check(lib.bfs_gl_scale(p.h_coefficients.ptr, p.h_coefficients.ptr, d, d, 3, table_mod._inv(offset), p.stream))
+        if debug_checks.enabled():
+            # an honest trace: every quotient's degree bound is at most max_degree, so H on the FULL domain interpolates to d coefficients
+            full = XArray.empty(n, self.xfield)
+            self.compose_into(full, 0, p.weights, p.challenges, p.terminals)
+            coefficients = XArray.empty(n, self.xfield)
+            raw_ntt(full.ptr, n, n, coefficients.ptr, n, n.bit_length() - 1, 3, table_mod._inv(omega), 1, table_mod._inv(n), p.stream)
+            assert not coefficients.to_numpy()[:, d:].any(), "the composition polynomial has degree >= N / expansion_factor"
+
+    def _deep_stage_composition_commit(self, p):          # C2
+        p.commitments.append(p.pc.commit([p.h_coefficients], p.proof_stream))
+
+    def _deep_stage_opening(self, p):
+        """z, drawn behind C2's root, and the one opening of all 26 columns"""
+        p.z = tuple(self.xfield.sample(p.proof_stream.prover_fiat_shamir()).limbs())
+        if p.z[1] == 0 and p.z[2] == 0:
+            raise ValueError("the drawn point lies in the base field (chance 2^-128): prove again")
+        p.plan = deep_opening_plan(self.tables, p.z)
+        p.opened = p.pc.open_rounds(p.commitments, p.plan.groups, p.proof_stream)
+        self._last = {"challenges": p.challenges, "terminals": p.terminals}
+        if self.keep_intermediates:
+            self._last.update({"commitments": p.commitments, "weights": p.weights, "z": p.z, "plan": p.plan, "h_values": p.h_values,
+                               "h_coefficients": p.h_coefficients, "base_polys": p.base_polys, "ext_polys": p.ext_polys,
+                               "opened": [[[tuple(v.limbs()) for v in per_point] for per_point in per_group] for per_group in p.opened]})
+        else:
+            BrainfuckStark._release(*self.tables)
+
+    def verify_deep(self, proof):
+        """the verifier of prove_deep -- host code only (Python ints, hashlib, Fri.verify): the terminals against the public input, output
+        and program; the opening of the 26 columns at the plan's points for the values the prover claims (read_rounds); every value of a
+        table without rows zero; and
+            sum_t sum_q beta_{t,q} constraint_{t,q}(cur_t, nxt_t) Z_kind(z) + sum_j beta_j (lhs_j(z) - rhs_j(z)) / (z - 1) = H(z)
+        with Z the zerofier factors of csrc/air.hip: 1 / (z - 1), (z - omicron^-1) / (z^h - 1), 1 / (z - omicron^-1).
+        False with one printed line for every refusal, a malformed stream included; raises nothing."""
+        try:
+            return self._verify_deep_stream(ProofStream().deserialize(proof))
+        except Exception as e:          # whatever a stream that is not prove_deep's makes the readers raise
+            print("malformed proof: %s" % type(e).__name__)
+            return False
+
+    def _verify_deep_stream(self, proof_stream):
+        X0, X1, xadd, xsub, xmul, xinv, xpow = air.X0, air.X1, air.xadd, air.xsub, air.xmul, air.xinv, air.xpow
+        root0 = proof_stream.pull()
+        challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.verifier_fiat_shamir()))
+        root1 = proof_stream.pull()
+        terminal_objects = [proof_stream.pull() for _ in range(5)]
+        terminals = [_canonical_limbs(t) for t in terminal_objects]
+        stored = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
+        for io, ea in zip((self.input_table, self.output_table), self.evaluation_arguments):          # the rule of _verify_head, as a refusal
+            if io.height != 0 and not any(stored[io.terminal_index]) and any(ea.compute_terminal(challenges)):
+                print("evaluation terminal of a non-empty input or output table is zero")
+                return False
+        for ea in self.evaluation_arguments:
+            if tuple(ea.select_terminal(stored)) != tuple(ea.compute_terminal(challenges)):
+                print("a terminal does not match the public input, output or program")
+                return False
+        weights = BrainfuckStark._sample_weights(self.deep_weight_count(), proof_stream.verifier_fiat_shamir())
+        root2 = proof_stream.pull()
+        z = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
+        if z[1] == 0 and z[2] == 0:
+            print("the drawn point lies in the base field")
+            return False
+        plan = deep_opening_plan(self.tables, z)
+        values = PolynomialCommitment(self.fri).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
+        if values is None:
+            return False
+        if plan.empty_group is not None and any(any(v) for v in values[plan.empty_group][0]):
+            print("a column of a table without rows is not zero")
+            return False
+        total, at, rows = X0, 0, []
+        boundary = xinv(xsub(z, X1))
+        for t, g in zip(self.tables, plan.table_group):
+            if g is None:
+                rows.append([X0] * t.full_width)
+                at += t.num_quotients()
+                continue
+            cur = values[g][0]
+            nxt = values[g][1] if len(values[g]) > 1 else cur          # height 1: the next row is the row itself
+            rows.append(cur)
+            off = xsub(z, (table_mod._inv(t.omicron.value), 0, 0))
+            factors = {"boundary": boundary, "transition": xmul(off, xinv(xsub(xpow(z, t.height), X1))), "terminal": xinv(off)}
+            params, memo = t.air_params(challenges), {}
+            for kind, constraints in t.air.all():
+                for e in constraints:
+                    value = air.evaluate(e, cur, nxt, challenges, terminals, params, memo)
+                    total = xadd(total, xmul(xmul(weights[at], value), factors[kind]))
+                    at += 1
+        for j, pa in enumerate(self.permutation_arguments):
+            total = xadd(total, xmul(xmul(weights[at + j], pa.evaluate_difference(rows)), boundary))
+        if total != tuple(values[plan.h_group][0][0]):
+            print("the composition polynomial does not match the opened rows")
+            return False
+        return True
 
     # ------------------------------------------------------------------------------------------------------------
     def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):

@@ -47,6 +47,10 @@ group]), plain ints -- numbering and plan are inside every later Fiat-Shamir has
 [t indices]; per index i: for r = 0 .. R - 1 the row tuple of C_r at x_i and its authentication path, then the opening of g as above;
 then Fri.prove over g.  With one commitment the quotient is `open_at`'s and the stream differs by the widths in the shape.
 
+For a protocol whose codewords exist already, and whose verifier learns the values from the proof (BrainfuckStark.prove_deep / verify_deep):
+      .commit_evaluated(polys, codewords, proof_stream)          `commit` over codewords that are in HBM in Commitment's layout: nothing is transformed
+      .read_rounds(roots, widths, plan, proof_stream)            `verify_rounds` that TAKES the values from the stream -> values[g][j][r] or None
+
 The three openings are ONE prover and ONE verifier over an OpeningPlan (PolynomialCommitment._open, ._verify_quotient): `open` is the plan
 of one group of all columns (built without the rule against a point given twice, which `open` never had), `open_at` a plan over one
 commitment, `open_rounds` a plan over the columns of several.  They differ in what they push behind the points (nothing; the shape; the
@@ -340,7 +344,7 @@ class PolynomialCommitment:
         """polys: BaseArrays (batch 1) and XArrays of coefficients in HBM, at most N // expansion_factor each; at most 32 columns, at
         most 16 of them extension columns.  Extends every polynomial to the FRI domain (bfs_gl_ntt), hashes the rows
         (bfs_merkle_build_rows without salts: leaf i = the tuple of all values at x_i, extension columns first) and pushes the root."""
-        lib, stream, n = _lib.load(), current_stream(), self.n
+        stream, n = current_stream(), self.n
         assert polys, "nothing to commit to"
         for f in polys:
             assert isinstance(f, XArray) or (isinstance(f, BaseArray) and f.batch == 1), "polynomials are BaseArrays of batch 1 and XArrays"
@@ -360,11 +364,37 @@ class PolynomialCommitment:
             else:
                 raw_ntt(f.ptr, f.n, f.n, committed.column_ptr(c), n, log_n, 1, self.omega, self.offset, 1, stream)
             cols[c].d_values, cols[c].is_ext, cols[c].field_id = committed.column_ptr(c), int(is_ext[position]), 1
-        nodes = DeviceBuffer(2 * n * 8)
-        _lib.check(lib.bfs_merkle_build_rows(cols, len(polys), n, None, 0, nodes.ptr, stream))
-        committed.tree = Merkle(_RowCount(n), _device_nodes=nodes)
+        return self._commit_rows(committed, cols, proof_stream)
+
+    def _commit_rows(self, committed, cols, proof_stream):
+        """the row tree over a commitment's codewords (bfs_merkle_build_rows without salts); pushes the root"""
+        nodes = DeviceBuffer(2 * self.n * 8)
+        _lib.check(_lib.load().bfs_merkle_build_rows(cols, len(committed.polys), self.n, None, 0, nodes.ptr, current_stream()))
+        committed.tree = Merkle(_RowCount(self.n), _device_nodes=nodes)
         proof_stream.push(committed.tree.root())
         return committed
+
+    def commit_evaluated(self, polys, codewords, proof_stream):
+        """`commit` for polynomials whose codewords on the FRI domain are in HBM already: nothing is transformed.  codewords: a device
+        buffer in Commitment's layout -- per extension polynomial three planes of N words, then per base polynomial N words --, which
+        the commitment keeps and never writes; polys: the coefficients in THAT order (XArrays, with any stride, then BaseArrays of batch 1),
+        which openings evaluate.  That the codewords are the polynomials' is the caller's word: an opening of other data fails its own
+        low-degree test.  Builds the row tree and pushes the root, as `commit` does."""
+        n = self.n
+        assert polys, "nothing to commit to"
+        is_ext = [isinstance(f, XArray) for f in polys]
+        for f in polys:
+            assert isinstance(f, XArray) or (isinstance(f, BaseArray) and f.batch == 1), "polynomials are BaseArrays of batch 1 and XArrays"
+            assert 1 <= len(f) <= self.max_coefficients, "a polynomial has 1 .. N / expansion_factor coefficients"
+        assert is_ext == sorted(is_ext, reverse=True), "extension polynomials first: the order of the codewords in the buffer"
+        n_ext = sum(is_ext)
+        assert len(polys) <= MAX_COLUMNS and n_ext <= MAX_EXT_COLUMNS, "at most 32 columns, at most 16 extension columns"
+        assert codewords.count >= (3 * n_ext + len(polys) - n_ext) * n, "the codeword buffer is shorter than the row layout"
+        committed = Commitment(list(polys), is_ext, list(range(len(polys))), codewords, n, None)
+        cols = (_lib.RowColumn * len(polys))()
+        for c in range(len(polys)):
+            cols[c].d_values, cols[c].is_ext, cols[c].field_id = committed.column_ptr(c), int(is_ext[c]), 1
+        return self._commit_rows(committed, cols, proof_stream)
 
     def _row(self, committed, i, words):
         """the tuple of element objects of row i (one object per row: a row opened twice is the same tuple twice)"""
@@ -633,27 +663,39 @@ class PolynomialCommitment:
             return False
         return self._verify_plan([(root, plan.m)], plan, plan.shape, values, proof_stream)
 
-    def _verify_plan(self, trees, plan, shape, values, proof_stream):
-        """what verify_at and verify_rounds share: points, shape and values against the caller's, then the quotient.  trees: (root,
-        width) per commitment; shape: what the prover pushed behind the points"""
+    def _verify_plan(self, trees, plan, shape, values, proof_stream, read=False):
+        """what verify_at, verify_rounds and read_rounds share: points, shape and values against the caller's, then the quotient.  trees:
+        (root, width) per commitment; shape: what the prover pushed behind the points.  read (read_rounds): `values` is not looked at;
+        the stream's values are checked against the quotient and returned as limb triples values[g][j][r], None on refusal"""
         is_element = lambda e: isinstance(e, ExtensionFieldElement)
+        refused = None if read else False
         pushed = proof_stream.pull()
         if not isinstance(pushed, list) or not all(is_element(z) for z in pushed) or [_limbs(z) for z in pushed] != plan.points:
             print("points differ from the caller's plan")
-            return False
+            return refused
         if proof_stream.pull() != shape:
             print("groups differ from the caller's plan")
-            return False
+            return refused
         claimed = proof_stream.pull()
+        lengths = [[len(columns)] * len(indices) for columns, indices in plan.groups]
+        got = None          # the stream's values as limb triples, if they are lists of lists of lists of elements
+        if isinstance(claimed, list) and all(isinstance(per_group, list) and all(isinstance(per_point, list) and all(is_element(v) for v in per_point)
+                                                                                 for per_point in per_group) for per_group in claimed):
+            got = [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in claimed]
+        if read:
+            # the caller does not know the values: they are the stream's, provided they have the plan's shape and are canonical elements
+            if got is None or [[len(per_point) for per_point in per_group] for per_group in got] != lengths:
+                print("values do not have the shape of the caller's plan")
+                return None
+            if not all(len(v) == 3 and all(type(c) is int and 0 <= c < P for c in v) for per_group in got for per_point in per_group for v in per_point):
+                print("values are not canonical elements")
+                return None
+            return got if self._verify_quotient(trees, plan, got, proof_stream) else None
         try:
             want = [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in values]
         except TypeError:
             want = None
-        lengths = [[len(columns)] * len(indices) for columns, indices in plan.groups]
-        if (want is None or [[len(per_point) for per_point in per_group] for per_group in want] != lengths or not isinstance(claimed, list)
-                or not all(isinstance(per_group, list) and all(isinstance(per_point, list) and all(is_element(v) for v in per_point) for per_point in per_group)
-                           for per_group in claimed)
-                or [[[_limbs(v) for v in per_point] for per_point in per_group] for per_group in claimed] != want):
+        if want is None or [[len(per_point) for per_point in per_group] for per_group in want] != lengths or got != want:
             print("values differ from the caller's")
             return False
         return self._verify_quotient(trees, plan, want, proof_stream)
@@ -725,6 +767,11 @@ class PolynomialCommitment:
         -- commitments of row widths `widths`, in the order `open_rounds` was given them -- take `values` (values[g][j][r]) under
         `plan`?  The roots are the caller's: it has read each from the transcript where `commit` pushed it.  Host code only; one printed
         line per refusal."""
+        checked = self._checked_rounds(roots, widths, plan)
+        return checked is not None and self._verify_plan(*checked, values, proof_stream)
+
+    def _checked_rounds(self, roots, widths, plan):
+        """(trees, plan, shape) as _verify_plan takes them for commitments of these roots and widths, or None with one printed line"""
         try:
             roots = list(roots)
             widths = self._widths(widths)
@@ -732,10 +779,19 @@ class PolynomialCommitment:
                 raise ValueError("one root and one width per commitment (got %d and %d)" % (len(roots), len(widths)))
         except (TypeError, ValueError) as e:
             print("commitments cannot be opened: %s" % e)
-            return False
+            return None
         try:
             plan = self.rounds_plan(plan, widths)
         except ValueError as e:
             print("plan cannot be opened: %s" % e)
-            return False
-        return self._verify_plan(list(zip(roots, widths)), plan, (tuple(widths), plan.shape), values, proof_stream)
+            return None
+        return list(zip(roots, widths)), plan, (tuple(widths), plan.shape)
+
+    @_reads_leaf_pickles
+    def read_rounds(self, roots, widths, plan, proof_stream):
+        """`verify_rounds` for a caller that does not know the values beforehand (a verifier that has drawn the points itself and wants
+        the committed polynomials' values there): points and shape are checked against the caller's plan, the values are TAKEN from the
+        stream and the quotient is checked against them.  Returns values[g][j][r] as limb triples -- exactly what an accepted opening
+        vouches for -- or None on refusal, with one printed line.  Host code only."""
+        checked = self._checked_rounds(roots, widths, plan)
+        return None if checked is None else self._verify_plan(*checked, None, proof_stream, read=True)

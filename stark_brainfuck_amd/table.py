@@ -230,13 +230,17 @@ def _draw_randomizers(table, extension):
     return [sample_base(random_source(urandom)(3 * 8)) for _ in range(table.base_width)]
 
 
-def lde_tables(tables, domain, extension=False):
+def lde_tables(tables, domain, extension=False, keep_coefficients=False):
     """The low-degree extension of the base columns (extension=False) or the extension columns (True) of several tables -- Table.lde /
     Table.ldex are the calls with one table -- with ONE transform onto the FRI domain: every table interpolates its own columns (its
     own subgroup) into its rows of a shared coefficient buffer, and the coset evaluation -- the same N-point transform for all of them
     -- runs once over all columns (three launches instead of three per table; on short traces the launches are the cost).
     Randomizers are drawn table by table, column by column.  A table without rows gets zero codewords, one without columns an empty
-    buffer; either may be true of every table."""
+    buffer; either may be true of every table.
+    keep_coefficients: returns (codewords, coefficients, stride) -- the buffer of all codewords (per column, or per limb plane of an
+    extension column, N words, in table order), the buffer of the interpolants' coefficients in the same order, `stride` words per row
+    (a table's rows hold transform_coefficients() coefficients, zeros behind them; None when no table has a row), for a caller that
+    commits to the codewords as they lie (PolynomialCommitment.commit_evaluated).  Otherwise the coefficients go back to the pool."""
     lib, stream = _lib.load(), current_stream()
     n = domain.length
     log_n = n.bit_length() - 1
@@ -297,6 +301,8 @@ def lde_tables(tables, domain, extension=False):
             t.base_codewords = view
             t._base_device = d_in          # the trace columns stay in HBM for extend_device()
         at += w
+    if keep_coefficients:
+        return out, coeffs, stride
 
 
 def zerofier_inverses(tables, domain, rows=None):

@@ -1,0 +1,295 @@
+"""BrainfuckStark.prove_deep / verify_deep: the committed fixtures of the mode, and its time and proof size beside prove().
+
+    python tools/deep_stark_time.py [--program big|loop|...] [--reps 5] [--kernel-reps 20] [--json FILE]
+    python tools/deep_stark_time.py --sizes
+    python tools/deep_stark_time.py --write-golden DIR
+
+Without an option: on the 37 254-cycle program of bench.py --full (FRI domain 2^22) prove_deep and prove (Python stages, stage_timing) by
+stage, proof bytes of both, verify_deep, and every bfsc_air_compose launch at log_step 0 and 2 against bfs_air_combine on the same table
+with all column weights and every second weight zero (the same sum with more work), alternating in one process on the codewords a proof
+left in HBM.  Every figure is a median with min and max; stages from a host clock around work that ends in a stream synchronise, kernels from
+device events.  --sizes prints the proof bytes of both modes for the four fixture programs.
+
+--write-golden DIR writes the proofs of FIXTURES on seeded randomness (randomness.override with the SHAKE-256 stream of
+tools/stark_fri_modes.py, tag b"deep-" + name) and DIR/deep_stark.json.  The proofs need a GPU; the claims, the seeds and the byte-level
+tamperings the tests share with this tool are importable without one.
+"""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from tools import stark_fri_modes as modes          # noqa: E402
+from tools.stark_fri_modes import mode              # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+FIXTURE_LIST = "deep_stark.json"
+# name -> (source, input): FRI domains 2^8 .. 2^11; both I/O tables empty, of height 1, of height 2, input empty and output of height 1
+PROGRAMS = {"plus1": ("+", ""), "io": (",.", "a"), "two_io": (",.,.", "ab"), "loop": ("++[>+<-]>.", "")}
+DOMAINS = {"plus1": 1 << 8, "io": 1 << 9, "two_io": 1 << 10, "loop": 1 << 11}
+HEIGHTS = {"plus1": (0, 0), "io": (1, 1), "two_io": (2, 2), "loop": (0, 1)}          # input and output table
+MODE_A8C_G4 = mode(8, True, 4, security_level=6)
+FIXTURES = [(name, mode()) for name in PROGRAMS] + [("two_io", MODE_A8C_G4)]
+
+
+def fixture_file(name, m):
+    return "deep_%s_proof.bin" % name if m == mode() else "deep_%s_%s_proof.bin" % (name, modes.mode_id(m).split("_e")[0])
+
+
+_claims = {}
+
+
+def claim(name):
+    """(program, running_time, input symbols, output symbols, trace matrices)"""
+    from stark_brainfuck_amd.vm import VirtualMachine
+    if name not in _claims:
+        source, given = PROGRAMS[name] if name in PROGRAMS else (name, "")
+        program = VirtualMachine.compile(source)
+        running_time, inputs, outputs = VirtualMachine.run(program, input_data=list(given))
+        _claims[name] = (program, running_time, inputs, outputs, VirtualMachine.simulate(program, input_data=list(inputs)))
+    return _claims[name]
+
+
+def make_stark(name, m=None, output_symbols=None):
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    m = mode() if m is None else m
+    program, running_time, inputs, outputs, matrices = claim(name)
+    return BrainfuckStark(running_time, len(matrices[1]), program, inputs, outputs if output_symbols is None else output_symbols,
+                          m["log_expansion_factor"], m["security_level"], m["folding_factor"], m["coset_leaves"], m["grinding_bits"])
+
+
+def seed_tag(name):
+    return b"deep-" + name.encode()
+
+
+def prove_deep_seeded(name, m=None, prepare=None, matrices=None):
+    """-> (stark, proof) of program `name` on the seeded randomness; prepare(stark) runs before prove_deep; matrices: other traces"""
+    from stark_brainfuck_amd import randomness
+    stark = make_stark(name, m)
+    if prepare is not None:
+        prepare(stark)
+    with randomness.override(modes.Stream(seed_tag(name))):
+        proof = stark.prove_deep(claim(name)[0], *(claim(name)[4] if matrices is None else matrices))
+    return stark, proof
+
+
+def fixtures(directory=GOLDEN):
+    path = os.path.join(directory, FIXTURE_LIST)
+    if not os.path.exists(path):
+        return []
+    with open(path) as f:
+        return json.load(f)["proofs"]
+
+
+# ---- a proof as its objects: root0, root1, five terminals, root2, then open_rounds' points, shape, values, ...
+ROOT2_AT, VALUES_AT = 7, 10
+
+
+def objects_of(proof):
+    from stark_brainfuck_amd.ip import ProofStream
+    return list(ProofStream().deserialize(proof).objects)
+
+
+def bytes_of(objects):
+    from stark_brainfuck_amd.ip import ProofStream
+    ps = ProofStream()
+    for obj in objects:
+        ps.push(obj)
+    return ps.serialize()
+
+
+def _bumped(element):
+    from stark_brainfuck_amd.air import P
+    limbs = list(element.limbs())
+    limbs[1] = (limbs[1] + 1) % P
+    return element.field.from_limbs(limbs)
+
+
+def tamperings(proof):
+    """name -> bytes: the byte-level changes verify_deep must refuse"""
+    objects = objects_of(proof)
+    values = [[list(per_point) for per_point in per_group] for per_group in objects[VALUES_AT]]
+    values[0][0][1] = _bumped(values[0][0][1])
+    root2 = bytearray(objects[ROOT2_AT])
+    root2[5] ^= 1
+    return {"a limb of an opened value": bytes_of(objects[:VALUES_AT] + [values] + objects[VALUES_AT + 1:]),
+            "a limb of a terminal": bytes_of(objects[:2] + [_bumped(objects[2])] + objects[3:]),
+            "a digest of the composition's root": bytes_of(objects[:ROOT2_AT] + [bytes(root2)] + objects[ROOT2_AT + 1:]),
+            "a truncated proof": proof[:len(proof) // 2]}
+
+
+def write_golden(directory):
+    os.makedirs(directory, exist_ok=True)
+    entries = []
+    for name, m in FIXTURES:
+        stark, proof = prove_deep_seeded(name, m)
+        assert stark.fri.domain.length == DOMAINS[name]
+        assert make_stark(name, m).verify_deep(proof) is True, "%s %s does not verify" % (name, modes.mode_id(m))
+        assert prove_deep_seeded(name, m)[1] == proof, "two proofs on the same seed differ"
+        source, given = PROGRAMS[name]
+        entry = {"file": fixture_file(name, m), "name": name, "program": source, "input": given, "output": "".join(claim(name)[3]), "args": m,
+                 "seed": "shake_256(b'bfs-golden-urandom' + %r)" % seed_tag(name), "fri_domain_length": stark.fri.domain.length,
+                 "proof_len": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest()}
+        with open(os.path.join(directory, entry["file"]), "wb") as f:
+            f.write(proof)
+        entries.append(entry)
+        print("wrote %s  %d bytes  sha256 %s" % (entry["file"], len(proof), entry["proof_sha256"][:16]), flush=True)
+    with open(os.path.join(directory, FIXTURE_LIST), "w") as f:
+        json.dump({"made_by": "tools/deep_stark_time.py --write-golden", "randomness": "randomness.override(tools.stark_fri_modes.Stream(b'deep-' + name))",
+                   "proofs": entries}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+# ---- timing
+def _sync():
+    from stark_brainfuck_amd.device import current_stream, synchronize
+    synchronize(current_stream())
+
+
+def _mmm(values):
+    return {"median": round(statistics.median(values), 4), "min": round(min(values), 4), "max": round(max(values), 4)}
+
+
+def sizes():
+    """proof bytes of prove and prove_deep for the four fixture programs"""
+    rows = []
+    for name in PROGRAMS:
+        program, _, _, _, matrices = claim(name)
+        rows.append({"program": name, "fri_domain_length": DOMAINS[name], "prove_bytes": len(make_stark(name).prove(program, *matrices)),
+                     "prove_deep_bytes": len(make_stark(name).prove_deep(program, *matrices))})
+        print("SIZE " + json.dumps(rows[-1], sort_keys=True), flush=True)
+    return rows
+
+
+def time_proofs(name, reps):
+    """prove_deep and prove (Python stages) by stage, ms; proof bytes; verify_deep"""
+    program, _, _, _, matrices = claim(name)
+    out = {}
+    for label in ("prove_deep", "prove"):
+        per_stage, totals, proof = {}, [], None
+        for rep in range(reps + 1):
+            stark = make_stark(name)
+            stark.stage_timing = True
+            t0 = time.perf_counter()
+            proof = getattr(stark, label)(program, *matrices)
+            _sync()
+            if rep:          # (the first proof of a shape warms it and is dropped)
+                totals.append((time.perf_counter() - t0) * 1e3)
+                for stage, seconds in stark.timing.items():
+                    per_stage.setdefault(stage, []).append(seconds * 1e3)
+        out[label] = {"total_ms": _mmm(totals), "stages_ms": {s: _mmm(v) for s, v in per_stage.items()}, "proof_bytes": len(proof),
+                      "fri_domain_length": stark.fri.domain.length}
+        out[label + "_proof"] = proof
+    verify_ms = []
+    for rep in range(reps + 1):
+        verifier = make_stark(name)
+        t0 = time.perf_counter()
+        assert verifier.verify_deep(out["prove_deep_proof"]) is True
+        verify_ms.append((time.perf_counter() - t0) * 1e3)
+    out["verify_deep_ms"] = _mmm(verify_ms[1:])
+    del out["prove_deep_proof"], out["prove_proof"]
+    return out
+
+
+def time_kernels(name, reps):
+    """per table with rows: bfsc_air_compose at log_step 0 and 2 and the yardstick bfs_air_combine (column weights and wb zero, zerofier
+    inverses computed in the kernel, as the compose kernel computes them), alternating, device events, us"""
+    import numpy as np
+    from stark_brainfuck_amd import _lib
+    from stark_brainfuck_amd.arrays import XArray
+    from stark_brainfuck_amd.device import current_stream
+    from stark_brainfuck_amd.table import _air_arguments
+    lib, stream = _lib.load(), current_stream()
+    program, _, _, _, matrices = claim(name)
+    stark = make_stark(name)
+    stark.keep_intermediates = True          # (the codewords stay in HBM)
+    stark.prove_deep(program, *matrices)
+    last, domain, n = stark._last, stark.fri.domain, stark.fri.domain.length
+    challenges, terminals, weights = last["challenges"], last["terminals"], last["weights"]
+    shifts = stark._layout.shifts(stark._quotient_degree_bounds(challenges, terminals))
+    start, stop = ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.check(lib.bfs_event_create(ctypes.byref(start)))
+    _lib.check(lib.bfs_event_create(ctypes.byref(stop)))
+
+    def timed(call):
+        _lib.check(lib.bfs_event_record(start, stream))
+        call()
+        _lib.check(lib.bfs_event_record(stop, stream))
+        _sync()
+        ms = ctypes.c_float()
+        _lib.check(lib.bfs_event_elapsed_ms(start, stop, ctypes.byref(ms)))
+        return ms.value * 1e3
+    full, quarter, combined = XArray.empty(n, stark.xfield), XArray.empty(n >> 2, stark.xfield), XArray.empty(n, stark.xfield)
+    _lib.check(lib.bfs_memset(combined.ptr, 0, 3 * n * 8, stream))
+    rows, at = [], 0
+    for k, t in enumerate(stark.tables):
+        nq = t.num_quotients()
+        mine = np.ascontiguousarray(weights[at:at + nq])
+        at += nq
+        if not t.height:
+            continue
+        limbs = mine.reshape(-1).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        head = (t.table_index, t.base_codewords.ptr, t.ext_codewords.ptr) + tuple(t._domain_arguments(domain)) + tuple(_air_arguments(t, challenges, terminals))
+        layout = stark._layout
+        terms = np.zeros((t.full_width + nq, 7), dtype=np.uint64)
+        terms[:, 6] = shifts[layout.base[k]] + shifts[layout.ext[k]] + shifts[layout.quot[k]]
+        terms[t.full_width:, 0:3] = mine
+        calls = {"compose_step1": lambda: _lib.check(lib.bfsc_air_compose(*head, limbs, 0, 1, full.ptr, stream)),
+                 "compose_step4": lambda: _lib.check(lib.bfsc_air_compose(*head, limbs, 2, 1, quarter.ptr, stream)),
+                 "combine_yardstick": lambda: t.combine_into(domain, challenges, terminals, terms, combined)}
+        series = {label: [] for label in calls}
+        for rep in range(reps + 2):
+            for label, call in calls.items():
+                us = timed(call)
+                if rep >= 2:
+                    series[label].append(us)
+        row = {"table": t.air.name, "height": t.height, "us": {label: _mmm(v) for label, v in series.items()}}
+        base = row["us"]["combine_yardstick"]
+        row["allowance_us"] = round(base["median"] + (base["max"] - base["min"]), 4)
+        row["within_yardstick"] = row["us"]["compose_step1"]["median"] <= row["allowance_us"]
+        row["step4_over_step1"] = round(row["us"]["compose_step4"]["median"] / row["us"]["compose_step1"]["median"], 4)
+        rows.append(row)
+        print("KERNEL " + json.dumps(row, sort_keys=True), flush=True)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--program", default="big")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--sizes", action="store_true")
+    ap.add_argument("--write-golden", default=None)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing is proven or timed here")
+    if args.write_golden:
+        return write_golden(args.write_golden)
+    result = {}
+    if args.sizes:
+        result["sizes"] = sizes()
+    else:
+        name = args.program
+        if name == "big":
+            PROGRAMS["big"] = (modes.BIG, "")
+        result["program"] = name
+        result["proofs"] = time_proofs(name, args.reps)
+        print("PROOFS " + json.dumps(result["proofs"], sort_keys=True), flush=True)
+        result["kernels"] = time_kernels(name, args.kernel_reps)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(result, fh, indent=1, sort_keys=True)
+
+
+if __name__ == "__main__":
+    main()

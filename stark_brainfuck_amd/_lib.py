@@ -198,6 +198,11 @@ _COMPOSE_SIGNATURES = {
     "bfsc_difference_compose": (ci, [vp, vp, u32, u64, u64, ctypes.POINTER(u64), u32, ci, vp, vp]),
 }
 
+# include/bfstark_segments.h: the commitment codewords of prove_deep(segmented=True) (prefix bfsg_; the header says why); bound together with the five tables above
+_SEGMENTS_SIGNATURES = {
+    "bfsg_decimate_rows": (ci, [vp, u64, u32, vp, u64, u64, u32, vp]),
+}
+
 
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
@@ -297,6 +302,11 @@ def compose_exported_symbols():
     return sorted(_COMPOSE_SIGNATURES)
 
 
+def segments_exported_symbols():
+    """names include/bfstark_segments.h declares"""
+    return sorted(_SEGMENTS_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -314,7 +324,7 @@ def load():
         pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()) + list(_ROUNDS_SIGNATURES.items())
-                              + list(_COMPOSE_SIGNATURES.items())):
+                              + list(_COMPOSE_SIGNATURES.items()) + list(_SEGMENTS_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -28,7 +28,7 @@ from .randomness import source as random_source
 from . import _lib, air, arrays, salted_merkle as salted_mod, table as table_mod
 from .algebra import BaseField, BaseFieldElement
 from .arrays import BaseArray, XArray, raw_ntt
-from .device import DeviceView, GatherBatch, current_stream, gather, synchronize
+from .device import DeviceBuffer, DeviceView, GatherBatch, current_stream, gather, synchronize
 from .evaluation_argument import EvaluationArgument, ProgramEvaluationArgument
 from .extension_field import ExtensionField, ExtensionFieldElement
 from .fri import MAX_GRINDING_BITS, Fri
@@ -37,7 +37,7 @@ from .io_table import InputTable, OutputTable
 from .ip import ProofStream
 from .memory_table import MemoryTable
 from .merkle import CosetMerkle, Merkle, leaf_pickle_source
-from .pcs import PolynomialCommitment
+from .pcs import MAX_EXT_COLUMNS, PolynomialCommitment
 from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
@@ -80,16 +80,19 @@ def _seed_or_stream(draw, nbytes):
     return None, draw(nbytes)
 
 
-def deep_opening_plan(tables, z):
+def deep_opening_plan(tables, z, segments=1):
     """The one opening of prove_deep / verify_deep at the drawn point z (a limb triple), from public data alone: the tables' heights,
     widths and subgroup generators.  The columns are those of the three commitments numbered through (PolynomialCommitment.
-    global_column): every table's base columns in table order, then every table's extension columns, then H.
+    global_column): every table's base columns in table order, then every table's extension columns, then H -- or, in the segmented
+    mode, the `segments` (1 .. 16, pcs.MAX_EXT_COLUMNS) segments H_0 .. H_{s-1} of H.
       * one group per table with rows: its base columns, then its extension columns, at [z, z * omicron] -- at [z] alone for a table of
         height 1, whose next row is its own row (omicron = 1);
       * one group of the columns of all tables without rows at [z], if there is such a table (their polynomials are zero);
-      * a last group (H) at [z].
+      * a last group (H, or all its segments) at [z].
     -> namespace: groups (the plan as `open_rounds` takes it), widths (the commitments' row widths), table_group (per table the index
     of its group, None for a table without rows), empty_group (index or None), h_group"""
+    if not (type(segments) is int and 1 <= segments <= MAX_EXT_COLUMNS):
+        raise ValueError("the composition polynomial has 1 .. %d segments (got %r)" % (MAX_EXT_COLUMNS, segments))
     z = tuple(int(v) for v in z)
     num_base = sum(t.base_width for t in tables)
     base_at, ext_at = 0, num_base
@@ -108,8 +111,8 @@ def deep_opening_plan(tables, z):
     if empty:
         empty_group = len(groups)
         groups.append((sorted(empty), [z]))
-    groups.append(([ext_at], [z]))
-    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, 1), table_group=table_group, empty_group=empty_group,
+    groups.append((list(range(ext_at, ext_at + segments)), [z]))
+    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, segments), table_group=table_group, empty_group=empty_group,
                            h_group=len(groups) - 1)
 
 
@@ -289,6 +292,7 @@ class BrainfuckStark:
                        folding_factor=folding_factor, coset_leaves=coset_leaves, grinding_bits=grinding_bits)
         self._default_fri = folding_factor == 2 and not coset_leaves and grinding_bits == 0          # the reference's protocol
         self._layout = _TermLayout(self.tables, self.permutation_arguments, self.max_degree)
+        self._segmented_fri = {}          # domain length -> the second Fri of the segmented prove_deep / verify_deep (deep_segmented_shape)
 
     def get_terminals(self):
         """the five terminals as int triples (:103-109)"""
@@ -917,7 +921,39 @@ class BrainfuckStark:
     # ---- proving by out-of-domain openings ("Proving by out-of-domain openings"): commitments in rounds through
     # pcs.PolynomialCommitment, the quotients composed into ONE polynomial H, everything opened at one drawn point z with one FRI proof.
     # A second protocol beside prove() / verify(), through Python stages only; the reference has no counterpart.
-    def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None):
+    def deep_segmented_shape(self):
+        """The domains of the segmented mode of prove_deep / verify_deep ("Segmented composition"), from public data alone.
+        With e the expansion factor:
+          L  the power of two >= the largest coefficient count of a trace interpolant (Table.transform_coefficients), at least 1;
+          S  max(max_degree + 1, L): the coefficients of H, as in the unsegmented mode;
+          s  S // L segments H_i of L coefficients each, H(x) = sum_i x^(i L) H_i(x);
+          n  e L, the length of the commitment and FRI domain offset * omega_n^i (offset the field's generator, as self.fri's);
+          w  max(n, S), the length of the working domain the trace is extended to: the commitment domain is every (w / n)-th of its
+             points, the points H is computed on every (w / S)-th.
+        s > 16 (pcs.MAX_EXT_COLUMNS) is refused with a ValueError.  It cannot arise with this AIR at e >= 4: a table's transition
+        degree is at most 10 h_t + 1 (the processor's), so S <= 16 h for the tallest table's h, while L >= 2 h holds its h + 1
+        coefficients -- s <= 8 (and >= 2: the memory table's 2 h_t + 1).
+        -> namespace L, S, s, n, w, fri (a second Fri over the n points with the constructor's modes, made on first use and kept),
+        domain (its domain), working_domain"""
+        f, e = BrainfuckStark.field, self.expansion_factor
+        L = BrainfuckStark.roundup_npo2(max([t.transform_coefficients() for t in self.tables] + [1]))
+        S = max(self.max_degree + 1, L)
+        s = S // L
+        if s > MAX_EXT_COLUMNS:
+            raise ValueError("the composition polynomial would have %d segments of %d coefficients, more than the %d extension columns of a "
+                             "commitment" % (s, L, MAX_EXT_COLUMNS))
+        n = e * L
+        w = max(n, S)
+        fri = self._segmented_fri.get(n)
+        if fri is None:
+            fri = self._segmented_fri[n] = Fri(f.generator(), f.primitive_nth_root(n), n, e, self.num_colinearity_checks, self.xfield,
+                                               folding_factor=self.fri.folding_factor, coset_leaves=self.fri.coset_leaves,
+                                               grinding_bits=self.fri.grinding_bits)
+        working = fri.domain if w == n else Fri.Domain(f.generator(), f.primitive_nth_root(w), w)
+        return SimpleNamespace(L=L, S=S, s=s, n=n, w=w, fri=fri, domain=fri.domain, working_domain=working)
+
+    def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None,
+                   segmented=False):
         """A proof of the same claim as prove()'s in the form current STARKs use (DEEP-ALI): C0 commits to the 16 base columns, C1 -- after
         the 11 challenges -- to the 9 extension columns, C2 -- after the terminals and one weight per quotient -- to the composition
         polynomial H = sum beta_q quotient_q, computed on every expansion_factor-th point of the domain (bfsc_air_compose) and
@@ -925,14 +961,24 @@ class BrainfuckStark:
         its next row z * omicron, and H at z.  verify_deep() checks the opening and the one identity that ties H(z) to the opened rows.
         The Fri modes of the constructor apply as they are.  Returns the proof bytes; for a false trace too (verify_deep refuses them).
 
+        segmented=True (deep_segmented_shape): the three commitments and the FRI proof live on a domain of expansion_factor * L points, L
+        the power of two that holds a trace interpolant, instead of expansion_factor * (max_degree + 1); the trace is extended to the
+        working domain of max(that, max_degree + 1) points, on which H is computed as before; C0 and C1 commit to every (w / n)-th word
+        of the codewords (bfsg_decimate_rows; the codewords as they lie where w = n), and C2 to the s = (max_degree + 1) / L segments
+        H_i of H(x) = sum_i x^(i L) H_i(x), all opened at z.  The random draws and the order of the stream are the unsegmented mode's;
+        the bytes are not, and each verifier refuses the other mode's proofs.
+
         NOT zero-knowledge: the commitments are not hiding (pcs.py: unsalted row trees, plain values in the proof) and no randomizer
-        polynomial is mixed in; the one trace randomizer per column only keeps the interpolants' shape of prove()."""
+        polynomial is mixed in; the one trace randomizer per column only keeps the interpolants' shape of prove().  In both modes."""
         assert len(processor_matrix) + len(program) == len(instruction_matrix)
+        seg = self.deep_segmented_shape() if segmented else None
+        fri, domain = (seg.fri, seg.working_domain) if segmented else (self.fri, self.fri.domain)
         gc.freeze()          # (as prove(): the trace matrices' objects are not walked by collections during the proof)
         try:
             self.timing, stream, mark = {}, current_stream(), time.perf_counter()
+            # domain, n: where the trace is extended to and H is computed from; the commitments are pc's, on fri's domain (the same unless segmented)
             p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
-                                domain=self.fri.domain, n=self.fri.domain.length, stream=stream, pc=PolynomialCommitment(self.fri), commitments=[])
+                                domain=domain, n=domain.length, stream=stream, pc=PolynomialCommitment(fri), commitments=[], seg=seg)
             for name, stage in (("pad", self._deep_stage_pad), ("base_lde", self._deep_stage_base_lde), ("base_commit", self._deep_stage_base_commit),
                                 ("extend", self._stage_extend), ("ext_lde", self._deep_stage_ext_lde), ("ext_commit", self._deep_stage_ext_commit),
                                 ("composition", self._deep_stage_composition), ("composition_commit", self._deep_stage_composition_commit),
@@ -966,29 +1012,42 @@ class BrainfuckStark:
         return polys
 
     def _deep_stage_base_lde(self, p):
-        p.base_codewords, p.base_coefficients, stride = lde_tables(self.tables, p.domain, keep_coefficients=True)
-        p.base_polys = self._deep_polys(p.base_coefficients, stride, False)
+        p.base_codewords, p.base_coefficients, p.base_stride = lde_tables(self.tables, p.domain, keep_coefficients=True)
+        p.base_polys = self._deep_polys(p.base_coefficients, p.base_stride, False)
         p.prepared_extension = prepare_extension(self.tables)
 
+    def _deep_commit_codewords(self, p, codewords, rows):
+        """the `rows` codewords (or limb planes) a commitment is made to: `codewords` as lde_tables wrote them -- unless the segmented
+        mode's working domain is longer than its commitment domain: then every (w / n)-th word of each, gathered by one launch"""
+        if p.seg is None or p.seg.w == p.seg.n:
+            return codewords
+        n, w = p.seg.n, p.seg.w
+        out = DeviceBuffer(rows * n)
+        _lib.check(_lib.load().bfsg_decimate_rows(codewords.ptr, w, (w // n).bit_length() - 1, out.ptr, n, n, rows, p.stream))
+        return out
+
     def _deep_stage_base_commit(self, p):          # C0: the codewords as lde_tables wrote them are the commitment's rows
-        p.commitments.append(p.pc.commit_evaluated(p.base_polys, p.base_codewords, p.proof_stream))
+        p.base_committed = self._deep_commit_codewords(p, p.base_codewords, len(p.base_polys))
+        p.commitments.append(p.pc.commit_evaluated(p.base_polys, p.base_committed, p.proof_stream))
 
     def _deep_stage_ext_lde(self, p):
-        p.ext_codewords, p.ext_coefficients, stride = lde_tables(self.tables, p.domain, extension=True, keep_coefficients=True)
-        p.ext_polys = self._deep_polys(p.ext_coefficients, stride, True)
+        p.ext_codewords, p.ext_coefficients, p.ext_stride = lde_tables(self.tables, p.domain, extension=True, keep_coefficients=True)
+        p.ext_polys = self._deep_polys(p.ext_coefficients, p.ext_stride, True)
 
     def _deep_stage_ext_commit(self, p):          # C1
-        p.commitments.append(p.pc.commit_evaluated(p.ext_polys, p.ext_codewords, p.proof_stream))
+        p.ext_committed = self._deep_commit_codewords(p, p.ext_codewords, 3 * len(p.ext_polys))
+        p.commitments.append(p.pc.commit_evaluated(p.ext_polys, p.ext_committed, p.proof_stream))
 
     def deep_weight_count(self):
         """one weight per quotient: the tables' (boundary, transition, terminal within a table), then the permutation arguments'"""
         return sum(t.num_quotients() for t in self.tables) + len(self.permutation_arguments)
 
-    def compose_into(self, out, log_step, weights, challenges, terminals):
-        """H on every 2^log_step-th point of the FRI domain into `out` (XArray of N >> log_step elements): bfsc_air_compose per table with
-        rows, bfsc_difference_compose per permutation argument; the first call writes, the others add.  weights: (deep_weight_count(), 3)
-        uint64; weights of a table without rows are skipped."""
-        lib, domain, n = _lib.load(), self.fri.domain, self.fri.domain.length
+    def compose_into(self, out, log_step, weights, challenges, terminals, domain=None):
+        """H on every 2^log_step-th point of `domain` -- the FRI domain unless given; the one the tables' codewords lie on -- into `out`
+        (XArray of N >> log_step elements): bfsc_air_compose per table with rows, bfsc_difference_compose per permutation argument; the
+        first call writes, the others add.  weights: (deep_weight_count(), 3) uint64; weights of a table without rows are skipped."""
+        domain = self.fri.domain if domain is None else domain
+        lib, n = _lib.load(), domain.length
         assert out.n == n >> log_step and out.stride == out.n
         weights = np.ascontiguousarray(weights, dtype=np.uint64)
         as_limbs = lambda w: np.ascontiguousarray(w).reshape(-1).ctypes.data_as(ctypes.POINTER(_u64))
@@ -1016,15 +1075,19 @@ class BrainfuckStark:
         for t in self._terminal_objects(p.terminals):
             p.proof_stream.push(t)
         p.weights = BrainfuckStark._sample_weights(self.deep_weight_count(), p.proof_stream.prover_fiat_shamir(), as_array=True)
-        n, e, lib = p.n, self.expansion_factor, _lib.load()
-        d = n // e
+        n, lib = p.n, _lib.load()
+        # (segmented: the same d = max_degree + 1 points, every (w / d)-th of the working domain -- all of them at expansion factor 4)
+        d = n // self.expansion_factor if p.seg is None else p.seg.S
+        e = n // d
         offset, omega = p.domain.offset.value, p.domain.omega.value
         p.h_values = XArray.empty(d, self.xfield)
-        self.compose_into(p.h_values, e.bit_length() - 1, p.weights, p.challenges, p.terminals)
+        self.compose_into(p.h_values, e.bit_length() - 1, p.weights, p.challenges, p.terminals, domain=p.domain)
         p.h_coefficients = XArray.empty(d, self.xfield)
         raw_ntt(p.h_values.ptr, d, d, p.h_coefficients.ptr, d, d.bit_length() - 1, 3, table_mod._inv(pow(omega, e, P_GOLDILOCKS)), 1, table_mod._inv(d), p.stream)
         _lib.check(lib.bfs_gl_scale(p.h_coefficients.ptr, p.h_coefficients.ptr, d, d, 3, table_mod._inv(offset), p.stream))
-        if debug_checks.enabled():
+        if debug_checks.enabled() and p.seg is not None:
+            self._deep_check_segmented_degree(p)
+        elif debug_checks.enabled():
             # an honest trace: every quotient's degree bound is at most max_degree, so H on the FULL domain interpolates to d coefficients
             full = XArray.empty(n, self.xfield)
             self.compose_into(full, 0, p.weights, p.challenges, p.terminals)
@@ -1032,38 +1095,90 @@ class BrainfuckStark:
             raw_ntt(full.ptr, n, n, coefficients.ptr, n, n.bit_length() - 1, 3, table_mod._inv(omega), 1, table_mod._inv(n), p.stream)
             assert not coefficients.to_numpy()[:, d:].any(), "the composition polynomial has degree >= N / expansion_factor"
 
+    def _deep_check_segmented_degree(self, p):
+        """DEBUG, segmented mode: an honest trace's H has degree < S, so H on 2 S points interpolates to S coefficients.  The points
+        are those of the working domain where it has as many; else the kept interpolants are extended to a domain of 2 S points, on
+        which the tables' codewords lie for the length of this check."""
+        S, w, f, xf = p.seg.S, p.n, BrainfuckStark.field, self.xfield
+        n2 = 2 * S
+        saved = [(t.base_codewords, t.ext_codewords, t._n) for t in self.tables]
+        if w >= n2:
+            domain, log_step = p.domain, (w // n2).bit_length() - 1
+        else:
+            domain, log_step = Fri.Domain(f.generator(), f.primitive_nth_root(n2), n2), 0
+            widths = [(t.base_width, 3 * (t.full_width - t.base_width)) for t in self.tables]
+            buffers = []
+            for k, (coefficients, stride) in enumerate(((p.base_coefficients, p.base_stride), (p.ext_coefficients, p.ext_stride))):
+                rows = sum(pair[k] for pair in widths)
+                buffers.append(DeviceBuffer(rows * n2))
+                raw_ntt(coefficients.ptr, stride, stride, buffers[k].ptr, n2, n2.bit_length() - 1, rows, domain.omega.value, domain.offset.value, 1, p.stream)
+            at = [0, 0]
+            for t, (bw, xw) in zip(self.tables, widths):
+                t.base_codewords, t.ext_codewords, t._n = DeviceView(buffers[0], at[0] * n2, bw * n2), DeviceView(buffers[1], at[1] * n2, xw * n2), n2
+                at = [at[0] + bw, at[1] + xw]
+        try:
+            twice, coefficients = XArray.empty(n2, xf), XArray.empty(n2, xf)
+            self.compose_into(twice, log_step, p.weights, p.challenges, p.terminals, domain=domain)
+            root = pow(domain.omega.value, 1 << log_step, P_GOLDILOCKS)
+            raw_ntt(twice.ptr, n2, n2, coefficients.ptr, n2, n2.bit_length() - 1, 3, table_mod._inv(root), 1, table_mod._inv(n2), p.stream)
+            assert not coefficients.to_numpy()[:, S:].any(), "the composition polynomial has degree >= max_degree + 1"
+        finally:
+            for t, (base, ext, n) in zip(self.tables, saved):
+                t.base_codewords, t.ext_codewords, t._n = base, ext, n
+
+    def _deep_segments(self, p):
+        """the s segments of H as views of its coefficients: segment i holds the coefficients [i L, (i + 1) L) of each limb plane"""
+        L, S, h = p.seg.L, p.seg.S, p.h_coefficients
+        return [XArray(DeviceView(h.buf, i * L, 2 * S + L), L, self.xfield, stride=S) for i in range(p.seg.s)]
+
     def _deep_stage_composition_commit(self, p):          # C2
-        p.commitments.append(p.pc.commit([p.h_coefficients], p.proof_stream))
+        from . import debug_checks
+        if p.seg is None:
+            p.commitments.append(p.pc.commit([p.h_coefficients], p.proof_stream))
+            return
+        p.segments = self._deep_segments(p)
+        if debug_checks.enabled():
+            assert len(p.segments) * p.seg.L == len(p.h_coefficients) and all(len(f) == p.seg.L and f.stride == p.seg.S for f in p.segments), \
+                "the segments do not tile the composition polynomial's coefficients"
+        p.commitments.append(p.pc.commit(p.segments, p.proof_stream))
 
     def _deep_stage_opening(self, p):
         """z, drawn behind C2's root, and the one opening of all 26 columns"""
         p.z = tuple(self.xfield.sample(p.proof_stream.prover_fiat_shamir()).limbs())
         if p.z[1] == 0 and p.z[2] == 0:
             raise ValueError("the drawn point lies in the base field (chance 2^-128): prove again")
-        p.plan = deep_opening_plan(self.tables, p.z)
+        p.plan = deep_opening_plan(self.tables, p.z, segments=1 if p.seg is None else p.seg.s)
         p.opened = p.pc.open_rounds(p.commitments, p.plan.groups, p.proof_stream)
         self._last = {"challenges": p.challenges, "terminals": p.terminals}
         if self.keep_intermediates:
             self._last.update({"commitments": p.commitments, "weights": p.weights, "z": p.z, "plan": p.plan, "h_values": p.h_values,
                                "h_coefficients": p.h_coefficients, "base_polys": p.base_polys, "ext_polys": p.ext_polys,
                                "opened": [[[tuple(v.limbs()) for v in per_point] for per_point in per_group] for per_group in p.opened]})
+            if p.seg is not None:          # the working codewords (w words each) and the committed ones (n words each; the same buffers where w = n)
+                self._last.update({"segments": p.segments, "L": p.seg.L, "S": p.seg.S, "s": p.seg.s, "working_base_codewords": p.base_codewords,
+                                   "working_ext_codewords": p.ext_codewords, "committed_base_codewords": p.base_committed,
+                                   "committed_ext_codewords": p.ext_committed})
         else:
             BrainfuckStark._release(*self.tables)
 
-    def verify_deep(self, proof):
+    def verify_deep(self, proof, segmented=False):
         """the verifier of prove_deep -- host code only (Python ints, hashlib, Fri.verify): the terminals against the public input, output
         and program; the opening of the 26 columns at the plan's points for the values the prover claims (read_rounds); every value of a
         table without rows zero; and
             sum_t sum_q beta_{t,q} constraint_{t,q}(cur_t, nxt_t) Z_kind(z) + sum_j beta_j (lhs_j(z) - rhs_j(z)) / (z - 1) = H(z)
         with Z the zerofier factors of csrc/air.hip: 1 / (z - 1), (z - omicron^-1) / (z^h - 1), 1 / (z - omicron^-1).
-        False with one printed line for every refusal, a malformed stream included; raises nothing."""
+        False with one printed line for every refusal, a malformed stream included; raises nothing.
+        segmented=True verifies prove_deep(segmented=True)'s proofs: the opening is read over the Fri of deep_segmented_shape(), the last
+        group holds the s segments, and the right-hand side is H(z) = sum_i z^(i L) H_i(z).  A proof of the other mode has another
+        shape (widths, domain length) and is refused by the opening's reader like any stream that is not this mode's."""
+        seg = self.deep_segmented_shape() if segmented else None          # (what it raises is about this object, not about the proof)
         try:
-            return self._verify_deep_stream(ProofStream().deserialize(proof))
+            return self._verify_deep_stream(ProofStream().deserialize(proof), seg)
         except Exception as e:          # whatever a stream that is not prove_deep's makes the readers raise
             print("malformed proof: %s" % type(e).__name__)
             return False
 
-    def _verify_deep_stream(self, proof_stream):
+    def _verify_deep_stream(self, proof_stream, seg=None):
         X0, X1, xadd, xsub, xmul, xinv, xpow = air.X0, air.X1, air.xadd, air.xsub, air.xmul, air.xinv, air.xpow
         root0 = proof_stream.pull()
         challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.verifier_fiat_shamir()))
@@ -1085,8 +1200,8 @@ class BrainfuckStark:
         if z[1] == 0 and z[2] == 0:
             print("the drawn point lies in the base field")
             return False
-        plan = deep_opening_plan(self.tables, z)
-        values = PolynomialCommitment(self.fri).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
+        plan = deep_opening_plan(self.tables, z, segments=1 if seg is None else seg.s)
+        values = PolynomialCommitment(self.fri if seg is None else seg.fri).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
         if values is None:
             return False
         if plan.empty_group is not None and any(any(v) for v in values[plan.empty_group][0]):
@@ -1112,7 +1227,10 @@ class BrainfuckStark:
                     at += 1
         for j, pa in enumerate(self.permutation_arguments):
             total = xadd(total, xmul(xmul(weights[at + j], pa.evaluate_difference(rows)), boundary))
-        if total != tuple(values[plan.h_group][0][0]):
+        h_at_z, z_to_L = X0, xpow(z, 1 if seg is None else seg.L)
+        for segment in reversed(values[plan.h_group][0]):          # (Horner in z^L; one segment: H(z) itself)
+            h_at_z = xadd(xmul(h_at_z, z_to_L), tuple(segment))
+        if total != h_at_z:
             print("the composition polynomial does not match the opened rows")
             return False
         return True

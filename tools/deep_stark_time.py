@@ -3,6 +3,13 @@
     python tools/deep_stark_time.py [--program big|loop|...] [--reps 5] [--kernel-reps 20] [--json FILE]
     python tools/deep_stark_time.py --sizes
     python tools/deep_stark_time.py --write-golden DIR
+    python tools/deep_stark_time.py --segmented [--program ...] [--reps 5] [--kernel-reps 20] [--json FILE]
+    python tools/deep_stark_time.py --write-golden-segmented DIR
+
+--segmented: prove_deep and prove_deep(segmented=True) alternating in one process by stage, proof bytes of both modes for the program and
+the four fixture programs, and bfsg_decimate_rows on 2^20 -> 2^19 words over 16 and 27 rows beside a second transform of the kept
+coefficients and a device copy of the output bytes (profiles/deep_stark_segmented.md).  --write-golden-segmented DIR writes the segmented
+proofs of FIXTURES and DIR/deep_segmented.json, on the same seeds.
 
 Without an option: on the 37 254-cycle program of bench.py --full (FRI domain 2^22) prove_deep and prove (Python stages, stage_timing) by
 stage, proof bytes of both, verify_deep, and every bfsc_air_compose launch at log_step 0 and 2 against bfs_air_combine on the same table
@@ -44,6 +51,15 @@ def fixture_file(name, m):
     return "deep_%s_proof.bin" % name if m == mode() else "deep_%s_%s_proof.bin" % (name, modes.mode_id(m).split("_e")[0])
 
 
+# the segmented mode (prove_deep(segmented=True)): the same claims, seeds and FRI modes, a list and file names of their own
+SEGMENTED_FIXTURE_LIST = "deep_segmented.json"
+SEGMENTED_DOMAINS = {"plus1": 1 << 5, "io": 1 << 6, "two_io": 1 << 7, "loop": 1 << 8}          # expansion_factor * L
+
+
+def segmented_fixture_file(name, m):
+    return "deep_segmented_" + fixture_file(name, m)[len("deep_"):]
+
+
 _claims = {}
 
 
@@ -70,19 +86,20 @@ def seed_tag(name):
     return b"deep-" + name.encode()
 
 
-def prove_deep_seeded(name, m=None, prepare=None, matrices=None):
+def prove_deep_seeded(name, m=None, prepare=None, matrices=None, segmented=False):
     """-> (stark, proof) of program `name` on the seeded randomness; prepare(stark) runs before prove_deep; matrices: other traces"""
     from stark_brainfuck_amd import randomness
     stark = make_stark(name, m)
     if prepare is not None:
         prepare(stark)
+    kwargs = {"segmented": True} if segmented else {}
     with randomness.override(modes.Stream(seed_tag(name))):
-        proof = stark.prove_deep(claim(name)[0], *(claim(name)[4] if matrices is None else matrices))
+        proof = stark.prove_deep(claim(name)[0], *(claim(name)[4] if matrices is None else matrices), **kwargs)
     return stark, proof
 
 
-def fixtures(directory=GOLDEN):
-    path = os.path.join(directory, FIXTURE_LIST)
+def fixtures(directory=GOLDEN, listing=FIXTURE_LIST):
+    path = os.path.join(directory, listing)
     if not os.path.exists(path):
         return []
     with open(path) as f:
@@ -126,24 +143,44 @@ def tamperings(proof):
             "a truncated proof": proof[:len(proof) // 2]}
 
 
-def write_golden(directory):
+def segment_tamperings(proof):
+    """name -> bytes: changes to the opened segment values (the last group of a segmented proof's values) verify_deep must refuse"""
+    objects = objects_of(proof)
+
+    def with_segments(change):
+        values = [[list(per_point) for per_point in per_group] for per_group in objects[VALUES_AT]]
+        values[-1][0] = change(values[-1][0])
+        return bytes_of(objects[:VALUES_AT] + [values] + objects[VALUES_AT + 1:])
+    segments = list(objects[VALUES_AT][-1][0])
+    assert len(segments) >= 2 and segments[0].limbs() != segments[1].limbs()
+    return {"a segment value replaced by another canonical value": with_segments(lambda v: v[:-1] + [_bumped(v[-1])]),
+            "two segment values swapped": with_segments(lambda v: [v[1], v[0]] + v[2:])}
+
+
+def write_golden(directory, segmented=False):
     os.makedirs(directory, exist_ok=True)
     entries = []
+    option = "--write-golden-segmented" if segmented else "--write-golden"
     for name, m in FIXTURES:
-        stark, proof = prove_deep_seeded(name, m)
-        assert stark.fri.domain.length == DOMAINS[name]
-        assert make_stark(name, m).verify_deep(proof) is True, "%s %s does not verify" % (name, modes.mode_id(m))
-        assert prove_deep_seeded(name, m)[1] == proof, "two proofs on the same seed differ"
+        stark, proof = prove_deep_seeded(name, m, segmented=segmented)
+        length = stark.deep_segmented_shape().n if segmented else stark.fri.domain.length
+        assert length == (SEGMENTED_DOMAINS if segmented else DOMAINS)[name]
+        kwargs = {"segmented": True} if segmented else {}
+        assert make_stark(name, m).verify_deep(proof, **kwargs) is True, "%s %s does not verify" % (name, modes.mode_id(m))
+        assert prove_deep_seeded(name, m, segmented=segmented)[1] == proof, "two proofs on the same seed differ"
         source, given = PROGRAMS[name]
-        entry = {"file": fixture_file(name, m), "name": name, "program": source, "input": given, "output": "".join(claim(name)[3]), "args": m,
-                 "seed": "shake_256(b'bfs-golden-urandom' + %r)" % seed_tag(name), "fri_domain_length": stark.fri.domain.length,
-                 "proof_len": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest()}
+        entry = {"file": (segmented_fixture_file if segmented else fixture_file)(name, m), "name": name, "program": source, "input": given,
+                 "output": "".join(claim(name)[3]), "args": m, "seed": "shake_256(b'bfs-golden-urandom' + %r)" % seed_tag(name),
+                 "fri_domain_length": length, "proof_len": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest()}
+        if segmented:
+            shape = stark.deep_segmented_shape()
+            entry.update({"segments": shape.s, "segment_length": shape.L, "working_domain_length": shape.w})
         with open(os.path.join(directory, entry["file"]), "wb") as f:
             f.write(proof)
         entries.append(entry)
         print("wrote %s  %d bytes  sha256 %s" % (entry["file"], len(proof), entry["proof_sha256"][:16]), flush=True)
-    with open(os.path.join(directory, FIXTURE_LIST), "w") as f:
-        json.dump({"made_by": "tools/deep_stark_time.py --write-golden", "randomness": "randomness.override(tools.stark_fri_modes.Stream(b'deep-' + name))",
+    with open(os.path.join(directory, SEGMENTED_FIXTURE_LIST if segmented else FIXTURE_LIST), "w") as f:
+        json.dump({"made_by": "tools/deep_stark_time.py " + option, "randomness": "randomness.override(tools.stark_fri_modes.Stream(b'deep-' + name))",
                    "proofs": entries}, f, indent=1, sort_keys=True)
         f.write("\n")
 
@@ -261,13 +298,103 @@ def time_kernels(name, reps):
     return rows
 
 
+def segmented_sizes():
+    """proof bytes of prove_deep in both modes for the four fixture programs"""
+    rows = []
+    for name in PROGRAMS:
+        program, _, _, _, matrices = claim(name)
+        rows.append({"program": name, "fri_domain_length": DOMAINS[name], "segmented_fri_domain_length": SEGMENTED_DOMAINS[name],
+                     "prove_deep_bytes": len(make_stark(name).prove_deep(program, *matrices)),
+                     "prove_deep_segmented_bytes": len(make_stark(name).prove_deep(program, *matrices, segmented=True))})
+        print("SIZE " + json.dumps(rows[-1], sort_keys=True), flush=True)
+    return rows
+
+
+def time_segmented(name, reps):
+    """prove_deep in both modes by stage, ms, ALTERNATING in one process (a warm-up proof of each first, dropped); proof bytes; verify_deep"""
+    program, _, _, _, matrices = claim(name)
+    legs = {"prove_deep": {}, "prove_deep_segmented": {"segmented": True}}
+    series = {label: {"totals": [], "stages": {}} for label in legs}
+    proofs, lengths = {}, {}
+    for rep in range(reps + 1):
+        for label, kwargs in legs.items():
+            stark = make_stark(name)
+            stark.stage_timing = True
+            t0 = time.perf_counter()
+            proofs[label] = stark.prove_deep(program, *matrices, **kwargs)
+            _sync()
+            if rep:
+                series[label]["totals"].append((time.perf_counter() - t0) * 1e3)
+                for stage, seconds in stark.timing.items():
+                    series[label]["stages"].setdefault(stage, []).append(seconds * 1e3)
+            lengths[label] = stark.deep_segmented_shape().n if kwargs else stark.fri.domain.length
+    out = {}
+    for label, kwargs in legs.items():
+        verify_ms = []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            assert make_stark(name).verify_deep(proofs[label], **kwargs) is True
+            verify_ms.append((time.perf_counter() - t0) * 1e3)
+        out[label] = {"total_ms": _mmm(series[label]["totals"]), "stages_ms": {s: _mmm(v) for s, v in series[label]["stages"].items()},
+                      "proof_bytes": len(proofs[label]), "fri_domain_length": lengths[label], "verify_ms": _mmm(verify_ms[1:])}
+    out["segmented_median_below_unsegmented_min"] = out["prove_deep_segmented"]["total_ms"]["median"] < out["prove_deep"]["total_ms"]["min"]
+    return out
+
+
+def time_decimation(reps, log_in=20, log_out=19, coefficients=(1 << 16) + 1):
+    """bfsg_decimate_rows from 2^log_in to 2^log_out words per row over 16 and 27 rows, beside the alternative it was chosen against -- a
+    second transform of the kept `coefficients` coefficients per row onto the 2^log_out points -- and a device copy of the same output
+    bytes; alternating, device events, us"""
+    from stark_brainfuck_amd import _lib
+    from stark_brainfuck_amd.algebra import BaseField
+    from stark_brainfuck_amd.arrays import raw_ntt
+    from stark_brainfuck_amd.device import DeviceBuffer, current_stream
+    lib, stream, f = _lib.load(), current_stream(), BaseField.main()
+    n_in, n_out = 1 << log_in, 1 << log_out
+    omega, offset = f.primitive_nth_root(n_out).value, f.generator().value
+    start, stop = ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.check(lib.bfs_event_create(ctypes.byref(start)))
+    _lib.check(lib.bfs_event_create(ctypes.byref(stop)))
+
+    def timed(call):
+        _lib.check(lib.bfs_event_record(start, stream))
+        call()
+        _lib.check(lib.bfs_event_record(stop, stream))
+        _sync()
+        ms = ctypes.c_float()
+        _lib.check(lib.bfs_event_elapsed_ms(start, stop, ctypes.byref(ms)))
+        return ms.value * 1e3
+    rows_out = []
+    for rows in (16, 27):
+        source, coeffs, out = DeviceBuffer(rows * n_in), DeviceBuffer(rows * coefficients), DeviceBuffer(rows * n_out)
+        for buf in (source, out):
+            _lib.check(lib.bfs_memset(buf.ptr, 1, buf.nbytes, stream))
+        _lib.check(lib.bfs_memset(coeffs.ptr, 0, coeffs.nbytes, stream))
+        calls = {"decimate": lambda: _lib.check(lib.bfsg_decimate_rows(source.ptr, n_in, log_in - log_out, out.ptr, n_out, n_out, rows, stream)),
+                 "second_ntt": lambda: raw_ntt(coeffs.ptr, coefficients, coefficients, out.ptr, n_out, log_out, rows, omega, offset, 1, stream),
+                 "device_copy": lambda: _lib.check(lib.bfs_memcpy_d2d(out.ptr, source.ptr, rows * n_out * 8, stream))}
+        series = {label: [] for label in calls}
+        for rep in range(reps + 2):
+            for label, call in calls.items():
+                us = timed(call)
+                if rep >= 2:
+                    series[label].append(us)
+        rows_out.append({"rows": rows, "words_in": n_in, "words_out": n_out, "us": {label: _mmm(v) for label, v in series.items()}})
+        print("DECIMATE " + json.dumps(rows_out[-1], sort_keys=True), flush=True)
+        for buf in (source, coeffs, out):
+            buf.free()
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--program", default="big")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--sizes", action="store_true")
+    ap.add_argument("--segmented", action="store_true", help="both modes of prove_deep alternating, their proof sizes, the decimation kernel")
     ap.add_argument("--write-golden", default=None)
+    ap.add_argument("--write-golden-segmented", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     import torch
@@ -275,8 +402,20 @@ def main():
         raise SystemExit("no GPU: nothing is proven or timed here")
     if args.write_golden:
         return write_golden(args.write_golden)
+    if args.write_golden_segmented:
+        return write_golden(args.write_golden_segmented, segmented=True)
     result = {}
-    if args.sizes:
+    if args.segmented:
+        name = args.program
+        if name == "big":
+            PROGRAMS["big"] = (modes.BIG, "")
+        result["program"] = name
+        result["proofs"] = time_segmented(name, args.reps)
+        print("SEGMENTED " + json.dumps(result["proofs"], sort_keys=True), flush=True)
+        PROGRAMS.pop("big", None)
+        result["sizes"] = segmented_sizes()
+        result["decimation"] = time_decimation(args.kernel_reps)
+    elif args.sizes:
         result["sizes"] = sizes()
     else:
         name = args.program

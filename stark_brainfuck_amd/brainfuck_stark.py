@@ -13,6 +13,9 @@ Where the time goes in the reference, and where it goes here:
   FRI (:336)                                                        fri.Fri.prove (bfs_fri_commit / bfs_fri_query), round 0 on the
                                                                     combination tree that was just built
 Padding, Fiat-Shamir sampling, transcript assembly and the object-identity bookkeeping of opened rows stay on the host.
+
+The second protocol, proving by out-of-domain openings (prove_deep / verify_deep and their two domain shapes), which the reference has
+no counterpart for, lives in deep_stark.py; the methods of that name here hand over to it, and it reaches back through the object.
 """
 import ctypes
 import gc
@@ -25,10 +28,11 @@ import numpy as np
 from os import urandom          # module-level on purpose: tests patch `brainfuck_stark.urandom` for determinism
 from .randomness import source as random_source
 
-from . import _lib, air, arrays, salted_merkle as salted_mod, table as table_mod
+from . import _lib, air, arrays, deep_stark, salted_merkle as salted_mod, table as table_mod
 from .algebra import BaseField, BaseFieldElement
-from .arrays import BaseArray, XArray, raw_ntt
-from .device import DeviceBuffer, DeviceView, GatherBatch, current_stream, gather, synchronize
+from .arrays import XArray
+from .deep_stark import deep_opening_plan          # (importable from here as before)
+from .device import GatherBatch, current_stream, gather, synchronize
 from .evaluation_argument import EvaluationArgument, ProgramEvaluationArgument
 from .extension_field import ExtensionField, ExtensionFieldElement
 from .fri import MAX_GRINDING_BITS, Fri
@@ -37,7 +41,6 @@ from .io_table import InputTable, OutputTable
 from .ip import ProofStream
 from .memory_table import MemoryTable
 from .merkle import CosetMerkle, Merkle, leaf_pickle_source
-from .pcs import MAX_EXT_COLUMNS, PolynomialCommitment
 from .permutation_argument import PermutationArgument
 from .processor_table import ProcessorTable
 from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
@@ -78,42 +81,6 @@ def _seed_or_stream(draw, nbytes):
     if draw is os.urandom or getattr(draw, "expand_on_device", False):
         return draw(32), None
     return None, draw(nbytes)
-
-
-def deep_opening_plan(tables, z, segments=1):
-    """The one opening of prove_deep / verify_deep at the drawn point z (a limb triple), from public data alone: the tables' heights,
-    widths and subgroup generators.  The columns are those of the three commitments numbered through (PolynomialCommitment.
-    global_column): every table's base columns in table order, then every table's extension columns, then H -- or, in the segmented
-    mode, the `segments` (1 .. 16, pcs.MAX_EXT_COLUMNS) segments H_0 .. H_{s-1} of H.
-      * one group per table with rows: its base columns, then its extension columns, at [z, z * omicron] -- at [z] alone for a table of
-        height 1, whose next row is its own row (omicron = 1);
-      * one group of the columns of all tables without rows at [z], if there is such a table (their polynomials are zero);
-      * a last group (H, or all its segments) at [z].
-    -> namespace: groups (the plan as `open_rounds` takes it), widths (the commitments' row widths), table_group (per table the index
-    of its group, None for a table without rows), empty_group (index or None), h_group"""
-    if not (type(segments) is int and 1 <= segments <= MAX_EXT_COLUMNS):
-        raise ValueError("the composition polynomial has 1 .. %d segments (got %r)" % (MAX_EXT_COLUMNS, segments))
-    z = tuple(int(v) for v in z)
-    num_base = sum(t.base_width for t in tables)
-    base_at, ext_at = 0, num_base
-    groups, table_group, empty = [], [], []
-    for t in tables:
-        bw, xw = t.base_width, t.full_width - t.base_width
-        columns = list(range(base_at, base_at + bw)) + list(range(ext_at, ext_at + xw))
-        base_at, ext_at = base_at + bw, ext_at + xw
-        if t.height == 0:
-            empty += columns
-            table_group.append(None)
-        else:
-            table_group.append(len(groups))
-            groups.append((columns, [z] if t.height == 1 else [z, air.xscale(z, t.omicron.value)]))
-    empty_group = None
-    if empty:
-        empty_group = len(groups)
-        groups.append((sorted(empty), [z]))
-    groups.append((list(range(ext_at, ext_at + segments)), [z]))
-    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, segments), table_group=table_group, empty_group=empty_group,
-                           h_group=len(groups) - 1)
 
 
 class _TermLayout:
@@ -727,31 +694,42 @@ class BrainfuckStark:
         proof = self._prove_native(program, (processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix), proof_stream)
         if proof is not None:
             return proof
-        self.timing, sync_stages, stream, mark = {}, self.stage_timing, current_stream(), time.perf_counter()
         # the per-proof record (nothing in it refers to this object): the matrices in the order of self.tables and what else is given; the stages
         # add draw, randomizer_polynomial, randomizer_codeword, prepared_extension, rows (the _RowBuilder), base_tree, challenges, terminals,
         # extension_tree, weights_seed, combination, combination_tree, indices, unit_distances, known (the opened combination leaves), proof
         p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
-                            domain=self.fri.domain, n=self.fri.domain.length, stream=stream, quotient_degree_bounds=None, quotient_buffers=[])
-        for name, stage in (("pad", self._stage_pad),           # (includes the randomizer's GPU time where it outlasts the padding)
-                            ("randomizer", None), ("base_lde", self._stage_base_lde), ("base_tree", self._stage_base_tree),
-                            ("extend", self._stage_extend), ("ext_lde", self._stage_ext_lde), ("ext_tree", self._stage_ext_tree),
-                            ("quotients", self._stage_quotients), ("combination", self._stage_combination),
-                            ("combination_tree", self._stage_combination_tree), ("openings", self._stage_openings),
-                            ("fri", self._stage_fri), ("serialize", self._stage_serialize)):
+                            domain=self.fri.domain, n=self.fri.domain.length, stream=current_stream(), quotient_degree_bounds=None, quotient_buffers=[])
+        return self._run_stages(p, (("pad", self._stage_pad),           # (includes the randomizer's GPU time where it outlasts the padding)
+                                    ("randomizer", None), ("base_lde", self._stage_base_lde), ("base_tree", self._stage_base_tree),
+                                    ("extend", self._stage_extend), ("ext_lde", self._stage_ext_lde), ("ext_tree", self._stage_ext_tree),
+                                    ("quotients", self._stage_quotients), ("combination", self._stage_combination),
+                                    ("combination_tree", self._stage_combination_tree), ("openings", self._stage_openings),
+                                    ("fri", self._stage_fri), ("serialize", self._stage_serialize)))
+
+    def _run_stages(self, p, stages):
+        """the stage loop of both protocols: stages = (timing key, function of the record `p` or None for a key without a stage), run in
+        order; `timing` gets the keys in that order, split by stage on the GPU too where stage_timing is set.  -> p.proof"""
+        self.timing, mark = {}, time.perf_counter()
+        for name, stage in stages:
             if stage is not None:
                 stage(p)
-            if sync_stages:
-                synchronize(stream)
+            if self.stage_timing:
+                synchronize(p.stream)
             now = time.perf_counter()
             self.timing[name], mark = now - mark, now
         return p.proof
+
+    def _random_source(self):
+        """where a proof draws from: the module's urandom, read now (tests patch it), or this context's shared stream (randomness.override)"""
+        return random_source(urandom)
+
+    _canonical_limbs = staticmethod(_canonical_limbs)          # (deep_stark's verifier reads proofs through the same rule)
 
     def _stage_pad(self, p):
         """randomizer polynomial and codeword (:162-167) -- queued FIRST: padding (:143-148) is host work that draws no randomness, so the
         GPU expands and transforms the randomizer while the host pads (the order of the random draws is the reference's either way)"""
         xf, count = self.xfield, self.max_degree + 1
-        p.draw = random_source(urandom)    # the module's urandom, read now, or this context's shared stream (randomness.override)
+        p.draw = self._random_source()
         seed, blob = _seed_or_stream(p.draw, 3 * 9 * count)      # `count` draws of 27 bytes
         if seed is not None:
             p.randomizer_polynomial = XArray.empty(count, xf)
@@ -918,9 +896,16 @@ class BrainfuckStark:
     def _stage_serialize(self, p):
         p.proof = p.proof_stream.serialize()
 
-    # ---- proving by out-of-domain openings ("Proving by out-of-domain openings"): commitments in rounds through
-    # pcs.PolynomialCommitment, the quotients composed into ONE polynomial H, everything opened at one drawn point z with one FRI proof.
-    # A second protocol beside prove() / verify(), through Python stages only; the reference has no counterpart.
+    # ---- proving by out-of-domain openings: the second protocol, deep_stark.py; these methods hand over to it
+    def deep_shape(self, segmented=False):
+        """The domains of prove_deep / verify_deep as the namespace L, S, s, n, w, fri, domain, working_domain that deep_segmented_shape()
+        describes; segmented=True is that shape.  The unsegmented mode is its case of ONE segment, and both run the same code on their
+        shape: the constructor makes max_degree + 1 a power of two and self.fri's domain expansion_factor times as long, so
+        L = S = max_degree + 1, s = 1, n = w = self.fri.domain.length with fri = self.fri and domain = working_domain = self.fri.domain
+        (these objects: no Fri is made, nothing is refused) say what that mode does -- no decimation (w = n), H on every
+        expansion_factor-th point (w / S), its S coefficients the one segment, and the verifier's Horner loop in z^L over one value H(z)."""
+        return deep_stark.make_shape(self, segmented)
+
     def deep_segmented_shape(self):
         """The domains of the segmented mode of prove_deep / verify_deep ("Segmented composition"), from public data alone.
         With e the expansion factor:
@@ -935,22 +920,7 @@ class BrainfuckStark:
         coefficients -- s <= 8 (and >= 2: the memory table's 2 h_t + 1).
         -> namespace L, S, s, n, w, fri (a second Fri over the n points with the constructor's modes, made on first use and kept),
         domain (its domain), working_domain"""
-        f, e = BrainfuckStark.field, self.expansion_factor
-        L = BrainfuckStark.roundup_npo2(max([t.transform_coefficients() for t in self.tables] + [1]))
-        S = max(self.max_degree + 1, L)
-        s = S // L
-        if s > MAX_EXT_COLUMNS:
-            raise ValueError("the composition polynomial would have %d segments of %d coefficients, more than the %d extension columns of a "
-                             "commitment" % (s, L, MAX_EXT_COLUMNS))
-        n = e * L
-        w = max(n, S)
-        fri = self._segmented_fri.get(n)
-        if fri is None:
-            fri = self._segmented_fri[n] = Fri(f.generator(), f.primitive_nth_root(n), n, e, self.num_colinearity_checks, self.xfield,
-                                               folding_factor=self.fri.folding_factor, coset_leaves=self.fri.coset_leaves,
-                                               grinding_bits=self.fri.grinding_bits)
-        working = fri.domain if w == n else Fri.Domain(f.generator(), f.primitive_nth_root(w), w)
-        return SimpleNamespace(L=L, S=S, s=s, n=n, w=w, fri=fri, domain=fri.domain, working_domain=working)
+        return self.deep_shape(True)
 
     def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None,
                    segmented=False):
@@ -970,73 +940,8 @@ class BrainfuckStark:
 
         NOT zero-knowledge: the commitments are not hiding (pcs.py: unsalted row trees, plain values in the proof) and no randomizer
         polynomial is mixed in; the one trace randomizer per column only keeps the interpolants' shape of prove().  In both modes."""
-        assert len(processor_matrix) + len(program) == len(instruction_matrix)
-        seg = self.deep_segmented_shape() if segmented else None
-        fri, domain = (seg.fri, seg.working_domain) if segmented else (self.fri, self.fri.domain)
-        gc.freeze()          # (as prove(): the trace matrices' objects are not walked by collections during the proof)
-        try:
-            self.timing, stream, mark = {}, current_stream(), time.perf_counter()
-            # domain, n: where the trace is extended to and H is computed from; the commitments are pc's, on fri's domain (the same unless segmented)
-            p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
-                                domain=domain, n=domain.length, stream=stream, pc=PolynomialCommitment(fri), commitments=[], seg=seg)
-            for name, stage in (("pad", self._deep_stage_pad), ("base_lde", self._deep_stage_base_lde), ("base_commit", self._deep_stage_base_commit),
-                                ("extend", self._stage_extend), ("ext_lde", self._deep_stage_ext_lde), ("ext_commit", self._deep_stage_ext_commit),
-                                ("composition", self._deep_stage_composition), ("composition_commit", self._deep_stage_composition_commit),
-                                ("opening", self._deep_stage_opening), ("serialize", self._stage_serialize)):
-                stage(p)
-                if self.stage_timing:
-                    synchronize(stream)
-                now = time.perf_counter()
-                self.timing[name], mark = now - mark, now
-            return p.proof
-        finally:
-            gc.unfreeze()
-
-    def _deep_stage_pad(self, p):          # padding as _stage_pad; no randomizer polynomial is drawn
-        p.draw = random_source(urandom)
-        self._pad_tables(p)
-
-    def _deep_polys(self, coefficients, stride, extension):
-        """the interpolants lde_tables left in `coefficients` as views, in table order: a table's own coefficient count each, one zero
-        coefficient for a table without rows"""
-        polys, at = [], 0
-        for t in self.tables:
-            count = max(t.transform_coefficients(), 1)
-            if extension:
-                for c in range(t.full_width - t.base_width):
-                    polys.append(XArray(DeviceView(coefficients, (at + 3 * c) * stride, 3 * stride), count, self.xfield, stride=stride))
-                at += 3 * (t.full_width - t.base_width)
-            else:
-                polys += [BaseArray(DeviceView(coefficients, (at + c) * stride, stride), count, BrainfuckStark.field) for c in range(t.base_width)]
-                at += t.base_width
-        return polys
-
-    def _deep_stage_base_lde(self, p):
-        p.base_codewords, p.base_coefficients, p.base_stride = lde_tables(self.tables, p.domain, keep_coefficients=True)
-        p.base_polys = self._deep_polys(p.base_coefficients, p.base_stride, False)
-        p.prepared_extension = prepare_extension(self.tables)
-
-    def _deep_commit_codewords(self, p, codewords, rows):
-        """the `rows` codewords (or limb planes) a commitment is made to: `codewords` as lde_tables wrote them -- unless the segmented
-        mode's working domain is longer than its commitment domain: then every (w / n)-th word of each, gathered by one launch"""
-        if p.seg is None or p.seg.w == p.seg.n:
-            return codewords
-        n, w = p.seg.n, p.seg.w
-        out = DeviceBuffer(rows * n)
-        _lib.check(_lib.load().bfsg_decimate_rows(codewords.ptr, w, (w // n).bit_length() - 1, out.ptr, n, n, rows, p.stream))
-        return out
-
-    def _deep_stage_base_commit(self, p):          # C0: the codewords as lde_tables wrote them are the commitment's rows
-        p.base_committed = self._deep_commit_codewords(p, p.base_codewords, len(p.base_polys))
-        p.commitments.append(p.pc.commit_evaluated(p.base_polys, p.base_committed, p.proof_stream))
-
-    def _deep_stage_ext_lde(self, p):
-        p.ext_codewords, p.ext_coefficients, p.ext_stride = lde_tables(self.tables, p.domain, extension=True, keep_coefficients=True)
-        p.ext_polys = self._deep_polys(p.ext_coefficients, p.ext_stride, True)
-
-    def _deep_stage_ext_commit(self, p):          # C1
-        p.ext_committed = self._deep_commit_codewords(p, p.ext_codewords, 3 * len(p.ext_polys))
-        p.commitments.append(p.pc.commit_evaluated(p.ext_polys, p.ext_committed, p.proof_stream))
+        return deep_stark.prove(self, program, (processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix), proof_stream,
+                                self.deep_shape(segmented))
 
     def deep_weight_count(self):
         """one weight per quotient: the tables' (boundary, transition, terminal within a table), then the permutation arguments'"""
@@ -1046,120 +951,7 @@ class BrainfuckStark:
         """H on every 2^log_step-th point of `domain` -- the FRI domain unless given; the one the tables' codewords lie on -- into `out`
         (XArray of N >> log_step elements): bfsc_air_compose per table with rows, bfsc_difference_compose per permutation argument; the
         first call writes, the others add.  weights: (deep_weight_count(), 3) uint64; weights of a table without rows are skipped."""
-        domain = self.fri.domain if domain is None else domain
-        lib, n = _lib.load(), domain.length
-        assert out.n == n >> log_step and out.stride == out.n
-        weights = np.ascontiguousarray(weights, dtype=np.uint64)
-        as_limbs = lambda w: np.ascontiguousarray(w).reshape(-1).ctypes.data_as(ctypes.POINTER(_u64))
-        at, accumulate = 0, 0
-        for t in self.tables:
-            nq = t.num_quotients()
-            if t.height:
-                mine = np.ascontiguousarray(weights[at:at + nq])
-                _lib.check(lib.bfsc_air_compose(t.table_index, t.base_codewords.ptr, t.ext_codewords.ptr, *t._domain_arguments(domain),
-                                                *table_mod._air_arguments(t, challenges, terminals), as_limbs(mine), log_step, accumulate, out.ptr,
-                                                current_stream()))
-                accumulate = 1
-            at += nq
-        for j, pa in enumerate(self.permutation_arguments):
-            lt, rt = self.tables[pa.lhs[0]], self.tables[pa.rhs[0]]
-            mine = np.ascontiguousarray(weights[at + j])
-            _lib.check(lib.bfsc_difference_compose(lt.ext_codeword_ptr(pa.lhs[1]), rt.ext_codeword_ptr(pa.rhs[1]), n.bit_length() - 1, domain.offset.value,
-                                                   domain.omega.value, as_limbs(mine), log_step, accumulate, out.ptr, current_stream()))
-            accumulate = 1
-
-    def _deep_stage_composition(self, p):
-        """terminals, weights, H on the d = N / expansion_factor points offset * omega^(e k), and its d coefficients: a coset inverse
-        transform of length d with root omega^e and the domain's offset"""
-        from . import debug_checks
-        for t in self._terminal_objects(p.terminals):
-            p.proof_stream.push(t)
-        p.weights = BrainfuckStark._sample_weights(self.deep_weight_count(), p.proof_stream.prover_fiat_shamir(), as_array=True)
-        n, lib = p.n, _lib.load()
-        # (segmented: the same d = max_degree + 1 points, every (w / d)-th of the working domain -- all of them at expansion factor 4)
-        d = n // self.expansion_factor if p.seg is None else p.seg.S
-        e = n // d
-        offset, omega = p.domain.offset.value, p.domain.omega.value
-        p.h_values = XArray.empty(d, self.xfield)
-        self.compose_into(p.h_values, e.bit_length() - 1, p.weights, p.challenges, p.terminals, domain=p.domain)
-        p.h_coefficients = XArray.empty(d, self.xfield)
-        raw_ntt(p.h_values.ptr, d, d, p.h_coefficients.ptr, d, d.bit_length() - 1, 3, table_mod._inv(pow(omega, e, P_GOLDILOCKS)), 1, table_mod._inv(d), p.stream)
-        _lib.check(lib.bfs_gl_scale(p.h_coefficients.ptr, p.h_coefficients.ptr, d, d, 3, table_mod._inv(offset), p.stream))
-        if debug_checks.enabled() and p.seg is not None:
-            self._deep_check_segmented_degree(p)
-        elif debug_checks.enabled():
-            # an honest trace: every quotient's degree bound is at most max_degree, so H on the FULL domain interpolates to d coefficients
-            full = XArray.empty(n, self.xfield)
-            self.compose_into(full, 0, p.weights, p.challenges, p.terminals)
-            coefficients = XArray.empty(n, self.xfield)
-            raw_ntt(full.ptr, n, n, coefficients.ptr, n, n.bit_length() - 1, 3, table_mod._inv(omega), 1, table_mod._inv(n), p.stream)
-            assert not coefficients.to_numpy()[:, d:].any(), "the composition polynomial has degree >= N / expansion_factor"
-
-    def _deep_check_segmented_degree(self, p):
-        """DEBUG, segmented mode: an honest trace's H has degree < S, so H on 2 S points interpolates to S coefficients.  The points
-        are those of the working domain where it has as many; else the kept interpolants are extended to a domain of 2 S points, on
-        which the tables' codewords lie for the length of this check."""
-        S, w, f, xf = p.seg.S, p.n, BrainfuckStark.field, self.xfield
-        n2 = 2 * S
-        saved = [(t.base_codewords, t.ext_codewords, t._n) for t in self.tables]
-        if w >= n2:
-            domain, log_step = p.domain, (w // n2).bit_length() - 1
-        else:
-            domain, log_step = Fri.Domain(f.generator(), f.primitive_nth_root(n2), n2), 0
-            widths = [(t.base_width, 3 * (t.full_width - t.base_width)) for t in self.tables]
-            buffers = []
-            for k, (coefficients, stride) in enumerate(((p.base_coefficients, p.base_stride), (p.ext_coefficients, p.ext_stride))):
-                rows = sum(pair[k] for pair in widths)
-                buffers.append(DeviceBuffer(rows * n2))
-                raw_ntt(coefficients.ptr, stride, stride, buffers[k].ptr, n2, n2.bit_length() - 1, rows, domain.omega.value, domain.offset.value, 1, p.stream)
-            at = [0, 0]
-            for t, (bw, xw) in zip(self.tables, widths):
-                t.base_codewords, t.ext_codewords, t._n = DeviceView(buffers[0], at[0] * n2, bw * n2), DeviceView(buffers[1], at[1] * n2, xw * n2), n2
-                at = [at[0] + bw, at[1] + xw]
-        try:
-            twice, coefficients = XArray.empty(n2, xf), XArray.empty(n2, xf)
-            self.compose_into(twice, log_step, p.weights, p.challenges, p.terminals, domain=domain)
-            root = pow(domain.omega.value, 1 << log_step, P_GOLDILOCKS)
-            raw_ntt(twice.ptr, n2, n2, coefficients.ptr, n2, n2.bit_length() - 1, 3, table_mod._inv(root), 1, table_mod._inv(n2), p.stream)
-            assert not coefficients.to_numpy()[:, S:].any(), "the composition polynomial has degree >= max_degree + 1"
-        finally:
-            for t, (base, ext, n) in zip(self.tables, saved):
-                t.base_codewords, t.ext_codewords, t._n = base, ext, n
-
-    def _deep_segments(self, p):
-        """the s segments of H as views of its coefficients: segment i holds the coefficients [i L, (i + 1) L) of each limb plane"""
-        L, S, h = p.seg.L, p.seg.S, p.h_coefficients
-        return [XArray(DeviceView(h.buf, i * L, 2 * S + L), L, self.xfield, stride=S) for i in range(p.seg.s)]
-
-    def _deep_stage_composition_commit(self, p):          # C2
-        from . import debug_checks
-        if p.seg is None:
-            p.commitments.append(p.pc.commit([p.h_coefficients], p.proof_stream))
-            return
-        p.segments = self._deep_segments(p)
-        if debug_checks.enabled():
-            assert len(p.segments) * p.seg.L == len(p.h_coefficients) and all(len(f) == p.seg.L and f.stride == p.seg.S for f in p.segments), \
-                "the segments do not tile the composition polynomial's coefficients"
-        p.commitments.append(p.pc.commit(p.segments, p.proof_stream))
-
-    def _deep_stage_opening(self, p):
-        """z, drawn behind C2's root, and the one opening of all 26 columns"""
-        p.z = tuple(self.xfield.sample(p.proof_stream.prover_fiat_shamir()).limbs())
-        if p.z[1] == 0 and p.z[2] == 0:
-            raise ValueError("the drawn point lies in the base field (chance 2^-128): prove again")
-        p.plan = deep_opening_plan(self.tables, p.z, segments=1 if p.seg is None else p.seg.s)
-        p.opened = p.pc.open_rounds(p.commitments, p.plan.groups, p.proof_stream)
-        self._last = {"challenges": p.challenges, "terminals": p.terminals}
-        if self.keep_intermediates:
-            self._last.update({"commitments": p.commitments, "weights": p.weights, "z": p.z, "plan": p.plan, "h_values": p.h_values,
-                               "h_coefficients": p.h_coefficients, "base_polys": p.base_polys, "ext_polys": p.ext_polys,
-                               "opened": [[[tuple(v.limbs()) for v in per_point] for per_point in per_group] for per_group in p.opened]})
-            if p.seg is not None:          # the working codewords (w words each) and the committed ones (n words each; the same buffers where w = n)
-                self._last.update({"segments": p.segments, "L": p.seg.L, "S": p.seg.S, "s": p.seg.s, "working_base_codewords": p.base_codewords,
-                                   "working_ext_codewords": p.ext_codewords, "committed_base_codewords": p.base_committed,
-                                   "committed_ext_codewords": p.ext_committed})
-        else:
-            BrainfuckStark._release(*self.tables)
+        deep_stark.compose_into(self, out, log_step, weights, challenges, terminals, domain)
 
     def verify_deep(self, proof, segmented=False):
         """the verifier of prove_deep -- host code only (Python ints, hashlib, Fri.verify): the terminals against the public input, output
@@ -1171,69 +963,7 @@ class BrainfuckStark:
         segmented=True verifies prove_deep(segmented=True)'s proofs: the opening is read over the Fri of deep_segmented_shape(), the last
         group holds the s segments, and the right-hand side is H(z) = sum_i z^(i L) H_i(z).  A proof of the other mode has another
         shape (widths, domain length) and is refused by the opening's reader like any stream that is not this mode's."""
-        seg = self.deep_segmented_shape() if segmented else None          # (what it raises is about this object, not about the proof)
-        try:
-            return self._verify_deep_stream(ProofStream().deserialize(proof), seg)
-        except Exception as e:          # whatever a stream that is not prove_deep's makes the readers raise
-            print("malformed proof: %s" % type(e).__name__)
-            return False
-
-    def _verify_deep_stream(self, proof_stream, seg=None):
-        X0, X1, xadd, xsub, xmul, xinv, xpow = air.X0, air.X1, air.xadd, air.xsub, air.xmul, air.xinv, air.xpow
-        root0 = proof_stream.pull()
-        challenges = tuple(BrainfuckStark._sample_weights(11, proof_stream.verifier_fiat_shamir()))
-        root1 = proof_stream.pull()
-        terminal_objects = [proof_stream.pull() for _ in range(5)]
-        terminals = [_canonical_limbs(t) for t in terminal_objects]
-        stored = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
-        for io, ea in zip((self.input_table, self.output_table), self.evaluation_arguments):          # the rule of _verify_head, as a refusal
-            if io.height != 0 and not any(stored[io.terminal_index]) and any(ea.compute_terminal(challenges)):
-                print("evaluation terminal of a non-empty input or output table is zero")
-                return False
-        for ea in self.evaluation_arguments:
-            if tuple(ea.select_terminal(stored)) != tuple(ea.compute_terminal(challenges)):
-                print("a terminal does not match the public input, output or program")
-                return False
-        weights = BrainfuckStark._sample_weights(self.deep_weight_count(), proof_stream.verifier_fiat_shamir())
-        root2 = proof_stream.pull()
-        z = tuple(self.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
-        if z[1] == 0 and z[2] == 0:
-            print("the drawn point lies in the base field")
-            return False
-        plan = deep_opening_plan(self.tables, z, segments=1 if seg is None else seg.s)
-        values = PolynomialCommitment(self.fri if seg is None else seg.fri).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
-        if values is None:
-            return False
-        if plan.empty_group is not None and any(any(v) for v in values[plan.empty_group][0]):
-            print("a column of a table without rows is not zero")
-            return False
-        total, at, rows = X0, 0, []
-        boundary = xinv(xsub(z, X1))
-        for t, g in zip(self.tables, plan.table_group):
-            if g is None:
-                rows.append([X0] * t.full_width)
-                at += t.num_quotients()
-                continue
-            cur = values[g][0]
-            nxt = values[g][1] if len(values[g]) > 1 else cur          # height 1: the next row is the row itself
-            rows.append(cur)
-            off = xsub(z, (table_mod._inv(t.omicron.value), 0, 0))
-            factors = {"boundary": boundary, "transition": xmul(off, xinv(xsub(xpow(z, t.height), X1))), "terminal": xinv(off)}
-            params, memo = t.air_params(challenges), {}
-            for kind, constraints in t.air.all():
-                for e in constraints:
-                    value = air.evaluate(e, cur, nxt, challenges, terminals, params, memo)
-                    total = xadd(total, xmul(xmul(weights[at], value), factors[kind]))
-                    at += 1
-        for j, pa in enumerate(self.permutation_arguments):
-            total = xadd(total, xmul(xmul(weights[at + j], pa.evaluate_difference(rows)), boundary))
-        h_at_z, z_to_L = X0, xpow(z, 1 if seg is None else seg.L)
-        for segment in reversed(values[plan.h_group][0]):          # (Horner in z^L; one segment: H(z) itself)
-            h_at_z = xadd(xmul(h_at_z, z_to_L), tuple(segment))
-        if total != h_at_z:
-            print("the composition polynomial does not match the opened rows")
-            return False
-        return True
+        return deep_stark.verify(self, proof, self.deep_shape(segmented))          # (what deep_shape raises is about this object, not about the proof)
 
     # ------------------------------------------------------------------------------------------------------------
     def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):

@@ -27,12 +27,16 @@ def sb():
 
 
 # ------------------------------------------------------------------------------------------------ 1. domains
-def _shape(sb, running_time, memory_length, program_length, log_expansion_factor=2):
+def _stark(sb, running_time, memory_length, program_length, log_expansion_factor=2):
     from stark_brainfuck_amd.algebra import BaseFieldElement
     from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
     from stark_brainfuck_amd.vm import VirtualMachine
     program = [BaseFieldElement(0, VirtualMachine.field)] * program_length
-    stark = BrainfuckStark(running_time, memory_length, program, [], [], log_expansion_factor, 2 * log_expansion_factor)
+    return BrainfuckStark(running_time, memory_length, program, [], [], log_expansion_factor, 2 * log_expansion_factor)
+
+
+def _shape(sb, running_time, memory_length, program_length, log_expansion_factor=2):
+    stark = _stark(sb, running_time, memory_length, program_length, log_expansion_factor)
     return stark, stark.deep_segmented_shape()
 
 
@@ -60,6 +64,36 @@ def test_the_domains_of_the_four_claims(sb, claim):
     # at expansion factor 16 the commitment domain is the working domain
     _, g16 = _shape(sb, *claim, log_expansion_factor=4)
     assert (g16.L, g16.S, g16.s, g16.n, g16.w) == (L, S, s, 16 * L, 16 * L) and g16.working_domain is g16.domain
+
+
+@pytest.mark.parametrize("log_expansion_factor", [2, 4])
+@pytest.mark.parametrize("claim", sorted(TABLE), ids=lambda c: "t%d_m%d_p%d" % c)
+def test_the_unsegmented_shape_is_the_one_segment_case_on_the_first_fri(sb, claim, log_expansion_factor):
+    from stark_brainfuck_amd.brainfuck_stark import deep_opening_plan
+    stark = _stark(sb, *claim, log_expansion_factor=log_expansion_factor)
+    g = stark.deep_shape(False)
+    assert g.L == g.S == stark.max_degree + 1
+    assert g.s == 1
+    assert g.n == g.w == stark.fri.domain.length
+    assert g.fri is stark.fri
+    assert g.domain is g.working_domain is stark.fri.domain
+    assert stark._segmented_fri == {}          # no second Fri was made
+    assert vars(stark.deep_shape()) == vars(g)          # (the default is the unsegmented shape)
+    numbers = lambda shape: (shape.L, shape.S, shape.s, shape.n, shape.w)
+    again, named = stark.deep_shape(True), stark.deep_segmented_shape()
+    (L, S, s), e = TABLE[claim][:3], 1 << log_expansion_factor
+    assert numbers(again) == numbers(named) == (L, S, s, e * L, max(e * L, S))
+    assert again.fri is named.fri and again.domain is named.domain is named.fri.domain and list(stark._segmented_fri) == [e * L]
+    assert deep_opening_plan(stark.tables, (5, 6, 7), segments=g.s).widths[2] == 1
+
+
+def test_the_unsegmented_shape_is_never_refused(sb, monkeypatch):
+    stark, g = _shape(sb, 19, 19, 10)
+    monkeypatch.setattr(stark, "max_degree", 32 * g.L - 1)
+    one = stark.deep_shape(False)
+    assert (one.L, one.S, one.s) == (32 * g.L, 32 * g.L, 1) and one.fri is stark.fri
+    with pytest.raises(ValueError, match="segments"):
+        stark.deep_shape(True)
 
 
 FOUR_SEGMENTS = "+>+>+>" + "+" * 30 + "<<<+"          # 40 instructions whose memory trace has 142 rows: three cells are left and come back to

@@ -250,6 +250,29 @@ def test_the_debug_switch_checks_the_degree_of_the_composition_on_the_full_domai
         deep.prove_deep_seeded("loop", matrices=[LazyTraceMatrix(np.ascontiguousarray(values), VirtualMachine.field)] + matrices[1:])
 
 
+def _plus1_fixture():
+    return open(os.path.join(GOLDEN, deep.fixture_file("plus1", mode())), "rb").read()
+
+
+def test_the_unsegmented_proof_keeps_its_one_segment_and_commits_to_the_working_codewords(sb):
+    """BrainfuckStark.deep_shape: the mode is the one-segment case -- the segment is H's coefficients, nothing is decimated"""
+    stark, proof = proved("plus1")
+    last, shape = stark._last, stark.deep_shape()
+    assert (last["L"], last["S"], last["s"]) == (shape.L, shape.S, 1) and shape.S == stark.max_degree + 1 == deep.DOMAINS["plus1"] // 4
+    assert len(last["segments"]) == 1 and last["plan"].widths == (16, 9, 1)
+    assert last["segments"][0].to_numpy().shape == (3, shape.S) and np.array_equal(last["segments"][0].to_numpy(), last["h_coefficients"].to_numpy())
+    assert last["committed_base_codewords"] is last["working_base_codewords"] and last["committed_ext_codewords"] is last["working_ext_codewords"]
+    assert last["commitments"][0].codewords is last["working_base_codewords"] and [c.n for c in last["commitments"]] == [shape.n] * 3
+    assert proof == _plus1_fixture()
+
+
+def test_the_debug_switch_leaves_the_unsegmented_bytes_of_plus1(sb, monkeypatch):
+    """BFS_DEBUG=1 on a claim with empty input and output tables: the degree check and the assertion that the segments tile H (one
+    segment here) hold for the honest trace, and the proof is the fixture"""
+    monkeypatch.setenv("BFS_DEBUG", "1")
+    assert deep.prove_deep_seeded("plus1")[1] == _plus1_fixture()
+
+
 def test_every_fixture_is_proven_here():
     assert sorted(e["file"] for e in deep.fixtures()) == sorted(deep.fixture_file(name, m) for name, m in CASES)
 

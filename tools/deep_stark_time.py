@@ -163,7 +163,7 @@ def write_golden(directory, segmented=False):
     option = "--write-golden-segmented" if segmented else "--write-golden"
     for name, m in FIXTURES:
         stark, proof = prove_deep_seeded(name, m, segmented=segmented)
-        length = stark.deep_segmented_shape().n if segmented else stark.fri.domain.length
+        length = stark.deep_shape(segmented).n
         assert length == (SEGMENTED_DOMAINS if segmented else DOMAINS)[name]
         kwargs = {"segmented": True} if segmented else {}
         assert make_stark(name, m).verify_deep(proof, **kwargs) is True, "%s %s does not verify" % (name, modes.mode_id(m))
@@ -327,7 +327,7 @@ def time_segmented(name, reps):
                 series[label]["totals"].append((time.perf_counter() - t0) * 1e3)
                 for stage, seconds in stark.timing.items():
                     series[label]["stages"].setdefault(stage, []).append(seconds * 1e3)
-            lengths[label] = stark.deep_segmented_shape().n if kwargs else stark.fri.domain.length
+            lengths[label] = stark.deep_shape(bool(kwargs)).n
     out = {}
     for label, kwargs in legs.items():
         verify_ms = []

@@ -100,7 +100,11 @@ uint64_t bfs_gl_pow(uint64_t a, uint64_t e);
  * then the input is copied to a buffer of its size first.  Stream-ordered: the call only
  * enqueues kernels (it never measures, synchronises or allocates candidate buffers by itself; it may be captured into a hipGraph once
  * its tables exist, i.e. after one plain call of the same shape).  A pair of buffers that bfs_ntt_tune() found a faster route for is
- * served through the library buffer that call kept.
+ * served through the library buffer that call kept.  A batch of >= 2 full-size three-pass transforms of 64-128 MiB each whose input
+ * and output do not overlap runs column by column, every other column on a second stream that the library keeps next to `stream`
+ * (created at the first such call on `stream`, destroyed by bfs_stream_destroy): that stream is forked from `stream` and joined back
+ * inside the call, so everything the call enqueues runs after what `stream` held before it and before what is enqueued on `stream`
+ * after it; such a call ignores the route of bfs_ntt_tune(), and while `stream` is being captured it keeps to `stream` alone.
  * Errors: BFS_ERR_NOT_ROOT / BFS_ERR_NOT_PRIMITIVE as the reference's asserts; BFS_ERR_TOO_MANY_COEFFS.
  */
 int bfs_gl_ntt(const uint64_t* d_in, uint64_t n_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride,

@@ -15,7 +15,7 @@ namespace bfs {
 // Used by single-pass plans (n <= 4096: up to three register stages).
 // (A persistent variant with next-tile prefetch and 16-byte paired-lane accesses was measured slower: hardware workgroup turnover
 //  already overlaps HBM latency)
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT>
 __global__ void __launch_bounds__(256) ntt_tile_kernel(const PassArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 smem[];
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(256) ntt_tile_kernel(const PassArgs a) {
 #ifndef BFS_NTT_SPLIT_WAVES
 #define BFS_NTT_SPLIT_WAVES 6
 #endif
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT>
 __global__ void __launch_bounds__(256, B2 >= 3 ? BFS_NTT_SPLIT_WAVES : 0) ntt_tile_kernel_split(const PassArgs a) {
     static_assert(B1 == 4 && B2 > 0 && B3 == 0, "two register stages, 16 elements per thread");
     extern __shared__ __attribute__((aligned(16))) u64 smem[];
@@ -133,15 +133,19 @@ static int launch_tile(TileShape<B1, B2, B3, LOGC, MODE>, const PassArgs& a, u32
     if constexpr (MODE == PASS_SINGLE) {
         const size_t lds = (size_t)((B2 > 0 ? ((Cfg::LDS_WORDS + 1) & ~1) + Cfg::TW_WORDS : 0) + row_words) * sizeof(u64);
         if (a.streaming)
-            hipLaunchKernelGGL((ntt_tile_kernel<B1, B2, B3, LOGC, MODE, true>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
+            hipLaunchKernelGGL((ntt_tile_kernel<B1, B2, B3, LOGC, MODE, NTT_NT_ALL>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
         else
-            hipLaunchKernelGGL((ntt_tile_kernel<B1, B2, B3, LOGC, MODE, false>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
+            hipLaunchKernelGGL((ntt_tile_kernel<B1, B2, B3, LOGC, MODE, NTT_NT_NONE>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
     } else {
         const size_t lds = ((Cfg::LDS_WORDS * 4 + 15) & ~15u) + (Cfg::TW_WORDS + row_words) * sizeof(u64);
-        if (a.streaming)
-            hipLaunchKernelGGL((ntt_tile_kernel_split<B1, B2, B3, LOGC, MODE, true>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
+        // (loads alone non-temporal: pass 0 of the column pipeline, the only launch that asks for it)
+        constexpr int NT_FIRST = MODE == PASS_FIRST ? NTT_NT_LOADS : NTT_NT_ALL;
+        if (a.streaming == NT_FIRST)
+            hipLaunchKernelGGL((ntt_tile_kernel_split<B1, B2, B3, LOGC, MODE, NT_FIRST>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
+        else if (a.streaming)
+            hipLaunchKernelGGL((ntt_tile_kernel_split<B1, B2, B3, LOGC, MODE, NTT_NT_ALL>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
         else
-            hipLaunchKernelGGL((ntt_tile_kernel_split<B1, B2, B3, LOGC, MODE, false>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
+            hipLaunchKernelGGL((ntt_tile_kernel_split<B1, B2, B3, LOGC, MODE, NTT_NT_NONE>), dim3(grid_x, batch), dim3(Cfg::W), lds, stream, a);
     }
     BFS_HIP(hipGetLastError());
     return BFS_OK;
@@ -206,26 +210,80 @@ int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* l
 }
 
 // the pass runner: steps first..last of the schedule of plan p over the call's buffers (which step reads and writes what: ntt_make_schedule)
-int ntt_run_steps(const NttCall& c, const NttPlan& p, u64* mid, u32 first, u32 last) {
+// every table the steps of one call read: fetched once per call (each lookup takes the table cache's lock), whatever the number of
+// launches the call is then made of
+struct NttCallTables {
     NttTables tb;
-    BFS_TRY(get_tables(p, c.root, c.shift, c.post_scale, tb));
+    const u64* row[4];
+    const u64* srow[4];
+};
+static int get_call_tables(const NttCall& c, const NttPlan& p, NttCallTables& t) {
+    BFS_TRY(get_tables(p, c.root, c.shift, c.post_scale, t.tb));
+    for (u32 pass = p.expand ? 1 : 0; pass < p.npass && pass < 4; ++pass) BFS_TRY(get_row_tables(p, pass, c.root, &t.row[pass], &t.srow[pass]));   // (the passes of ntt_make_schedule)
+    return BFS_OK;
+}
+// nt_in: the NTT_NT_* mask of the step that reads the caller's input; every other step takes c.streaming
+static int run_steps(const NttCall& c, const NttPlan& p, u64* mid, u32 first, u32 last, const NttCallTables& t, u32 nt_in) {
     const NttSchedule s = ntt_make_schedule(p, c.n_in, mid != nullptr);
     const struct { u64* ptr; u64 stride; } buf[3] = {{const_cast<u64*>(c.in), c.in_stride}, {c.out, c.out_stride}, {mid, 1ull << p.log_n}};
+    NttTables tb = t.tb;
     for (u32 k = first; k <= last && k < s.nsteps; ++k) {
         const NttStep& st = s.step[k];
-        BFS_TRY(get_row_tables(p, st.pass, c.root, &tb.row, &tb.srow));
+        tb.row = t.row[st.pass];
+        tb.srow = t.srow[st.pass];
         PassArgs a = ntt_pass_args(p, st.pass, buf[st.src].ptr, buf[st.dst].ptr, buf[st.src].stride, buf[st.dst].stride, st.count, tb, c.shift != 1, c.shift, c.post_scale);
-        a.streaming = c.streaming;
+        a.streaming = st.src == NTT_BUF_IN ? nt_in : c.streaming;
         const int rc = ntt_with_tile_shape(st.mode, st.S, [&](auto shape) { return launch_tile(shape, a, st.grid_x, c.batch, c.stream); });
         if (rc == BFS_ERR_BAD_ARG) set_error("internal: no tile kernel for a %u-bit digit in mode %u", st.S, st.mode);
         BFS_TRY(rc);
     }
     return BFS_OK;
 }
+int ntt_run_steps(const NttCall& c, const NttPlan& p, u64* mid, u32 first, u32 last) {
+    NttCallTables t;
+    BFS_TRY(get_call_tables(c, p, t));
+    return run_steps(c, p, mid, first, last, t, c.streaming);
+}
+
+// The column pipeline.  A batch of three-pass transforms of 64-128 MiB each runs COLUMN BY COLUMN, even columns on the caller's
+// stream and odd ones on the library's second stream of that stream (runtime.cpp: stream_pair): a column's three passes follow each
+// other on one stream, so the column it is building stays in the 256 MiB Infinity Cache from its pass 0 to its pass 2 instead of
+// going to HBM and back twice, and while one column runs its in-place passes out of the cache the other stream's pass 0 uses the HBM
+// bandwidth they leave idle.  Exactly two streams: three and four measured slower than two, one stream slower than one launch per
+// pass for the whole batch (profiles/r04/ab_l3_pipeline.txt: launch tails).  The second stream is forked from the caller's with an
+// event before the first launch and joined back after the last, so the call stays ordered on the caller's stream like any other;
+// the join is enqueued on every way out, a failed launch included, so that nothing the helper already holds can be overtaken.
+// Cache policy (profiles/ntt_column_pipeline.md): pass 0 reads the caller's input once, non-temporal, so that it does not evict the
+// columns in flight; everything else is an ordinary access.  BFS_NTT_STREAMING=0 / 1 forces all-ordinary / all-non-temporal.
+static int ntt_run_columns(const NttCall& c, const NttPlan& p) {
+    const NttEnv& env = ntt_env();
+    StreamPair sp;
+    BFS_TRY(stream_pair(c.stream, &sp));
+    NttCallTables t;
+    BFS_TRY(get_call_tables(c, p, t));
+    const u32 nt_rest = env.force_streaming > 0 ? NTT_NT_ALL : NTT_NT_NONE;
+    const u32 nt_in = env.force_streaming >= 0 ? nt_rest : NTT_NT_LOADS;
+    BFS_HIP(hipEventRecord(sp.fork, c.stream));
+    BFS_HIP(hipStreamWaitEvent(sp.helper, sp.fork, 0));
+    int rc = BFS_OK;
+    for (u32 col = 0; rc == BFS_OK && col < c.batch; ++col) {
+        NttCall one = c;
+        one.in = c.in + (u64)col * c.in_stride;
+        one.out = c.out + (u64)col * c.out_stride;
+        one.batch = 1;
+        one.streaming = nt_rest;
+        one.stream = (col & 1) ? sp.helper : c.stream;
+        rc = run_steps(one, p, nullptr, 0, 3, t, nt_in);
+    }
+    if (hipEventRecord(sp.join, sp.helper) != hipSuccess || hipStreamWaitEvent(c.stream, sp.join, 0) != hipSuccess) {
+        if (rc == BFS_OK) { set_error("bfs_gl_ntt: joining the column pipeline's second stream failed"); rc = BFS_ERR_HIP; }
+    }
+    return rc;
+}
 
 const NttEnv& ntt_env() {
     static const NttEnv env = [] {
-        NttEnv v{NttRouteMode::Remembered, NTT_ROUTE_DIRECT, false, -1, true, false};
+        NttEnv v{NttRouteMode::Remembered, NTT_ROUTE_DIRECT, false, -1, true, false, NttPipeline::BySize};
         if (const char* e = getenv("BFS_NTT_WS_PROBE")) {
             if (e[0] == '0' || !strcmp(e, "direct")) v.route_mode = NttRouteMode::Forced;
             else if (!strncmp(e, "buffer", 6) && e[6] >= '0' && e[6] < '0' + NTT_ROUTE_CANDIDATES && !e[7]) { v.route_mode = NttRouteMode::Forced; v.forced_route = e[6] - '0'; }
@@ -235,6 +293,7 @@ const NttEnv& ntt_env() {
         if (const char* e = getenv("BFS_NTT_STREAMING")) v.force_streaming = atoi(e);
         if (const char* e = getenv("BFS_NTT_EXPAND")) v.allow_expand = e[0] != '0';
         v.plan_log = getenv("BFS_NTT_PLAN_LOG") != nullptr;
+        if (const char* e = getenv("BFS_NTT_PIPELINE")) v.pipeline = !strcmp(e, "force") ? NttPipeline::Forced : e[0] == '0' ? NttPipeline::Off : NttPipeline::BySize;
         return v;
     }();
     return env;
@@ -290,12 +349,27 @@ int ntt_launch(const u64* d_in, u64 n_in, u64 in_stride, u64* d_out, u64 out_str
         return BFS_OK;
     }
     // non-temporal data accesses once a buffer of the call no longer fits the Infinity Cache next to its neighbours (ntt_core.hpp)
-    const u32 streaming = env.force_streaming >= 0 ? (u32)(env.force_streaming != 0) : (u32)((u64)n * batch * sizeof(u64) > NTT_STREAMING_BYTES);
+    const bool nt = env.force_streaming >= 0 ? env.force_streaming != 0 : (u64)n * batch * sizeof(u64) > NTT_STREAMING_BYTES;
+    const u32 streaming = nt ? NTT_NT_ALL : NTT_NT_NONE;
     const NttCall c{d_in, n_in, in_stride, d_out, out_stride, batch, root, shift, post_scale, streaming, stream};
     if (env.plan_log) fprintf(stderr, "ntt plan: log_n %u n_in %llu batch %u overlap %d allow %d in %p out %p\n", log_n, (unsigned long long)n_in, batch, (int)overlap, (int)env.allow_expand, (const void*)d_in, (void*)d_out);
     // Large out-of-place transforms: which buffer pass 0 writes to is chosen by measurement (ntt_route.cpp)
     int route = NTT_ROUTE_DIRECT;
     if (!overlap && !p.expand && p.npass > 1) BFS_TRY(ntt_route(c, p, &route));
+    // Column by column on two streams (ntt_run_columns) where a column fits the Infinity Cache and two of them just do not: full-size
+    // out-of-place batches of three-pass transforms of 64-128 MiB each; BFS_NTT_PIPELINE=force: of any multi-pass transform (what
+    // lets the tests be small), =0: never.  A stream that is being captured keeps one launch per pass: the second stream and its
+    // events are not part of the caller's graph.  The pipeline writes pass 0 straight to the output: a remembered route through an
+    // intermediate buffer is ignored here, since a third 128 MiB buffer per column is what the cache has no room for.
+    bool columns = batch >= 2 && !overlap && !p.expand && n_in == n && env.pipeline != NttPipeline::Off &&
+                   (env.pipeline == NttPipeline::Forced ? p.npass >= 2 : p.npass == 3 && n * sizeof(u64) >= NTT_PIPELINE_MIN_BYTES && n * sizeof(u64) <= NTT_PIPELINE_MAX_BYTES);
+    if (columns) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); columns = false; }
+        else if (cap != hipStreamCaptureStatusNone) columns = false;
+    }
+    if (env.plan_log) fprintf(stderr, "ntt route: %s\n", columns ? "pipelined columns" : overlap ? "staged" : p.expand ? "expansion" : route >= 0 ? "single launch via buffer" : "single launch");
+    if (columns) return ntt_run_columns(c, p);
     u64* mid = nullptr;
     if (overlap || route >= 0) {
         void* w = nullptr;

@@ -152,21 +152,24 @@ template <int BITS>
 BFS_HD u32 perm_digit(int m, u32 uinv) { return (cx_bitrev((u32)m, BITS) * uinv) & ((1u << BITS) - 1); }
 
 // Streaming accesses.  Every element is read once and written once per pass, so when the data set is larger than the caches
-// nothing is gained by keeping it there: the NT = true instantiations mark the data loads and stores non-temporal (the twiddle
+// nothing is gained by keeping it there: the NT = NTT_NT_ALL instantiations mark the data loads and stores non-temporal (the twiddle
 // tables stay ordinary, cached reads).  8 x 2^24: 1.45 -> 1.41 ms, the memory-bound first pass 463 -> 437 us
 // (profiles/r02/ab_nontemporal.txt); a single 2^24 column, which lives in the 256 MiB Infinity Cache, is 2 % SLOWER with the
 // hint, so the launcher only uses it above NTT_STREAMING_BYTES per buffer (ntt.hip).
-template <bool NT>
+// NT is a mask, loads and stores apart: the column pipeline (ntt.hip: ntt_run_columns) reads its input once, non-temporal, and
+// writes the column it is building with ordinary stores, so that the next pass finds it in the Infinity Cache.
+enum { NTT_NT_NONE = 0, NTT_NT_LOADS = 1, NTT_NT_STORES = 2, NTT_NT_ALL = 3 };
+template <int NT>
 BFS_HD u64 ntt_ld(const u64* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (NT) return __builtin_nontemporal_load(p);
+    if constexpr ((NT & NTT_NT_LOADS) != 0) return __builtin_nontemporal_load(p);
 #endif
     return *p;
 }
-template <bool NT>
+template <int NT>
 BFS_HD void ntt_st(u64* p, u64 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (NT) { __builtin_nontemporal_store(v, p); return; }
+    if constexpr ((NT & NTT_NT_STORES) != 0) { __builtin_nontemporal_store(v, p); return; }
 #endif
     *p = v;
 }
@@ -216,7 +219,7 @@ struct PassArgs {
     u32 has_coset;       // pass 0: multiply input j by s^j
     u64 coset_delta;     // s^(stride of the stage-1 register index)
     u64 post_scale;      // last pass: n^-1 of intt (folded into tw1 / tw2 below, or multiplied in at the store of a single-stage pass); else 1
-    u32 streaming;       // data loads / stores are non-temporal (the launcher picks the NT instantiation; kept here for the record)
+    u32 streaming;       // NTT_NT_* mask: which data accesses are non-temporal (the launcher picks the NT instantiation; kept here for the record)
     // Balanced twiddle schedule of a three-pass plan (ntt_plan.hpp).  The factor in front of pass 2 splits,
     // w_N^(j2 (k0 + n0 k1)) = w_N^(j2 k0) * w_{n1 n2}^(j2 k1), and each piece goes where one of its indices is tile-uniform AND where
     // there is room:
@@ -368,7 +371,7 @@ BFS_HD void stage2_pos(u32 G, u32& c, u32& f1, u32& f3) {
 
 // store the 2^BQ registers of the last stage.  klow = the already-final lower digits of k_pass, c = column;
 // srow (LDS, or null): the store-time factors of the tile's output rows
-template <typename Cfg, int LOGC, int MODE, int BQ, bool NT = false>
+template <typename Cfg, int LOGC, int MODE, int BQ, int NT = 0>
 BFS_HD void final_store(const PassArgs& a, const TileGeom& g, const u64* x, u32 klow, int kshift, u32 c, const u64* srow = nullptr) {
     constexpr int Q = 1 << BQ;
     const bool scale = (Cfg::U == 1) && a.post_scale != 1;
@@ -428,7 +431,7 @@ BFS_HD Stage1Pos<B1, B2, B3, LOGC, MODE> stage1_pos(const PassArgs& a, const Til
     return p;
 }
 
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage1_load(const PassArgs& a, u32 tid, u32 bid_x, u32 bid_y, int sub, u64* x) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
     constexpr int Q = 1 << B1;
@@ -474,7 +477,7 @@ BFS_HD u32 stage2_in_index(u32 tid, int s, int d) {
 // stage 1 without the exchange: load-time twiddle, first radix and (U >= 2) the inner twiddle; x[m] is left holding the value
 // that stage1_out_index(m) receives.  U == 1: the values are final and are stored.
 // tw: dense inner-twiddle table for the stage 1 -> 2 exchange (2^(B1+B2) entries of a.tw1, in LDS on the GPU)
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage1_values(const PassArgs& a, const u64* tw, const u64* rowtw, u32 tid, u32 bid_x, u32 bid_y, int sub, u64* x,
                               const u64* srow = nullptr) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
@@ -571,7 +574,7 @@ BFS_HD void ntt_stage1_values(const PassArgs& a, const u64* tw, const u64* rowtw
     }
 }
 
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage1_compute(const PassArgs& a, u64* smem, const u64* tw, const u64* rowtw, u32 tid, u32 bid_x, u32 bid_y, int sub, u64* x,
                                const u64* srow = nullptr) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
@@ -595,7 +598,7 @@ BFS_HD void ntt_stage1(const PassArgs& a, u64* smem, const u64* tw, const u64* r
 
 // ---- stage 2: LDS read, second radix, (inner twiddle + LDS write) or final store
 // ntt_stage2_from: sub-group s of thread `tid` once its 2^B2 values are in x[] (however they got there)
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage2_from(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u32 bid_y, int s, u64* x, const u64* srow = nullptr) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
     if constexpr (B2 > 0) {
@@ -620,7 +623,7 @@ BFS_HD void ntt_stage2_from(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u3
     }
 }
 
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage2(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u32 bid_y, const u64* srow = nullptr) {
     if constexpr (B2 > 0) {
         constexpr int Q = 1 << B2, SG = 16 / Q;
@@ -635,7 +638,7 @@ BFS_HD void ntt_stage2(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u32 bid
 }
 
 // ---- stage 3: LDS read, third radix, final store
-template <int B1, int B2, int B3, int LOGC, int MODE, bool NT = false>
+template <int B1, int B2, int B3, int LOGC, int MODE, int NT = 0>
 BFS_HD void ntt_stage3(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u32 bid_y, const u64* srow = nullptr) {
     typedef TileCfg<B1, B2, B3, LOGC, MODE> Cfg;
     if constexpr (B3 > 0) {

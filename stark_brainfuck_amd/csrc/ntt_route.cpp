@@ -271,7 +271,7 @@ int ntt_tune(const u64* d_in, u64 in_stride, u64* d_out, u64 out_stride, u32 log
         return BFS_ERR_BAD_ARG;
     }
     (void)hipGetLastError();
-    const NttCall c{d_in, n, in_stride, d_out, out_stride, batch, root, 1, 1, (u32)((u64)n * batch * sizeof(u64) > NTT_STREAMING_BYTES), stream};
+    const NttCall c{d_in, n, in_stride, d_out, out_stride, batch, root, 1, 1, (u64)n * batch * sizeof(u64) > NTT_STREAMING_BYTES ? (u32)NTT_NT_ALL : (u32)NTT_NT_NONE, stream};
     int dev = 0;
     BFS_HIP(hipGetDevice(&dev));
     int route = NTT_ROUTE_DIRECT;

@@ -31,6 +31,12 @@ struct Scratch {
 };
 std::mutex g_mu;
 std::map<std::tuple<int, hipStream_t, int>, Scratch> g_scratch;
+std::map<std::pair<int, hipStream_t>, StreamPair> g_stream_pairs;        // (runtime.hpp: stream_pair)
+void destroy_stream_pair(const StreamPair& sp) {
+    if (sp.fork) (void)hipEventDestroy(sp.fork);
+    if (sp.join) (void)hipEventDestroy(sp.join);
+    if (sp.helper) (void)hipStreamDestroy(sp.helper);
+}
 std::map<std::tuple<int, uint64_t, uint64_t, uint64_t>, const u64*> g_tables;
 // Tables are keyed by caller-supplied values (roots, coset shifts, post-scales), so a caller that sweeps arbitrary shifts would grow
 // the cache without bound.  At TABLE_CAP entries the cache starts over: the tables of the generation before LAST are freed (after a
@@ -293,6 +299,28 @@ bool workspace_peek(int slot, hipStream_t stream, void** ptr, size_t* bytes) {
     return true;
 }
 
+int stream_pair(hipStream_t stream, StreamPair* out) {
+    int dev = 0;
+    BFS_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_mu);
+    auto it = g_stream_pairs.find(std::make_pair(dev, stream));
+    if (it == g_stream_pairs.end()) {
+        StreamPair sp{nullptr, nullptr, nullptr};
+        // non-blocking: ordered against the caller's stream by the two events alone, also when that stream is the null stream
+        hipError_t e = hipStreamCreateWithFlags(&sp.helper, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sp.fork, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sp.join, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            destroy_stream_pair(sp);
+            set_error("creating the library's second stream failed: %s", hipGetErrorString(e));
+            return BFS_ERR_HIP;
+        }
+        it = g_stream_pairs.emplace(std::make_pair(dev, stream), sp).first;
+    }
+    *out = it->second;
+    return BFS_OK;
+}
+
 // give one scratch buffer back to the driver (the NTT's route measurement keeps only the candidate it chose); the stream must be idle
 int workspace_release(int slot, hipStream_t stream) {
     int dev = 0;
@@ -314,6 +342,12 @@ int stream_retire(hipStream_t stream) {
     BFS_HIP(hipGetDevice(&dev));
     {
         std::lock_guard<std::mutex> lock(g_mu);
+        // (whatever the second stream held was joined back into `stream`, which is idle: synchronised above)
+        auto sp = g_stream_pairs.find(std::make_pair(dev, stream));
+        if (sp != g_stream_pairs.end()) {
+            destroy_stream_pair(sp->second);
+            g_stream_pairs.erase(sp);
+        }
         for (auto it = g_scratch.begin(); it != g_scratch.end();) {
             if (std::get<0>(it->first) == dev && std::get<1>(it->first) == stream) {
                 if (it->second.ptr) (void)hipFree(it->second.ptr);

@@ -54,7 +54,18 @@ int host_release(void* ptr);
 int copy_h2d(void* d, const void* h, size_t bytes, hipStream_t stream);
 int copy_d2h(void* h, const void* d, size_t bytes, hipStream_t stream);
 
-// a stream is about to be destroyed: wait for it, free its scratch buffers, forget it in the pools
+// The library's second stream next to a caller's stream, with the events that fork it from that stream and join it back (the NTT's
+// column pipeline).  One per (device, caller's stream), created the first time it is asked for and kept until stream_retire -- not
+// one per device: work of two callers queued on one shared helper would make either caller's stream wait for whatever the OTHER
+// one's stream is waiting for.  Threads that call on different streams share nothing; threads that call on the SAME stream share
+// the pair, and an event recorded twice before it is waited for only makes the wait cover more.
+struct StreamPair {
+    hipStream_t helper;
+    hipEvent_t fork, join;
+};
+int stream_pair(hipStream_t stream, StreamPair* out);
+
+// a stream is about to be destroyed: wait for it, free its scratch buffers and its second stream, forget it in the pools
 int stream_retire(hipStream_t stream);
 
 // upload a host table once and keep it (keyed by caller-chosen values; the cache starts over after 4096 entries, runtime.cpp)
@@ -173,13 +184,17 @@ int ntt_power_tables(u64 root, u32 log_n, const u64** lo, const u64** hi, u32* l
 constexpr int NTT_ROUTE_CANDIDATES = 3;
 constexpr int NTT_ROUTE_DIRECT = -1;                  // a route: direct, or k >= 0 through candidate buffer k
 enum class NttRouteMode { Remembered, Auto, Forced };
+enum class NttPipeline { Off, BySize, Forced };
+constexpr u64 NTT_PIPELINE_MIN_BYTES = 64ull << 20;   // the column pipeline (ntt.hip: ntt_run_columns): bytes of ONE transform's output
+constexpr u64 NTT_PIPELINE_MAX_BYTES = 128ull << 20;
 struct NttEnv {
     NttRouteMode route_mode;      // BFS_NTT_WS_PROBE unset: routes come from bfs_ntt_tune only; "auto" / "1": bfs_gl_ntt tunes a pair itself the third
     int forced_route;             //   time it sees it; "0" / "direct" / "buffer0..2": Forced, this route for every large transform and tune a no-op
     bool probe_log;               // BFS_NTT_WS_PROBE_LOG=1: the route measurements go to stderr
     int force_streaming;          // BFS_NTT_STREAMING=0 / 1 forces the choice (A/B, tools/ab_ntt.sh); -1: by size
     bool allow_expand;            // BFS_NTT_EXPAND=0: zero-padded transforms take the plain plan too
-    bool plan_log;                // BFS_NTT_PLAN_LOG: one stderr line per tiled call
+    bool plan_log;                // BFS_NTT_PLAN_LOG: two stderr lines per tiled call, the plan and the route it took
+    NttPipeline pipeline;         // BFS_NTT_PIPELINE=0 / 1 / force: the column pipeline never / by size (default) / for every multi-pass batch
 };
 const NttEnv& ntt_env();
 

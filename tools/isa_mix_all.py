@@ -9,8 +9,8 @@ text = open(lst).read().split("\n")
 idx = [i for i, l in enumerate(text) if l.startswith("_ZN3bfs21ntt_tile_kernel_split") and ": ; @" in l]
 out = ["Static instruction mix of the dominant NTT kernels: gfx950 listing made with the library's flags (stark_brainfuck_amd.build.build_listings():",
        "hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S), mnemonics counted between a kernel's label and .Lfunc_end (tools/isa_mix_all.py).",
-       "The 8 x 2^24 step runs ntt_tile_kernel_split<4,4,0,4,MODE,NT=true> three times: MODE 2 (PASS_FIRST: transposing, coset / padding fused) once,",
-       "MODE 0 (PASS_COLUMN: in place) twice.  The code is straight-line: a thread executes the listing once per tile (16 elements x 8 butterfly levels).", ""]
+       "The 8 x 2^24 step runs ntt_tile_kernel_split<4,4,0,4,MODE,NT> three times per column: MODE 2 (PASS_FIRST: transposing, coset / padding fused;",
+       "NT 1, loads non-temporal) once, MODE 0 (PASS_COLUMN: in place; NT 0) twice.  The code is straight-line: a thread executes the listing once per tile (16 elements x 8 butterfly levels).", ""]
 
 
 def mix(start):
@@ -37,7 +37,7 @@ def mix(start):
 for i in idx:
     name = text[i].split(":")[0]
     d = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    if "ntt_tile_kernel_split<4, 4, 0, 4" not in d or "true>" not in d:
+    if "ntt_tile_kernel_split<4, 4, 0, 4" not in d or not re.search(r", (2, 1|0, 0)>", d):
         continue
     counts, classes, nops = mix(i)
     out.append(d)

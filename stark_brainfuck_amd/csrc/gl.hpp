@@ -281,15 +281,43 @@ BFS_HD u64 gl_mul_other_form(u64 a, u64 b) {
 // keeps some sums unreduced (gl_add_lazy) and the rule which operands may be such values is enforced here on every emulated transform:
 // violations are counted (tests/emu: emu_canonical_violations) and the tests want zero.  An unreduced sum is only actually >= p
 // when it lands within 2^32 of p -- once in 2^32 for random operands -- so the tests that mean it feed values next to 0 and p.
+// The same build also counts, per site of the NTT tile kernels, the events that decide which branch of a carry chain an operation takes
+// (GL_EV_*): a test that plants operands at a site (ntt_core.hpp: BFS_NTT_SITE, tests/ntt_planted.py) asks these counters whether its
+// operands really drove the lazy sums over p THERE.  Slot 0 is "before the first site of a call"; an event belongs to the site whose
+// hook ran last, so a site's slot also holds what follows its butterflies: the inner twiddles, gl_canon of the unit-twiddle register,
+// the store-time products, and the load-time products of the next thread.
 #ifdef BFS_CHECK_CANONICAL
 inline unsigned long long& gl_canonical_violations() { static unsigned long long count = 0; return count; }      // (the emulation is single-threaded)
 #define BFS_CANONICAL(x) do { if (!((x) < GL_P)) ++gl_canonical_violations(); } while (0)
+enum {
+    GL_EV_LAZY_GE_P = 0,       // gl_add_lazy: no wrap, result in [p, 2^64)
+    GL_EV_LAZY_WRAP,           // gl_add_lazy: the 64-bit sum wrapped
+    GL_EV_LAZY_WRAP_GE_P,      // gl_add_lazy: wrapped and still >= p after + EPS
+    GL_EV_LAZY_FIRST_GE_P,     // gl_add_lazy: first operand >= p
+    GL_EV_SUB_MINUEND_GE_P,    // gl_sub: minuend >= p
+    GL_EV_SUB_BORROW,          // gl_sub: borrowed
+    GL_EV_MUL_OPERAND_GE_P,    // gl_mul / gl_mul_lazy: an operand >= p
+    GL_EV_CANON_GE_P,          // gl_canon: operand >= p
+    GL_EV_ADD_WRAP,            // gl_add: the 64-bit sum wrapped
+    GL_EV_ADD_GE_P,            // gl_add: no wrap, sum >= p
+    GL_EV_COUNT
+};
+constexpr int GL_SITE_SLOTS = 1 + 4 * 3;      // slot 1 + 3 * pass + (stage - 1): up to four passes of up to three register stages
+struct GlSiteEvents {
+    int slot = 0;
+    unsigned long long count[GL_SITE_SLOTS][GL_EV_COUNT] = {};
+};
+inline GlSiteEvents& gl_site_events() { static GlSiteEvents e; return e; }
+#define BFS_EVENT(ev, cond) do { if (cond) { GlSiteEvents& e_ = gl_site_events(); ++e_.count[e_.slot][ev]; } } while (0)
 #else
 #define BFS_CANONICAL(x) ((void)0)
+#define BFS_EVENT(ev, cond) ((void)0)
 #endif
 BFS_HD u64 gl_add(u64 a, u64 b) {
     BFS_CANONICAL(a); BFS_CANONICAL(b);
     u64 s = a + b;
+    BFS_EVENT(GL_EV_ADD_WRAP, s < a);
+    BFS_EVENT(GL_EV_ADD_GE_P, !(s < a) && s >= GL_P);
     // a, b < p: either the 64-bit add wrapped (then s + EPS is the canonical value) or s may be >= p
     if (s < a) return s + GL_EPS;
     return s >= GL_P ? s - GL_P : s;
@@ -298,6 +326,8 @@ BFS_HD u64 gl_add(u64 a, u64 b) {
 // any 64-bit a, canonical b
 BFS_HD u64 gl_sub(u64 a, u64 b) {
     BFS_CANONICAL(b);
+    BFS_EVENT(GL_EV_SUB_MINUEND_GE_P, a >= GL_P);
+    BFS_EVENT(GL_EV_SUB_BORROW, a < b);
     u64 d = a - b;
     return a < b ? d - GL_EPS : d;  // borrow: add p (== subtract EPS in wrapped arithmetic)
 }
@@ -306,6 +336,10 @@ BFS_HD u64 gl_sub(u64 a, u64 b) {
 BFS_HD u64 gl_add_lazy(u64 a, u64 b) {
     BFS_CANONICAL(b);
     u64 s = a + b;
+    BFS_EVENT(GL_EV_LAZY_FIRST_GE_P, a >= GL_P);
+    BFS_EVENT(GL_EV_LAZY_GE_P, !(s < a) && s >= GL_P);
+    BFS_EVENT(GL_EV_LAZY_WRAP, s < a);
+    BFS_EVENT(GL_EV_LAZY_WRAP_GE_P, s < a && s + GL_EPS >= GL_P);
     return s < a ? s + GL_EPS : s;
 }
 BFS_HD u64 gl_sub4(u64 a, u64 b) { return gl_sub(a, b); }      // the device's two instruction sequences (selftest.hip compares both with this)
@@ -327,12 +361,20 @@ BFS_HD u64 gl_reduce128(u64 hi, u64 lo) {
 BFS_HD u64 gl_reduce96(u32 top, u64 lo) { return gl_reduce128((u64)top, lo); }
 #endif
 
+#ifndef BFS_EVENT
+#define BFS_EVENT(ev, cond) ((void)0)          // (device code counts nothing)
+#endif
+
 BFS_HD u64 gl_neg(u64 a) { return a ? GL_P - a : 0; }
 // any 64-bit value -> its canonical residue
-BFS_HD u64 gl_canon(u64 a) { return a >= GL_P ? a - GL_P : a; }
+BFS_HD u64 gl_canon(u64 a) {
+    BFS_EVENT(GL_EV_CANON_GE_P, a >= GL_P);
+    return a >= GL_P ? a - GL_P : a;
+}
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 BFS_HD u64 gl_mul(u64 a, u64 b) {
+    BFS_EVENT(GL_EV_MUL_OPERAND_GE_P, a >= GL_P || b >= GL_P);
     u128 z = (u128)a * b;
     return gl_reduce128((u64)(z >> 64), (u64)z);
 }

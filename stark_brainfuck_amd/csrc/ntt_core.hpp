@@ -140,6 +140,38 @@ BFS_HD void dif_sparse(u64* x) {
     }
 }
 
+// BFS_NTT_SITE(pass, stage, x, Q): a site of the tile kernels -- the Q registers of one thread immediately before the butterflies of
+// register stage `stage` (1..3) of pass `pass`.  Nothing in the product.  In the host emulation (-DBFS_CHECK_CANONICAL, tests/emu) the
+// site becomes the one that gl.hpp's event counters count for, and a test may PLANT the registers of one chosen site from a buffer or
+// RECORD them into one, Q words per call in the emulation's call order (tests/emu/emu_ntt.cpp: emu_site_control; tests/ntt_planted.py
+// computes from a planted run the input that puts chosen operands at an inner site).
+#if defined(BFS_CHECK_CANONICAL) && !defined(__HIP_DEVICE_COMPILE__)
+enum { NTT_SITE_OFF = 0, NTT_SITE_PLANT = 1, NTT_SITE_RECORD = 2 };
+struct NttSiteControl {
+    int mode = NTT_SITE_OFF;
+    u32 pass = 0, stage = 0;
+    u64* buf = nullptr;
+    u64 capacity = 0;      // words in buf
+    u64 words = 0;         // words planted / recorded so far
+    u64 overrun = 0;       // words the site asked for beyond the capacity (nothing is read or written there)
+};
+inline NttSiteControl& ntt_site_control() { static NttSiteControl c; return c; }
+inline void ntt_site_hook(u32 pass, u32 stage, u64* x, int q) {
+    gl_site_events().slot = (pass < 4 && stage >= 1 && stage <= 3) ? (int)(1 + 3 * pass + (stage - 1)) : 0;
+    NttSiteControl& c = ntt_site_control();
+    if (c.mode == NTT_SITE_OFF || pass != c.pass || stage != c.stage) return;
+    if (c.words + (u64)q > c.capacity) { c.overrun += (u64)q; return; }
+    for (int d = 0; d < q; ++d) {
+        if (c.mode == NTT_SITE_PLANT) x[d] = c.buf[c.words + d];
+        else c.buf[c.words + d] = x[d];
+    }
+    c.words += (u64)q;
+}
+#define BFS_NTT_SITE(pass, stage, x, q) ntt_site_hook(pass, stage, x, q)
+#else
+#define BFS_NTT_SITE(pass, stage, x, q) ((void)0)
+#endif
+
 constexpr u32 cx_bitrev(u32 v, int bits) {
     u32 r = 0;
     for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1u) << (bits - 1 - i);
@@ -546,6 +578,7 @@ BFS_HD void ntt_stage1_values(const PassArgs& a, const u64* tw, const u64* rowtw
             }
         }
     }
+    BFS_NTT_SITE(a.pass_index, 1, x, Q);
     // U >= 2: every output meets an inner twiddle below (the one with a unit twiddle is reduced there)
     if (Q == 16 && dmax <= 8) {                    // (wave-uniform) zero-padded input: the network for the registers that can be non-zero
         if constexpr (Q == 16) {
@@ -606,6 +639,7 @@ BFS_HD void ntt_stage2_from(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u3
         const TileGeom g = tile_geom<Cfg, LOGC, MODE>(a, bid_x, bid_y);
         u32 c, f1, f3;
         stage2_pos<B1, B2, B3, LOGC, MODE>((u32)s * Cfg::W + tid, c, f1, f3);
+        BFS_NTT_SITE(a.pass_index, 2, x, Q);
         // unreduced outputs where all of them are multiplied next: by the inner twiddles of a third stage, or -- first pass of a multi-pass
         // plan -- by the store-time row here or by the next pass, which multiplies everything it loads
         dif<Q, (Cfg::U == 3 || MODE == PASS_FIRST)>(x);
@@ -653,6 +687,7 @@ BFS_HD void ntt_stage3(const PassArgs& a, u64* smem, u32 tid, u32 bid_x, u32 bid
             u64 x[Q];
             BFS_UNROLL
             for (int d = 0; d < Q; ++d) x[d] = smem[lds_addr<Cfg, LOGC>((f1 << Cfg::SH1) | (f2 << Cfg::SH2) | (u32)d, c)];
+            BFS_NTT_SITE(a.pass_index, 3, x, Q);
             dif<Q>(x);
             final_store<Cfg, LOGC, MODE, B3, NT>(a, g, x, f1 + (f2 << B1), B1 + B2, c, srow);
         }

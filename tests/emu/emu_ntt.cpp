@@ -48,8 +48,32 @@ extern "C" unsigned long long emu_canonical_violations(int reset) {
     return c;
 }
 
+// Sites of the tile kernels (ntt_core.hpp: BFS_NTT_SITE; tests/ntt_planted.py).  mode 0: off, 1: PLANT -- every thread that reaches the
+// butterflies of (pass, stage) has its registers overwritten from buf, in call order --, 2: RECORD -- they are copied to buf.  `words`
+// is the room in buf; the counts restart.  emu_site_words: the words planted / recorded since then; *overrun: the words the site asked
+// for beyond the room (none of them was read or written).
+extern "C" void emu_site_control(int mode, u32 pass, u32 stage, u64* buf, u64 words) {
+    NttSiteControl& c = ntt_site_control();
+    c.mode = mode; c.pass = pass; c.stage = stage; c.buf = buf; c.capacity = words; c.words = 0; c.overrun = 0;
+}
+extern "C" unsigned long long emu_site_words(unsigned long long* overrun) {
+    const NttSiteControl& c = ntt_site_control();
+    if (overrun) *overrun = c.overrun;
+    return c.words;
+}
+// the event counters of gl.hpp: out[slot * events + event], slot 0 = before the first site of a call, slot 1 + 3 * pass + (stage - 1);
+// returns the number of events per slot, *slots the number of slots (out may be null to ask for the shape)
+extern "C" int emu_site_events(int reset, unsigned long long* out, int* slots) {
+    GlSiteEvents& e = gl_site_events();
+    if (slots) *slots = GL_SITE_SLOTS;
+    if (out) memcpy(out, e.count, sizeof(e.count));
+    if (reset) { memset(e.count, 0, sizeof(e.count)); e.slot = 0; }
+    return GL_EV_COUNT;
+}
+
 extern "C" int emu_gl_ntt(const u64* in, u64 n_in, u64 in_stride, u64* out, u64 out_stride, u32 log_n, u32 batch,
                           u64 root, u64 shift, u64 post_scale) {
+    gl_site_events().slot = 0;      // what runs before the first site (the tables) belongs to no site
     int rc = ntt_check_root(root, log_n);
     if (rc) return rc;
     const u64 n = 1ull << log_n;

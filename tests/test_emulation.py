@@ -78,8 +78,10 @@ def test_tile_kernels_match_oracle(emu, oracle, logn):
 
 @pytest.mark.parametrize("logn", list(range(1, 15)) + [16, 17, 18])
 def test_values_next_to_zero_and_p_stay_canonical(emu, oracle, logn):
-    """every plan shape on operands that make unreduced sums actually exceed p: the oracle's transform, bit for bit, and no
-    non-canonical operand anywhere a canonical one is required (emu_ntt asserts the emulation's violation count)"""
+    """every plan shape on inputs next to 0 and p: the oracle's transform, bit for bit, and no non-canonical operand anywhere a
+    canonical one is required (emu_ntt asserts the emulation's violation count).  Such inputs make unreduced sums actually exceed p
+    in the FIRST butterfly block of the first pass only -- after the first inner twiddle the operands are uniform again;
+    tests/test_ntt_planted_host.py plants operands of this kind at every later stage and pass and counts what they reach there."""
     n = 1 << logn
     w = oracle.primitive_nth_root(n)
     for seed in range(3 if logn <= 14 else 1):

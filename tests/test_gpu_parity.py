@@ -96,9 +96,11 @@ def edge_values(n, seed):
 
 @pytest.mark.parametrize("logn", list(range(1, 25)))
 def test_ntt_on_values_next_to_zero_and_p(sb, oracle, logn):
-    """every plan shape on operands that drive the unreduced sums of the butterfly blocks over p: forward, inverse, coset and plain
-    zero-padded transforms equal the oracle's bit for bit -- in particular every output is a canonical residue.  (Round 4: a first
-    version of the lazy sums passed every random-data test and put a value >= p into a proof's codeword.)"""
+    """every plan shape on inputs next to 0 and p: forward, inverse, coset and plain zero-padded transforms equal the oracle's bit
+    for bit -- in particular every output is a canonical residue.  Such inputs drive the unreduced sums over p in the FIRST butterfly
+    block of the first pass only: after the first inner twiddle the operands are uniform again.  The later stages and passes meet
+    operands of this kind in tests/test_gpu_ntt_planted.py, whose inputs are computed to put them there.  (Round 4: a first version
+    of the lazy sums passed every random-data test and put a value >= p into a proof's codeword.)"""
     n = 1 << logn
     w = oracle.primitive_nth_root(n)
     for seed in range(3 if logn <= 16 else 1):

@@ -203,6 +203,12 @@ _SEGMENTS_SIGNATURES = {
     "bfsg_decimate_rows": (ci, [vp, u64, u32, vp, u64, u64, u32, vp]),
 }
 
+# include/bfstark_blind.h: the blinding kernels of prove_deep(zero_knowledge=True) (prefix bfsz_; the header says why); bound together with the six tables above
+_BLIND_SIGNATURES = {
+    "bfsz_poly_blind": (ci, [vp, u64, u64, u32, vp, u64, u64, vp]),
+    "bfsz_split_blind": (ci, [vp, u64, u64, u64, u32, vp, u64, u64, vp, u64, vp]),
+}
+
 
 class GatherRequest(ctypes.Structure):
     """bfs_gather_request (include/bfstark.h)"""
@@ -307,6 +313,11 @@ def segments_exported_symbols():
     return sorted(_SEGMENTS_SIGNATURES)
 
 
+def blind_exported_symbols():
+    """names include/bfstark_blind.h declares"""
+    return sorted(_BLIND_SIGNATURES)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -324,7 +335,7 @@ def load():
         pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_OPEN_SIGNATURES.items()) + list(_ROUNDS_SIGNATURES.items())
-                              + list(_COMPOSE_SIGNATURES.items()) + list(_SEGMENTS_SIGNATURES.items())):
+                              + list(_COMPOSE_SIGNATURES.items()) + list(_SEGMENTS_SIGNATURES.items()) + list(_BLIND_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

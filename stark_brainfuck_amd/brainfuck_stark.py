@@ -897,14 +897,23 @@ class BrainfuckStark:
         p.proof = p.proof_stream.serialize()
 
     # ---- proving by out-of-domain openings: the second protocol, deep_stark.py; these methods hand over to it
-    def deep_shape(self, segmented=False):
+    def deep_shape(self, segmented=False, zero_knowledge=False):
         """The domains of prove_deep / verify_deep as the namespace L, S, s, n, w, fri, domain, working_domain that deep_segmented_shape()
         describes; segmented=True is that shape.  The unsegmented mode is its case of ONE segment, and both run the same code on their
         shape: the constructor makes max_degree + 1 a power of two and self.fri's domain expansion_factor times as long, so
         L = S = max_degree + 1, s = 1, n = w = self.fri.domain.length with fri = self.fri and domain = working_domain = self.fri.domain
         (these objects: no Fri is made, nothing is refused) say what that mode does -- no decimation (w = n), H on every
-        expansion_factor-th point (w / S), its S coefficients the one segment, and the verifier's Horner loop in z^L over one value H(z)."""
-        return deep_stark.make_shape(self, segmented)
+        expansion_factor-th point (w / S), its S coefficients the one segment, and the verifier's Horner loop in z^L over one value H(z).
+
+        The namespace also carries k, m, L0, randomizer, hiding -- 0, 0, L, False, False unless zero_knowledge ("Zero-knowledge
+        openings").  With t the number of colinearity checks, zero_knowledge=True makes them
+          k = 2 t + 6   blinding coefficients per trace column: f + (X^h - 1) r has h + k coefficients;
+          S  the power of two above the largest transition quotient degree bound for such interpolants (the constructor's analysis);
+          L  (segmented) the power of two >= the largest h + k; (unsegmented) S;
+          m = t + 1, L0 = L - m, s = ceil(S / L0) blinded segments of at most L coefficients (segmented); m = 0, L0 = L, s = 1 otherwise;
+          randomizer = hiding = True: C2 carries a uniform masking polynomial of L coefficients, the three row trees are salted.
+        s + 1 > 16 or m > L0 is refused with the ValueError of deep_segmented_shape."""
+        return deep_stark.make_shape(self, segmented, zero_knowledge)
 
     def deep_segmented_shape(self):
         """The domains of the segmented mode of prove_deep / verify_deep ("Segmented composition"), from public data alone.
@@ -923,7 +932,7 @@ class BrainfuckStark:
         return self.deep_shape(True)
 
     def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None,
-                   segmented=False):
+                   segmented=False, zero_knowledge=False):
         """A proof of the same claim as prove()'s in the form current STARKs use (DEEP-ALI): C0 commits to the 16 base columns, C1 -- after
         the 11 challenges -- to the 9 extension columns, C2 -- after the terminals and one weight per quotient -- to the composition
         polynomial H = sum beta_q quotient_q, computed on every expansion_factor-th point of the domain (bfsc_air_compose) and
@@ -938,10 +947,20 @@ class BrainfuckStark:
         H_i of H(x) = sum_i x^(i L) H_i(x), all opened at z.  The random draws and the order of the stream are the unsegmented mode's;
         the bytes are not, and each verifier refuses the other mode's proofs.
 
-        NOT zero-knowledge: the commitments are not hiding (pcs.py: unsalted row trees, plain values in the proof) and no randomizer
-        polynomial is mixed in; the one trace randomizer per column only keeps the interpolants' shape of prove().  In both modes."""
+        zero_knowledge=False is NOT zero-knowledge, segmented or not: the commitments are not hiding (pcs.py: unsalted row trees, plain
+        values in the proof) and no randomizer polynomial is mixed in; the one trace randomizer per column only keeps the interpolants'
+        shape of prove().
+
+        zero_knowledge=True ("Zero-knowledge openings"; deep_shape gives the numbers) hides the trace in either mode: every
+        column of a table with rows is blinded by (X^h - 1) r with k = 2 t + 6 uniform coefficients (bfsz_poly_blind) -- as many as the
+        base-field functionals one proof reveals of it: t opened rows, their t next rows through H, two openings in F_p^3 --, the segments
+        of H are blinded so that they still sum to H (bfsz_split_blind, m = t + 1 coefficients each), C2 also commits to a uniform
+        polynomial R of L coefficients that is opened at z and masks the DEEP quotient with everything FRI shows of it, and the three row
+        trees are salted (pcs.PolynomialCommitment(hiding=True)).  Not hidden: the terminals (pushed in the clear, as prove() does) and
+        the heights; the blinding draws carry the bias of the reference's 9-bytes-mod-p sampling.  The bytes differ from the other modes',
+        and each of the four verifiers refuses the other three kinds of proof."""
         return deep_stark.prove(self, program, (processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix), proof_stream,
-                                self.deep_shape(segmented))
+                                self.deep_shape(segmented, zero_knowledge))
 
     def deep_weight_count(self):
         """one weight per quotient: the tables' (boundary, transition, terminal within a table), then the permutation arguments'"""
@@ -953,7 +972,7 @@ class BrainfuckStark:
         first call writes, the others add.  weights: (deep_weight_count(), 3) uint64; weights of a table without rows are skipped."""
         deep_stark.compose_into(self, out, log_step, weights, challenges, terminals, domain)
 
-    def verify_deep(self, proof, segmented=False):
+    def verify_deep(self, proof, segmented=False, zero_knowledge=False):
         """the verifier of prove_deep -- host code only (Python ints, hashlib, Fri.verify): the terminals against the public input, output
         and program; the opening of the 26 columns at the plan's points for the values the prover claims (read_rounds); every value of a
         table without rows zero; and
@@ -962,8 +981,12 @@ class BrainfuckStark:
         False with one printed line for every refusal, a malformed stream included; raises nothing.
         segmented=True verifies prove_deep(segmented=True)'s proofs: the opening is read over the Fri of deep_segmented_shape(), the last
         group holds the s segments, and the right-hand side is H(z) = sum_i z^(i L) H_i(z).  A proof of the other mode has another
-        shape (widths, domain length) and is refused by the opening's reader like any stream that is not this mode's."""
-        return deep_stark.verify(self, proof, self.deep_shape(segmented))          # (what deep_shape raises is about this object, not about the proof)
+        shape (widths, domain length) and is refused by the opening's reader like any stream that is not this mode's.
+        zero_knowledge=True verifies prove_deep(zero_knowledge=True)'s proofs of the same `segmented`: the roots and paths are salted
+        ((salt, path) behind each opened row, checked with SaltedMerkle.verify), the last group holds the s blinded segments and the
+        masking polynomial's value, which the opening alone uses, and the right-hand side is H(z) = sum_j z^(j L0) H_j'(z).  A proof of
+        another combination differs in width, salt or path shape and is refused."""
+        return deep_stark.verify(self, proof, self.deep_shape(segmented, zero_knowledge))          # (what deep_shape raises is about this object, not about the proof)
 
     # ------------------------------------------------------------------------------------------------------------
     def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):

@@ -3,9 +3,10 @@ pcs.PolynomialCommitment, the quotients composed into ONE polynomial H, everythi
 A second protocol beside prove() / verify(), through Python stages only; the reference has no counterpart.
 
 BrainfuckStark.prove_deep / verify_deep / deep_shape / compose_into are this module's `prove`, `verify`, `make_shape` and `compose_into`.
-Both modes of the protocol ("Segmented composition") are ONE code path over a shape -- L, S, s, n, w, fri, domain,
-working_domain (`make_shape`) --, which the per-proof record carries as `p.shape`: the stages and the verifier read the shape and never ask
-which mode made it.  What the stages share with prove() -- padding, the extension, the terminals' objects, the weights, the stage loop, the
+All four modes of the protocol -- segmented or not ("Segmented composition"), zero-knowledge or not ("Zero-knowledge openings")
+-- are ONE code path over a shape -- L, S, s, n, w, fri, domain, working_domain, k, m, L0, randomizer, hiding (`make_shape`) --, which the
+per-proof record carries as `p.shape`: the stages and the verifier read the shape and never ask which mode made it.  Without
+zero-knowledge k = m = 0, L0 = L and there is neither a masking polynomial nor a salt: no blinding launch, no draw, the same bytes.  What the stages share with prove() -- padding, the extension, the terminals' objects, the weights, the stage loop, the
 random source -- is reached through the `stark` object; this module does not import brainfuck_stark."""
 import ctypes
 import gc
@@ -25,7 +26,7 @@ from .table import lde_tables, prepare_extension
 _u64 = ctypes.c_uint64
 
 
-def deep_opening_plan(tables, z, segments=1):
+def deep_opening_plan(tables, z, segments=1, randomizer=False):
     """The one opening of prove_deep / verify_deep at the drawn point z (a limb triple), from public data alone: the tables' heights,
     widths and subgroup generators.  The columns are those of the three commitments numbered through (PolynomialCommitment.
     global_column): every table's base columns in table order, then every table's extension columns, then H -- or, in the segmented
@@ -33,11 +34,13 @@ def deep_opening_plan(tables, z, segments=1):
       * one group per table with rows: its base columns, then its extension columns, at [z, z * omicron] -- at [z] alone for a table of
         height 1, whose next row is its own row (omicron = 1);
       * one group of the columns of all tables without rows at [z], if there is such a table (their polynomials are zero);
-      * a last group (H, or all its segments) at [z].
+      * a last group (H, or all its segments) at [z] -- with randomizer=True (the zero-knowledge mode) followed by one more column of
+        the third commitment, the masking polynomial R, which the opening reads and the identity does not.
     -> namespace: groups (the plan as `open_rounds` takes it), widths (the commitments' row widths), table_group (per table the index
     of its group, None for a table without rows), empty_group (index or None), h_group"""
-    if not (type(segments) is int and 1 <= segments <= MAX_EXT_COLUMNS):
-        raise ValueError("the composition polynomial has 1 .. %d segments (got %r)" % (MAX_EXT_COLUMNS, segments))
+    randomizer = int(bool(randomizer))
+    if not (type(segments) is int and 1 <= segments <= MAX_EXT_COLUMNS - randomizer):
+        raise ValueError("the composition polynomial has 1 .. %d segments (got %r)" % (MAX_EXT_COLUMNS - randomizer, segments))
     z = tuple(int(v) for v in z)
     num_base = sum(t.base_width for t in tables)
     base_at, ext_at = 0, num_base
@@ -56,32 +59,56 @@ def deep_opening_plan(tables, z, segments=1):
     if empty:
         empty_group = len(groups)
         groups.append((sorted(empty), [z]))
-    groups.append((list(range(ext_at, ext_at + segments)), [z]))
-    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, segments), table_group=table_group, empty_group=empty_group,
-                           h_group=len(groups) - 1)
+    groups.append((list(range(ext_at, ext_at + segments + randomizer)), [z]))
+    return SimpleNamespace(groups=groups, widths=(num_base, ext_at - num_base, segments + randomizer), table_group=table_group,
+                           empty_group=empty_group, h_group=len(groups) - 1)
 
 
-def make_shape(stark, segmented=False):
-    """BrainfuckStark.deep_shape: the namespace L, S, s, n, w, fri, domain, working_domain (deep_segmented_shape's docstring defines them)"""
-    if not segmented:          # one segment on the constructor's Fri: nothing is made, nothing can be refused
+def blinded_degree_bound(stark, k):
+    """max_degree as the constructor computes it -- the largest transition quotient degree bound under all-ones challenges -- for trace
+    interpolants of h + k coefficients (degree h + k - 1 in the place of Table.interpolant_degree()) in every table with rows; kept per k"""
+    known = stark.__dict__.setdefault("_blinded_degree_bounds", {})
+    if k not in known:
+        # (the constructor's own call with another interpolant degree: Table keeps the symbolic expansion under these challenges)
+        ones = [air.X1] * 11
+        known[k] = max([1] + [t.max_transition_degree(ones, t.height + k - 1 if t.height else None) for t in stark.tables])
+    return known[k]
+
+
+def make_shape(stark, segmented=False, zero_knowledge=False):
+    """BrainfuckStark.deep_shape: the namespace L, S, s, n, w, fri, domain, working_domain (deep_segmented_shape's docstring defines them)
+    and k, m, L0, randomizer, hiding (deep_shape's docstring; DESIGN.md, "Zero-knowledge openings"): 0, 0, L, False, False unless
+    zero_knowledge"""
+    if not segmented and not zero_knowledge:          # one segment on the constructor's Fri: nothing is made, nothing can be refused
         S, fri = stark.max_degree + 1, stark.fri
-        return SimpleNamespace(L=S, S=S, s=1, n=fri.domain.length, w=fri.domain.length, fri=fri, domain=fri.domain, working_domain=fri.domain)
-    f, e = stark.field, stark.expansion_factor
-    L = type(stark).roundup_npo2(max([t.transform_coefficients() for t in stark.tables] + [1]))
-    S = max(stark.max_degree + 1, L)
-    s = S // L
-    if s > MAX_EXT_COLUMNS:
-        raise ValueError("the composition polynomial would have %d segments of %d coefficients, more than the %d extension columns of a "
-                         "commitment" % (s, L, MAX_EXT_COLUMNS))
+        return SimpleNamespace(L=S, S=S, s=1, n=fri.domain.length, w=fri.domain.length, fri=fri, domain=fri.domain, working_domain=fri.domain,
+                               k=0, m=0, L0=S, randomizer=False, hiding=False)
+    f, e, t = stark.field, stark.expansion_factor, stark.num_colinearity_checks
+    roundup = type(stark).roundup_npo2
+    k = 2 * t + 6 if zero_knowledge else 0
+    S = roundup(1 + blinded_degree_bound(stark, k)) if zero_knowledge else stark.max_degree + 1
+    randomizer = 1 if zero_knowledge else 0
+    if segmented:
+        L = roundup(max([max(table.transform_coefficients(), table.height + k if table.height else 0) for table in stark.tables] + [1]))
+        S = max(S, L)
+        m = t + 1 if zero_knowledge else 0
+        L0 = L - m
+        s = -(-S // L0) if L0 > 0 else 0
+        if m > L0 or s + randomizer > MAX_EXT_COLUMNS:
+            raise ValueError("the composition polynomial would have %d segments of %d coefficients, more than the %d extension columns of a "
+                             "commitment" % (s, L0, MAX_EXT_COLUMNS - randomizer))
+    else:
+        L, L0, s, m = S, S, 1, 0
     n = e * L
     w = max(n, S)
-    fri = stark._segmented_fri.get(n)
+    fri = stark.fri if not segmented and n == stark.fri.domain.length else stark._segmented_fri.get(n)
     if fri is None:
         fri = stark._segmented_fri[n] = Fri(f.generator(), f.primitive_nth_root(n), n, e, stark.num_colinearity_checks, stark.xfield,
                                             folding_factor=stark.fri.folding_factor, coset_leaves=stark.fri.coset_leaves,
                                             grinding_bits=stark.fri.grinding_bits)
     working = fri.domain if w == n else Fri.Domain(f.generator(), f.primitive_nth_root(w), w)
-    return SimpleNamespace(L=L, S=S, s=s, n=n, w=w, fri=fri, domain=fri.domain, working_domain=working)
+    return SimpleNamespace(L=L, S=S, s=s, n=n, w=w, fri=fri, domain=fri.domain, working_domain=working, k=k, m=m, L0=L0,
+                           randomizer=bool(randomizer), hiding=bool(zero_knowledge))
 
 
 def compose_into(stark, out, log_step, weights, challenges, terminals, domain=None):
@@ -118,8 +145,8 @@ def prove(stark, program, matrices, proof_stream, shape):
     try:
         # domain, n: where the trace is extended to and H is computed from (the working domain); the commitments are pc's, on the shape's fri
         p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
-                            domain=shape.working_domain, n=shape.w, stream=current_stream(), pc=PolynomialCommitment(shape.fri), commitments=[],
-                            shape=shape)
+                            domain=shape.working_domain, n=shape.w, stream=current_stream(), pc=PolynomialCommitment(shape.fri, hiding=shape.hiding),
+                            commitments=[], shape=shape)
         own = lambda stage: lambda p: stage(stark, p)
         return stark._run_stages(p, (("pad", own(_stage_pad)), ("base_lde", own(_stage_base_lde)), ("base_commit", own(_stage_base_commit)),
                                      ("extend", stark._stage_extend), ("ext_lde", own(_stage_ext_lde)), ("ext_commit", own(_stage_ext_commit)),
@@ -134,12 +161,18 @@ def _stage_pad(stark, p):          # padding as prove()'s; no randomizer polynom
     stark._pad_tables(p)
 
 
-def _polys(stark, coefficients, stride, extension):
-    """the interpolants lde_tables left in `coefficients` as views, in table order: a table's own coefficient count each, one zero
-    coefficient for a table without rows"""
+def _lde(stark, p, extension):
+    """lde_tables onto the working domain with the shape's k blinding coefficients per column (none for k = 0) -> codewords,
+    coefficients, stride, the per-table blinding buffers"""
+    return table_mod.lde_tables_blinded(stark.tables, p.domain, extension=extension, blinding=p.shape.k or None)
+
+
+def _polys(stark, coefficients, stride, extension, k=0):
+    """the interpolants lde_tables left in `coefficients` as views, in table order: a table's own coefficient count each -- h + k with k
+    blinding coefficients --, one zero coefficient for a table without rows"""
     polys, at = [], 0
     for t in stark.tables:
-        count = max(t.transform_coefficients(), 1)
+        count = max(t.transform_coefficients(), t.height + k if t.height else 0, 1)
         if extension:
             for c in range(t.full_width - t.base_width):
                 polys.append(XArray(DeviceView(coefficients, (at + 3 * c) * stride, 3 * stride), count, stark.xfield, stride=stride))
@@ -162,8 +195,8 @@ def _commit_codewords(p, codewords, rows):
 
 
 def _stage_base_lde(stark, p):
-    p.base_codewords, p.base_coefficients, p.base_stride = lde_tables(stark.tables, p.domain, keep_coefficients=True)
-    p.base_polys = _polys(stark, p.base_coefficients, p.base_stride, False)
+    p.base_codewords, p.base_coefficients, p.base_stride, p.base_blinding = _lde(stark, p, False)
+    p.base_polys = _polys(stark, p.base_coefficients, p.base_stride, False, p.shape.k)
     p.prepared_extension = prepare_extension(stark.tables)
 
 
@@ -173,8 +206,8 @@ def _stage_base_commit(stark, p):          # C0: the codewords as lde_tables wro
 
 
 def _stage_ext_lde(stark, p):
-    p.ext_codewords, p.ext_coefficients, p.ext_stride = lde_tables(stark.tables, p.domain, extension=True, keep_coefficients=True)
-    p.ext_polys = _polys(stark, p.ext_coefficients, p.ext_stride, True)
+    p.ext_codewords, p.ext_coefficients, p.ext_stride, p.ext_blinding = _lde(stark, p, True)
+    p.ext_polys = _polys(stark, p.ext_coefficients, p.ext_stride, True, p.shape.k)
 
 
 def _stage_ext_commit(stark, p):          # C1
@@ -232,14 +265,29 @@ def _check_degree(stark, p):
 
 
 def _stage_composition_commit(stark, p):
-    """C2: the s segments of H as views of its coefficients -- segment i holds the coefficients [i L, (i + 1) L) of each limb plane"""
+    """C2: the s segments of H -- without segment blinding (m = 0) views of its coefficients, segment i the coefficients [i L, (i + 1) L)
+    of each limb plane; with it the pieces of L0 = L - m coefficients blinded by bfsz_split_blind, H_j' = H_j + X^L0 b_j - b_{j-1} with
+    uniform b_0 .. b_{s-2} of m coefficients (one draw) -- and, where the shape has one, the masking polynomial R of L uniform
+    coefficients (the next draw) as the commitment's last column"""
     from . import debug_checks
-    L, S, h = p.shape.L, p.shape.S, p.h_coefficients
-    p.segments = [XArray(DeviceView(h.buf, i * L, 2 * S + L), L, stark.xfield, stride=S) for i in range(p.shape.s)]
-    if debug_checks.enabled():
-        assert len(p.segments) * L == len(h) and all(len(f) == L and f.stride == S for f in p.segments), \
-            "the segments do not tile the composition polynomial's coefficients"
-    p.commitments.append(p.pc.commit(p.segments, p.proof_stream))
+    shape, h = p.shape, p.h_coefficients
+    L, S, s, m = shape.L, shape.S, shape.s, shape.m
+    p.segment_blinding = p.blinded_segments = p.masking_polynomial = None
+    if m:
+        p.segment_blinding = table_mod.draw_field_words(p.draw, 3 * (s - 1) * m, p.stream)
+        p.blinded_segments = DeviceBuffer(3 * s * L)
+        _lib.check(_lib.load().bfsz_split_blind(h.ptr, h.stride, S, shape.L0, s, p.segment_blinding.ptr, m, m, p.blinded_segments.ptr, L, p.stream))
+        p.segments = [XArray(DeviceView(p.blinded_segments, 3 * i * L, 3 * L), L, stark.xfield, stride=L) for i in range(s)]
+    else:
+        p.segments = [XArray(DeviceView(h.buf, i * L, 2 * S + L), L, stark.xfield, stride=S) for i in range(s)]
+        if debug_checks.enabled():
+            assert len(p.segments) * L == len(h) and all(len(f) == L and f.stride == S for f in p.segments), \
+                "the segments do not tile the composition polynomial's coefficients"
+    committed = list(p.segments)
+    if shape.randomizer:
+        p.masking_polynomial = XArray(table_mod.draw_field_words(p.draw, 3 * L, p.stream), L, stark.xfield, stride=L)
+        committed.append(p.masking_polynomial)
+    p.commitments.append(p.pc.commit(committed, p.proof_stream))
 
 
 def _stage_opening(stark, p):
@@ -247,7 +295,7 @@ def _stage_opening(stark, p):
     p.z = tuple(stark.xfield.sample(p.proof_stream.prover_fiat_shamir()).limbs())
     if p.z[1] == 0 and p.z[2] == 0:
         raise ValueError("the drawn point lies in the base field (chance 2^-128): prove again")
-    p.plan = deep_opening_plan(stark.tables, p.z, segments=p.shape.s)
+    p.plan = deep_opening_plan(stark.tables, p.z, segments=p.shape.s, randomizer=p.shape.randomizer)
     p.opened = p.pc.open_rounds(p.commitments, p.plan.groups, p.proof_stream)
     stark._last = {"challenges": p.challenges, "terminals": p.terminals}
     if stark.keep_intermediates:          # the working codewords (w words each) and the committed ones (n words each; the same buffers where w = n)
@@ -256,7 +304,10 @@ def _stage_opening(stark, p):
                             "opened": [[[tuple(v.limbs()) for v in per_point] for per_point in per_group] for per_group in p.opened],
                             "segments": p.segments, "L": p.shape.L, "S": p.shape.S, "s": p.shape.s, "working_base_codewords": p.base_codewords,
                             "working_ext_codewords": p.ext_codewords, "committed_base_codewords": p.base_committed,
-                            "committed_ext_codewords": p.ext_committed})
+                            "committed_ext_codewords": p.ext_committed,
+                            # the zero-knowledge mode's draws (empty / None without): per table with rows its blinding words, w rows of k
+                            "k": p.shape.k, "m": p.shape.m, "L0": p.shape.L0, "base_blinding": p.base_blinding, "ext_blinding": p.ext_blinding,
+                            "b": p.segment_blinding, "R": p.masking_polynomial, "blinded_segments": p.blinded_segments})
     else:
         type(stark)._release(*stark.tables)
 
@@ -294,8 +345,8 @@ def _verify_stream(stark, proof_stream, shape):
     if z[1] == 0 and z[2] == 0:
         print("the drawn point lies in the base field")
         return False
-    plan = deep_opening_plan(stark.tables, z, segments=shape.s)
-    values = PolynomialCommitment(shape.fri).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
+    plan = deep_opening_plan(stark.tables, z, segments=shape.s, randomizer=shape.randomizer)
+    values = PolynomialCommitment(shape.fri, hiding=shape.hiding).read_rounds([root0, root1, root2], plan.widths, plan.groups, proof_stream)
     if values is None:
         return False
     if plan.empty_group is not None and any(any(v) for v in values[plan.empty_group][0]):
@@ -321,8 +372,8 @@ def _verify_stream(stark, proof_stream, shape):
                 at += 1
     for j, pa in enumerate(stark.permutation_arguments):
         total = xadd(total, xmul(xmul(weights[at + j], pa.evaluate_difference(rows)), boundary))
-    h_at_z, z_to_L = X0, xpow(z, shape.L)
-    for segment in reversed(values[plan.h_group][0]):          # Horner in z^L over the segments' values
+    h_at_z, z_to_L = X0, xpow(z, shape.L0)
+    for segment in reversed(values[plan.h_group][0][:shape.s]):          # Horner in z^L0 over the segments' values (a masking polynomial's value behind them is the opening's alone)
         h_at_z = xadd(xmul(h_at_z, z_to_L), tuple(segment))
     if total != h_at_z:
         print("the composition polynomial does not match the opened rows")

@@ -1,8 +1,8 @@
 """A polynomial commitment from FRI: commit to polynomials, then prove what they evaluate to at points OUTSIDE the FRI domain.
 
     evaluate_at(coeffs, points)                       values of coefficient arrays in HBM at points of the extension field
-    PolynomialCommitment(fri)
-      .commit(polys, proof_stream) -> Commitment      codewords + one unsalted row tree in HBM; pushes the root
+    PolynomialCommitment(fri, hiding=False)
+      .commit(polys, proof_stream) -> Commitment      codewords + one row tree in HBM (unsalted; salted with hiding=True); pushes the root
       .open(commitment, points, proof_stream)         pushes the opening proof; returns the values
       .verify(root, points, values, proof_stream)     host only (ints, hashlib, Fri.verify)
 
@@ -73,6 +73,7 @@ from .device import DeviceBuffer, current_stream, gather
 from .extension_field import ExtensionFieldElement
 from .merkle import CosetMerkle, Merkle, leaf_pickle_source
 from .ntt import _base_value
+from .salted_merkle import SaltedMerkle, ZippedSaltedMerkle
 
 _u64 = ctypes.c_uint64
 MAX_POINTS_PER_LAUNCH = 4          # bfs_poly_eval_points, bfs_deep_quotient
@@ -312,15 +313,24 @@ class PolynomialCommitment:
     (a polynomial with more is not what the low-degree test vouches for).  An accepted opening says: the columns behind `root` are
     within the FRI proximity bound of polynomials of degree < d that take the claimed values.
 
+    hiding=True: `commit` / `commit_evaluated` build the SALTED row tree of prove() (ZippedSaltedMerkle: leaf i = blake2b(pickle(row
+    tuple) || pickle(salt_i)), 24-byte salts that stay in HBM), every opening pushes `(salt, path)` behind each opened row as
+    SaltedMerkle.open returns it, and the verifier checks it with SaltedMerkle.verify (a salt that is not 24 bytes: "opened row is not
+    well formed").  The commitment then hides the unopened rows; what the opened rows, the values and g reveal is for the caller to
+    blind -- BrainfuckStark.prove_deep(zero_knowledge=True) does ("Zero-knowledge openings": blinded columns and a uniform
+    masking polynomial among the committed ones).  hiding=False (the default) keeps every stream as it was.
+
     What this scheme is NOT:
-      * it is not hiding -- the row tree is unsalted and no randomizer polynomial is mixed into g: the opened rows are plain values of
-        the committed polynomials, and the values themselves are in the proof;
+      * by default it is not hiding -- the row tree is unsalted --, and with or without `hiding` it is not zero-knowledge by itself: no
+        randomizer polynomial is mixed into g unless the caller commits to one, the opened rows are plain values of the committed
+        polynomials, and the values themselves are in the proof;
       * it does not choose the points -- the caller must draw them AFTER the commitment's root is in the transcript (from
         proof_stream.prover_fiat_shamir()); for points fixed beforehand a prover can commit to polynomials made to fit.
     Points of the FRI domain cannot be opened (the quotient's denominator vanishes there): `open` refuses them."""
 
-    def __init__(self, fri):
+    def __init__(self, fri, hiding=False):
         self.fri = fri
+        self.hiding = bool(hiding)
         self.xfield = fri.field
         self.n = fri.domain.length
         self.max_coefficients = self.n // fri.expansion_factor
@@ -367,7 +377,13 @@ class PolynomialCommitment:
         return self._commit_rows(committed, cols, proof_stream)
 
     def _commit_rows(self, committed, cols, proof_stream):
-        """the row tree over a commitment's codewords (bfs_merkle_build_rows without salts); pushes the root"""
+        """the row tree over a commitment's codewords (bfs_merkle_build_rows without salts); pushes the root.  hiding: the salted row
+        tree of prove() instead (ZippedSaltedMerkle: 24 bytes of salt per leaf, made on the device from one 32-byte draw and kept there,
+        or taken from a replaced random source)"""
+        if self.hiding:
+            committed.tree = ZippedSaltedMerkle([(c.d_values, c.is_ext, c.field_id) for c in cols], self.n, lambda i: None)
+            proof_stream.push(committed.tree.root())
+            return committed
         nodes = DeviceBuffer(2 * self.n * 8)
         _lib.check(_lib.load().bfs_merkle_build_rows(cols, len(committed.polys), self.n, None, 0, nodes.ptr, current_stream()))
         committed.tree = Merkle(_RowCount(self.n), _device_nodes=nodes)
@@ -492,6 +508,12 @@ class PolynomialCommitment:
                 reqs = committed.row_requests(i)
                 spans["row", r, i] = (len(requests), len(reqs))
                 requests += reqs
+        salted = []
+        if self.hiding:          # salts made on the device come with the same round trip; tree.open then knows them
+            for committed in commitments:
+                reqs, store = committed.tree.salt_requests(rows)
+                salted.append((store, len(requests), len(reqs)))
+                requests += reqs
         for c in leaves:
             spans["leaf", c] = (len(requests), a)
             requests += [(g.ptr + 8 * (c + j * q), 3, g.stride) for j in range(a)]
@@ -501,6 +523,8 @@ class PolynomialCommitment:
         def words(key):
             first, count = spans[key]
             return fetched[starts[first]:starts[first + count]]
+        for store, first, count in salted:
+            store([fetched[starts[first + j]:starts[first + j + 1]] for j in range(count)])
         known = {}
         for i in indices:
             for r, committed in enumerate(commitments):
@@ -578,7 +602,15 @@ class PolynomialCommitment:
                     return False
                 shapes[r] = kinds
                 path = proof_stream.pull()
-                if not self._is_path(path, n) or not Merkle.verify(root, i, path, row):
+                if self.hiding:          # (salt, path) as SaltedMerkle.open returns it
+                    if (not isinstance(path, tuple) or len(path) != 2 or not isinstance(path[0], (bytes, bytearray)) or len(path[0]) != 24
+                            or not self._is_path(path[1], n)):
+                        print("opened row is not well formed")
+                        return False
+                    authentic = SaltedMerkle.verify(root, i, path[0], path[1], row)
+                else:
+                    authentic = self._is_path(path, n) and Merkle.verify(root, i, path, row)
+                if not authentic:
                     print("merkle authentication path verification fails for an opened row")
                     return False
                 rows += [_limbs(e) for e in row]

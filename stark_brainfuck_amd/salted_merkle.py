@@ -128,6 +128,20 @@ class ZippedSaltedMerkle(SaltedMerkle):
                 return salts[24 * i:24 * i + 24]
         self._leafs = _LazyLeafs(n, make_row, salt_of)
 
+    def salt_requests(self, indices):
+        """`prefetch_salts` for a caller that gathers by itself (device.gather): -> (requests, store) -- one (address, 3 words, stride 1)
+        request per row of `indices` whose device-made salt is not known yet, and store(list of the fetched word arrays, in that order),
+        which keeps them for `open`.  No requests for salts that live on the host"""
+        cache = getattr(self, "_salt_cache", None)
+        if cache is None:
+            return [], lambda fetched: None
+        wanted = [i for i in dict.fromkeys(indices) if i not in cache]
+
+        def store(fetched):
+            for i, words in zip(wanted, fetched):
+                cache[i] = words.tobytes()
+        return [(self._salt_base + 24 * i, 3, 1) for i in wanted], store
+
     def prefetch_salts(self, indices, batch):
         """queue the salts of rows `indices` on a GatherBatch (device-made salts only); returns the function that stores them"""
         cache = getattr(self, "_salt_cache", None)

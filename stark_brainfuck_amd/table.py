@@ -230,7 +230,28 @@ def _draw_randomizers(table, extension):
     return [sample_base(random_source(urandom)(3 * 8)) for _ in range(table.base_width)]
 
 
-def lde_tables(tables, domain, extension=False, keep_coefficients=False):
+def sample_words(data, count):
+    """`count` base-field values from 9 * count bytes: BaseField.sample of consecutive 9-byte strings (what bfs_xfe_sample_fill does
+    per limb on the device), as a uint64 array"""
+    assert len(data) == 9 * count
+    return sample_ext_many(bytes(data) + bytes(-count % 3 * 9), (count + 2) // 3, 9).T.reshape(-1)[:count].copy()
+
+
+def draw_field_words(draw, count, stream=None):
+    """`count` uniform base-field values in HBM (a DeviceBuffer of at least `count` words, values in the first `count`), one draw of
+    `draw`: in production 32 bytes of it, expanded on the device (bfs_xfe_sample_fill: every limb of the extension elements it writes is
+    one sample, so three planes of ceil(count / 3) words are `count` values back to back); under a replaced source 9 bytes per value from
+    its stream, by the same rule (sample_words), value i from bytes [9 i, 9 i + 9)"""
+    stream = current_stream() if stream is None else stream
+    if draw is os.urandom or getattr(draw, "expand_on_device", False):
+        elements = (count + 2) // 3
+        out = DeviceBuffer(3 * elements)
+        _lib.check(_lib.load().bfs_xfe_sample_fill(draw(32), out.ptr, elements, elements, stream))
+        return out
+    return DeviceBuffer.from_numpy(sample_words(draw(9 * count), count))
+
+
+def lde_tables(tables, domain, extension=False, keep_coefficients=False, blinding=None):
     """The low-degree extension of the base columns (extension=False) or the extension columns (True) of several tables -- Table.lde /
     Table.ldex are the calls with one table -- with ONE transform onto the FRI domain: every table interpolates its own columns (its
     own subgroup) into its rows of a shared coefficient buffer, and the coset evaluation -- the same N-point transform for all of them
@@ -240,7 +261,20 @@ def lde_tables(tables, domain, extension=False, keep_coefficients=False):
     keep_coefficients: returns (codewords, coefficients, stride) -- the buffer of all codewords (per column, or per limb plane of an
     extension column, N words, in table order), the buffer of the interpolants' coefficients in the same order, `stride` words per row
     (a table's rows hold transform_coefficients() coefficients, zeros behind them; None when no table has a row), for a caller that
-    commits to the codewords as they lie (PolynomialCommitment.commit_evaluated).  Otherwise the coefficients go back to the pool."""
+    commits to the codewords as they lie (PolynomialCommitment.commit_evaluated).  Otherwise the coefficients go back to the pool.
+    blinding = k (prove_deep's zero-knowledge mode; DESIGN.md, "Zero-knowledge openings"): every column of a table with h > 0 rows becomes
+    f + (X^h - 1) r with k uniform coefficients r (bfsz_poly_blind, after the table's bfs_poly_randomize; the table's k words per row are
+    one draw behind its randomizers', draw_field_words) -- the same values on the trace, h + k coefficients; the rows of the coefficient
+    buffer are hmax + k words long.  None: no blinding, and everything above as it was.  (lde_tables_blinded also hands back the
+    blinding buffers.)"""
+    out, coeffs, stride, _ = lde_tables_blinded(tables, domain, extension, blinding)
+    if keep_coefficients:
+        return out, coeffs, stride
+
+
+def lde_tables_blinded(tables, domain, extension=False, blinding=None):
+    """lde_tables(..., keep_coefficients=True, blinding=blinding) -> (codewords, coefficients, stride, blinds): blinds holds, per table
+    with rows and columns, the buffer of its blinding words (width rows of `blinding` words) in table order; empty without blinding"""
     lib, stream = _lib.load(), current_stream()
     n = domain.length
     log_n = n.bit_length() - 1
@@ -249,6 +283,10 @@ def lde_tables(tables, domain, extension=False, keep_coefficients=False):
     randomized = any(t.height and t.num_randomizers for t in tables)
     stride = hmax + 1
     n_in = hmax + 1 if randomized else hmax
+    blinds = []
+    if blinding is not None:          # (bfsz_poly_blind: f + (X^h - 1) r, r of `blinding` coefficients, on every column of a table with rows)
+        assert type(blinding) is int and blinding >= 1, "blinding: the number of blinding coefficients per column"
+        stride = n_in = hmax + blinding
     assert n_in <= n, "interpolant does not fit the FRI domain"
     omega, offset = domain.omega.value, domain.offset.value
     out = DeviceBuffer(total * n)
@@ -267,6 +305,9 @@ def lde_tables(tables, domain, extension=False, keep_coefficients=False):
             raw_ntt(d_in.ptr, h, h, mine, stride, h.bit_length() - 1, w, _inv(t.omicron.value), 1, _inv(h), stream)
             if rand is not None:
                 _lib.check(lib.bfs_poly_randomize(mine, stride, h, w, omega, (_u64 * w)(*[int(v) for v in rand]), stream))
+            if blinding is not None:          # this table's draw follows its randomizers': w rows of `blinding` words
+                blinds.append(draw_field_words(random_source(urandom), w * blinding, stream))
+                _lib.check(lib.bfsz_poly_blind(mine, stride, h, w, blinds[-1].ptr, blinding, blinding, stream))
         inputs.append(d_in)
         at += w
     masks = None
@@ -285,7 +326,8 @@ def lde_tables(tables, domain, extension=False, keep_coefficients=False):
         # native path) -- a transform's cost depends on its zero padding (ntt_plan.hpp: 2^16 + 1 coefficients on 2^22 points take the
         # two-pass expansion plan, 2^17 + 1 the plain three passes), and a table must not pay for its neighbour's height
         first = 0
-        for count, run in itertools.groupby(range(len(tables)), key=lambda k: tables[k].transform_coefficients()):
+        counts = [t.transform_coefficients() if blinding is None or not t.height else t.height + blinding for t in tables]
+        for count, run in itertools.groupby(range(len(tables)), key=lambda k: counts[k]):
             cols = sum(widths[k] for k in run)
             if cols:
                 raw_ntt(coeffs.ptr + 8 * first * stride, min(max(count, 1), n_in), stride, out.ptr + 8 * first * n, n, log_n, cols, omega, offset, 1, stream)
@@ -301,8 +343,7 @@ def lde_tables(tables, domain, extension=False, keep_coefficients=False):
             t.base_codewords = view
             t._base_device = d_in          # the trace columns stay in HBM for extend_device()
         at += w
-    if keep_coefficients:
-        return out, coeffs, stride
+    return out, coeffs, stride, blinds
 
 
 def zerofier_inverses(tables, domain, rows=None):
@@ -707,7 +748,7 @@ class Table:
         memo = {}            # sub-expressions (deselectors, instruction zerofier, row differences) are shared between constraints
         return [air.total_degrees(air.expand(e, nvars, challenges, terminals, params, memo)) for e in dict(self.air.all())[kind]]
 
-    def _degree_bounds(self, kind, challenges, terminals, exact=False):
+    def _degree_bounds(self, kind, challenges, terminals, exact=False, interpolant_degree=None):
         """exact: never take the generic shortcut (the verifier's terminals come from the prover, who chooses them AFTER it has seen the
         challenges and could make one cancel a leading monomial while still looking sampled -- round-5 advice).
         symbolic degree bounds of the constraints composed with the interpolants (multivariate.py:144-170).  Which
@@ -715,7 +756,8 @@ class Table:
         distinct, zero or with more than 32 significant bits) the surviving set is the generic one except with probability
         ~2^-160, so it is computed once per zero pattern and reused.  Crafted values (the constructor's all-ones challenges,
         brainfuck_stark.py:84-92, or small test values) always take the exact expansion."""
-        md = self.interpolant_degree()
+        # interpolant_degree: the bound for interpolants of another degree than this table's own (deep_stark.blinded_degree_bound)
+        md = self.interpolant_degree() if interpolant_degree is None else interpolant_degree
         params = self.air_params(challenges)
         # (a proof asks fifteen times with the same challenges list: its part of the analysis is kept while that list is the argument)
         # -- only for a tuple of tuples, which cannot change between the calls
@@ -770,9 +812,9 @@ class Table:
     def num_quotients(self, challenges=None, terminals=None):
         return sum(len(c) for _, c in self.air.all())
 
-    def max_transition_degree(self, challenges):
+    def max_transition_degree(self, challenges, interpolant_degree=None):
         """symbolic degree of the composed transition constraints minus the zerofier (brainfuck_stark.py:84-92)"""
-        return max([b - (self.height - 1) for b in self._degree_bounds("transition", challenges, [air.X0] * 5)] or [1])
+        return max([b - (self.height - 1) for b in self._degree_bounds("transition", challenges, [air.X0] * 5, interpolant_degree=interpolant_degree)] or [1])
 
     # ---- the constraints as the reference presents them: lists of MPolynomial (table.py:145-146, 173-174, 248-249)
     def _constraints_ext(self, kind, challenges, terminals=None):

@@ -5,6 +5,13 @@
     python tools/deep_stark_time.py --write-golden DIR
     python tools/deep_stark_time.py --segmented [--program ...] [--reps 5] [--kernel-reps 20] [--json FILE]
     python tools/deep_stark_time.py --write-golden-segmented DIR
+    python tools/deep_stark_time.py --zero-knowledge [--program ...] [--reps 5] [--json FILE]
+    python tools/deep_stark_time.py --write-golden-zk DIR
+
+--zero-knowledge: prove_deep in its four modes (segmented or not, zero_knowledge or not) alternating in one process by stage, per stage
+the cost of zero-knowledge over its twin, proof bytes of all four for the program and the four fixture programs
+(profiles/deep_stark_zk.md).  --write-golden-zk DIR writes the zero-knowledge proofs of FIXTURES, unsegmented and segmented, on the seeds
+b"deep-zk-" + name, and DIR/deep_zk.json.
 
 --segmented: prove_deep and prove_deep(segmented=True) alternating in one process by stage, proof bytes of both modes for the program and
 the four fixture programs, and bfsg_decimate_rows on 2^20 -> 2^19 words over 16 and 27 rows beside a second transform of the kept
@@ -86,16 +93,87 @@ def seed_tag(name):
     return b"deep-" + name.encode()
 
 
-def prove_deep_seeded(name, m=None, prepare=None, matrices=None, segmented=False):
-    """-> (stark, proof) of program `name` on the seeded randomness; prepare(stark) runs before prove_deep; matrices: other traces"""
+def prove_deep_seeded(name, m=None, prepare=None, matrices=None, segmented=False, zero_knowledge=False):
+    """-> (stark, proof) of program `name` on the seeded randomness (the zero-knowledge mode on a stream of its own, zk_seed_tag);
+    prepare(stark) runs before prove_deep; matrices: other traces"""
     from stark_brainfuck_amd import randomness
     stark = make_stark(name, m)
     if prepare is not None:
         prepare(stark)
     kwargs = {"segmented": True} if segmented else {}
-    with randomness.override(modes.Stream(seed_tag(name))):
+    if zero_knowledge:
+        kwargs["zero_knowledge"] = True
+    with randomness.override(modes.Stream(zk_seed_tag(name) if zero_knowledge else seed_tag(name))):
         proof = stark.prove_deep(claim(name)[0], *(claim(name)[4] if matrices is None else matrices), **kwargs)
     return stark, proof
+
+
+# the zero-knowledge mode (prove_deep(zero_knowledge=True)), unsegmented and segmented: the same claims and FRI modes, seeds, a list and
+# file names of their own
+ZK_FIXTURE_LIST = "deep_zk.json"
+ZK_FIXTURES = [(name, m, segmented) for segmented in (False, True) for name, m in FIXTURES]
+
+
+def zk_seed_tag(name):
+    return b"deep-zk-" + name.encode()
+
+
+def zk_fixture_file(name, m, segmented):
+    return ("deep_zk_segmented_" if segmented else "deep_zk_") + fixture_file(name, m)[len("deep_"):]
+
+
+def zk_refusal(name, m, segmented):
+    """the ValueError's text if deep_shape refuses the zero-knowledge shape of this fixture (host arithmetic alone), else None"""
+    try:
+        make_stark(name, m).deep_shape(segmented, True)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+def zk_tamperings(proof):
+    """name -> bytes: changes to what only a zero-knowledge proof carries -- the salt behind the first opened row, the masking
+    polynomial's value at z (the last value of the last group) -- that verify_deep(zero_knowledge=True) must refuse"""
+    objects = objects_of(proof)
+    salt_at = VALUES_AT + 3          # values, the quotient's root, the first opened row, then its (salt, path)
+    salt, path = objects[salt_at]
+    assert isinstance(salt, bytes) and len(salt) == 24
+
+    def with_salt(changed):
+        return bytes_of(objects[:salt_at] + [(changed, path)] + objects[salt_at + 1:])
+    values = [[list(per_point) for per_point in per_group] for per_group in objects[VALUES_AT]]
+    values[-1][0][-1] = _bumped(values[-1][0][-1])
+    return {"a flipped salt byte": with_salt(bytes([salt[0] ^ 1]) + salt[1:]), "a salt of 23 bytes": with_salt(salt[:23]),
+            "the masking polynomial's value": bytes_of(objects[:VALUES_AT] + [values] + objects[VALUES_AT + 1:])}
+
+
+def write_golden_zk(directory):
+    os.makedirs(directory, exist_ok=True)
+    entries = []
+    for name, m, segmented in ZK_FIXTURES:
+        refusal = zk_refusal(name, m, segmented)
+        if refusal is not None:          # (a trace this short has more blinded segments than a commitment has columns: there is no such proof)
+            entries.append({"file": None, "name": name, "args": m, "segmented": segmented, "refused": refusal})
+            print("no proof of %s %s, segmented: %s" % (name, modes.mode_id(m), refusal), flush=True)
+            continue
+        stark, proof = prove_deep_seeded(name, m, segmented=segmented, zero_knowledge=True)
+        shape = stark.deep_shape(segmented, True)
+        assert make_stark(name, m).verify_deep(proof, segmented=segmented, zero_knowledge=True) is True, "%s %s does not verify" % (name, modes.mode_id(m))
+        assert prove_deep_seeded(name, m, segmented=segmented, zero_knowledge=True)[1] == proof, "two proofs on the same seed differ"
+        source, given = PROGRAMS[name]
+        entry = {"file": zk_fixture_file(name, m, segmented), "name": name, "program": source, "input": given, "output": "".join(claim(name)[3]),
+                 "args": m, "segmented": segmented, "seed": "shake_256(b'bfs-golden-urandom' + %r)" % zk_seed_tag(name),
+                 "fri_domain_length": shape.n, "working_domain_length": shape.w, "segments": shape.s, "segment_length": shape.L,
+                 "composition_coefficients": shape.S, "trace_blinding_coefficients": shape.k, "segment_blinding_coefficients": shape.m,
+                 "proof_len": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest()}
+        with open(os.path.join(directory, entry["file"]), "wb") as f:
+            f.write(proof)
+        entries.append(entry)
+        print("wrote %s  %d bytes  sha256 %s" % (entry["file"], len(proof), entry["proof_sha256"][:16]), flush=True)
+    with open(os.path.join(directory, ZK_FIXTURE_LIST), "w") as f:
+        json.dump({"made_by": "tools/deep_stark_time.py --write-golden-zk", "proofs": entries,
+                   "randomness": "randomness.override(tools.stark_fri_modes.Stream(b'deep-zk-' + name))"}, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def fixtures(directory=GOLDEN, listing=FIXTURE_LIST):
@@ -341,6 +419,56 @@ def time_segmented(name, reps):
     return out
 
 
+ZK_LEGS = {"prove_deep": {}, "prove_deep_segmented": {"segmented": True}, "prove_deep_zk": {"zero_knowledge": True},
+           "prove_deep_segmented_zk": {"segmented": True, "zero_knowledge": True}}
+
+
+def time_zero_knowledge(name, reps):
+    """prove_deep in its four modes by stage, ms, ALTERNATING in one process (a warm-up proof of each first, dropped); proof bytes;
+    verify_deep; per stage the median cost of zero-knowledge over the mode's twin without it"""
+    program, _, _, _, matrices = claim(name)
+    series = {label: {"totals": [], "stages": {}} for label in ZK_LEGS}
+    proofs, shapes = {}, {}
+    for rep in range(reps + 1):
+        for label, kwargs in ZK_LEGS.items():
+            stark = make_stark(name)
+            stark.stage_timing = True
+            t0 = time.perf_counter()
+            proofs[label] = stark.prove_deep(program, *matrices, **kwargs)
+            _sync()
+            if rep:
+                series[label]["totals"].append((time.perf_counter() - t0) * 1e3)
+                for stage, seconds in stark.timing.items():
+                    series[label]["stages"].setdefault(stage, []).append(seconds * 1e3)
+            shape = stark.deep_shape(**kwargs)
+            shapes[label] = {key: getattr(shape, key) for key in ("L", "S", "s", "n", "w", "k", "m", "L0")}
+    out = {}
+    for label, kwargs in ZK_LEGS.items():
+        verify_ms = []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            assert make_stark(name).verify_deep(proofs[label], **kwargs) is True
+            verify_ms.append((time.perf_counter() - t0) * 1e3)
+        out[label] = {"total_ms": _mmm(series[label]["totals"]), "stages_ms": {s: _mmm(v) for s, v in series[label]["stages"].items()},
+                      "proof_bytes": len(proofs[label]), "shape": shapes[label], "verify_ms": _mmm(verify_ms[1:])}
+    for plain in ("prove_deep", "prove_deep_segmented"):
+        a, b = out[plain], out[plain + "_zk"]
+        out[plain + "_zk"]["cost_over_twin_ms"] = dict({s: round(b["stages_ms"][s]["median"] - a["stages_ms"][s]["median"], 4) for s in a["stages_ms"]},
+                                                       total=round(b["total_ms"]["median"] - a["total_ms"]["median"], 4))
+    return out
+
+
+def zero_knowledge_sizes():
+    """proof bytes of prove_deep in its four modes for the four fixture programs"""
+    rows = []
+    for name in PROGRAMS:
+        program, _, _, _, matrices = claim(name)
+        rows.append(dict({label + "_bytes": None if kwargs.get("zero_knowledge") and zk_refusal(name, mode(), kwargs.get("segmented", False))
+                          else len(make_stark(name).prove_deep(program, *matrices, **kwargs)) for label, kwargs in ZK_LEGS.items()}, program=name))
+        print("SIZE " + json.dumps(rows[-1], sort_keys=True), flush=True)
+    return rows
+
+
 def time_decimation(reps, log_in=20, log_out=19, coefficients=(1 << 16) + 1):
     """bfsg_decimate_rows from 2^log_in to 2^log_out words per row over 16 and 27 rows, beside the alternative it was chosen against -- a
     second transform of the kept `coefficients` coefficients per row onto the 2^log_out points -- and a device copy of the same output
@@ -395,6 +523,8 @@ def main():
     ap.add_argument("--segmented", action="store_true", help="both modes of prove_deep alternating, their proof sizes, the decimation kernel")
     ap.add_argument("--write-golden", default=None)
     ap.add_argument("--write-golden-segmented", default=None)
+    ap.add_argument("--zero-knowledge", action="store_true", help="the four modes of prove_deep alternating, their proof sizes")
+    ap.add_argument("--write-golden-zk", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     import torch
@@ -404,8 +534,19 @@ def main():
         return write_golden(args.write_golden)
     if args.write_golden_segmented:
         return write_golden(args.write_golden_segmented, segmented=True)
+    if args.write_golden_zk:
+        return write_golden_zk(args.write_golden_zk)
     result = {}
-    if args.segmented:
+    if args.zero_knowledge:
+        name = args.program
+        if name == "big":
+            PROGRAMS["big"] = (modes.BIG, "")
+        result["program"] = name
+        result["proofs"] = time_zero_knowledge(name, args.reps)
+        print("ZERO_KNOWLEDGE " + json.dumps(result["proofs"], sort_keys=True), flush=True)
+        PROGRAMS.pop("big", None)
+        result["sizes"] = zero_knowledge_sizes()
+    elif args.segmented:
         name = args.program
         if name == "big":
             PROGRAMS["big"] = (modes.BIG, "")

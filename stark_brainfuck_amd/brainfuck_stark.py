@@ -932,7 +932,7 @@ class BrainfuckStark:
         return self.deep_shape(True)
 
     def prove_deep(self, program, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, proof_stream=None,
-                   segmented=False, zero_knowledge=False):
+                   segmented=False, zero_knowledge=False, secret_input=False):
         """A proof of the same claim as prove()'s in the form current STARKs use (DEEP-ALI): C0 commits to the 16 base columns, C1 -- after
         the 11 challenges -- to the 9 extension columns, C2 -- after the terminals and one weight per quotient -- to the composition
         polynomial H = sum beta_q quotient_q, computed on every expansion_factor-th point of the domain (bfsc_air_compose) and
@@ -958,9 +958,16 @@ class BrainfuckStark:
         polynomial R of L coefficients that is opened at z and masks the DEEP quotient with everything FRI shows of it, and the three row
         trees are salted (pcs.PolynomialCommitment(hiding=True)).  Not hidden: the terminals (pushed in the clear, as prove() does) and
         the heights; the blinding draws carry the bias of the reference's 9-bytes-mod-p sampling.  The bytes differ from the other modes',
-        and each of the four verifiers refuses the other three kinds of proof."""
+        and each of the four verifiers refuses the other three kinds of proof.
+
+        secret_input=True ("Secret input"; needs zero_knowledge=True and an object made with input_symbols="", else ValueError)
+        proves another claim: there IS an input on which `program` runs running_time cycles over memory_length memory rows and writes
+        output_symbols.  The matrices are those of a run on that input; the input matrix given is dropped -- the input table has no rows
+        --, the input evaluation terminal is not sent (four terminals; the kernels' terminal vector holds zero in its slot) and the
+        weight of the processor table's terminal constraint against it is zero (deep_stark.dropped_weight).  Everything else is the
+        zero-knowledge mode's; each verifier without secret_input refuses such a proof, and verify_deep(secret_input=True) the others'."""
         return deep_stark.prove(self, program, (processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix), proof_stream,
-                                self.deep_shape(segmented, zero_knowledge))
+                                self.deep_shape(segmented, zero_knowledge), secret_input=secret_input)
 
     def deep_weight_count(self):
         """one weight per quotient: the tables' (boundary, transition, terminal within a table), then the permutation arguments'"""
@@ -972,7 +979,7 @@ class BrainfuckStark:
         first call writes, the others add.  weights: (deep_weight_count(), 3) uint64; weights of a table without rows are skipped."""
         deep_stark.compose_into(self, out, log_step, weights, challenges, terminals, domain)
 
-    def verify_deep(self, proof, segmented=False, zero_knowledge=False):
+    def verify_deep(self, proof, segmented=False, zero_knowledge=False, secret_input=False):
         """the verifier of prove_deep -- host code only (Python ints, hashlib, Fri.verify): the terminals against the public input, output
         and program; the opening of the 26 columns at the plan's points for the values the prover claims (read_rounds); every value of a
         table without rows zero; and
@@ -985,11 +992,17 @@ class BrainfuckStark:
         zero_knowledge=True verifies prove_deep(zero_knowledge=True)'s proofs of the same `segmented`: the roots and paths are salted
         ((salt, path) behind each opened row, checked with SaltedMerkle.verify), the last group holds the s blinded segments and the
         masking polynomial's value, which the opening alone uses, and the right-hand side is H(z) = sum_j z^(j L0) H_j'(z).  A proof of
-        another combination differs in width, salt or path shape and is refused."""
-        return deep_stark.verify(self, proof, self.deep_shape(segmented, zero_knowledge))          # (what deep_shape raises is about this object, not about the proof)
+        another combination differs in width, salt or path shape and is refused.
+        secret_input=True verifies prove_deep(secret_input=True)'s proofs on an object made with input_symbols="" (ValueError otherwise, and
+        without zero_knowledge=True): four terminals are read, the input evaluation argument is not compared, the dropped constraint's
+        weight is zero; the output and program terminals are checked as ever.  A proof with five terminals is refused, and a secret-input
+        proof by every verifier without secret_input: the object behind the last terminal is not what either expects there."""
+        # (what deep_shape and the secret-input check raise is about this object and this call, not about the proof)
+        return deep_stark.verify(self, proof, self.deep_shape(segmented, zero_knowledge), secret_input=secret_input)
 
     # ------------------------------------------------------------------------------------------------------------
-    def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None):
+    def check_trace(self, processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix, challenges=None, initials=None,
+                    secret_input=False):
         """Which constraints an execution trace breaks, on the GPU: a list of AirViolation, empty for an honest trace.  The base AIR of
         every table on the matrices as given (test_vm.py::test_air); with challenges (11 triples) and initials (2 triples) also the
         full AIR on padded, extended copies, each table against its own terminals, and then what no single table's AIR sees -- the
@@ -997,7 +1010,9 @@ class BrainfuckStark:
         program evaluation terminals against this stark's input_symbols, output_symbols and program (what verify() checks).
         Those come back as kind "permutation" (index 0 instruction, 1 memory) / "evaluation" (0 input, 1 output, 2 program) with
         first_row None; an input or output MATRIX that does not hold the symbols the processor read or wrote comes back the same way
-        under the table name "input" / "output".  The caller's matrices are left as they are."""
+        under the table name "input" / "output".  The caller's matrices are left as they are.
+        secret_input=True (the claim of prove_deep(secret_input=True): the input is not public) leaves out the two checks that name the
+        input -- the processor's input evaluation terminal against input_symbols, and the input matrix against what the processor read."""
         import copy
         matrices = {0: processor_matrix, 1: instruction_matrix, 2: memory_matrix, 3: input_matrix, 4: output_matrix}
         tables = []
@@ -1042,6 +1057,8 @@ class BrainfuckStark:
         # IO tables' terminal constraints are taken against those
         pairs += [("input", "evaluation", 0, inp.evaluation_terminal, pt.input_evaluation_terminal),
                   ("output", "evaluation", 1, outp.evaluation_terminal, pt.output_evaluation_terminal)]
+        if secret_input:
+            pairs = [pair for pair in pairs if pair[1:3] != ("evaluation", 0)]
         violations += [AirViolation(name, kind, k, None, 1) for name, kind, k, lhs, rhs in pairs if tuple(lhs) != tuple(rhs)]
         return violations
 

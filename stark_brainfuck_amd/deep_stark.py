@@ -6,7 +6,10 @@ BrainfuckStark.prove_deep / verify_deep / deep_shape / compose_into are this mod
 All four modes of the protocol -- segmented or not ("Segmented composition"), zero-knowledge or not ("Zero-knowledge openings")
 -- are ONE code path over a shape -- L, S, s, n, w, fri, domain, working_domain, k, m, L0, randomizer, hiding (`make_shape`) --, which the
 per-proof record carries as `p.shape`: the stages and the verifier read the shape and never ask which mode made it.  Without
-zero-knowledge k = m = 0, L0 = L and there is neither a masking polynomial nor a salt: no blinding launch, no draw, the same bytes.  What the stages share with prove() -- padding, the extension, the terminals' objects, the weights, the stage loop, the
+zero-knowledge k = m = 0, L0 = L and there is neither a masking polynomial nor a salt: no blinding launch, no draw, the same bytes.
+secret_input ("Secret input") is not a shape but a claim -- "some input gives this output" -- on the zero-knowledge shapes: the
+input table stays empty, the input evaluation terminal is not sent and one weight is zero (check_secret_input .. sent_terminals below say
+which).  What the stages share with prove() -- padding, the extension, the terminals' objects, the weights, the stage loop, the
 random source -- is reached through the `stark` object; this module does not import brainfuck_stark."""
 import ctypes
 import gc
@@ -22,6 +25,7 @@ from .fri import Fri
 from .ip import ProofStream
 from .pcs import MAX_EXT_COLUMNS, PolynomialCommitment
 from .table import lde_tables, prepare_extension
+from .vm import LazyTraceMatrix, VirtualMachine
 
 _u64 = ctypes.c_uint64
 
@@ -136,20 +140,78 @@ def compose_into(stark, out, log_step, weights, challenges, terminals, domain=No
         accumulate = 1
 
 
+# ---- the secret input ("Secret input"): what the mode leaves out, said once for the prover, the verifier and the DEBUG check
+def check_secret_input(stark, shape):
+    """the two refusals of secret_input=True: a claim that states its input, and a shape that hides nothing"""
+    if len(stark.input_symbols):
+        raise ValueError("secret_input=True proves knowledge of an input the claim does not state: construct the object with input_symbols=\"\"")
+    if not shape.hiding:
+        raise ValueError("secret_input=True needs zero_knowledge=True: without it the proof would hide nothing of the input")
+
+
+def _mentions_terminal(expression, index):
+    stack, seen = [expression], set()
+    while stack:
+        e = stack.pop()
+        if id(e) in seen:
+            continue
+        seen.add(id(e))
+        if e.op == "t" and e.val == index:
+            return True
+        stack += [c for c in (e.a, e.b) if c is not None]
+    return False
+
+
+def dropped_weight(stark):
+    """Which of the deep_weight_count() weights a secret-input proof replaces by zero: the position -- counted as compose_into and
+    _verify_stream count, through every table's air.all() in table order -- of the one terminal constraint of the processor table
+    that holds its running input evaluation against the input evaluation terminal (air.ProcessorAir.terminal: term(2) - IEV)"""
+    index, at, found = stark.input_table.terminal_index, 0, []
+    for t in stark.tables:
+        for kind, constraints in t.air.all():
+            for e in constraints:
+                if t is stark.processor_table and kind == "terminal" and _mentions_terminal(e, index):
+                    found.append(at)
+                at += 1
+    assert len(found) == 1, "the processor table has %d terminal constraints on the input evaluation terminal" % len(found)
+    return found[0]
+
+
+def secret_input_weights(stark, weights):
+    """the sampled weights ((count, 3) uint64, or a list of triples) as a secret-input proof uses them: a copy with dropped_weight() zero"""
+    at = dropped_weight(stark)
+    if isinstance(weights, np.ndarray):
+        weights = weights.copy()
+        weights[at] = 0
+    else:
+        weights = list(weights)
+        weights[at] = air.X0
+    return weights
+
+
+def sent_terminals(stark, secret_input):
+    """the indices (BrainfuckStark.get_terminals) of the terminals in the stream, in its order: all five, or all but the input evaluation"""
+    return [i for i in range(5) if not (secret_input and i == stark.input_table.terminal_index)]
+
+
 # ---- the prover: one function per stage of (stark, p), named after the `timing` key the stage ends on, over one per-proof record `p`
-def prove(stark, program, matrices, proof_stream, shape):
+def prove(stark, program, matrices, proof_stream, shape, secret_input=False):
     """BrainfuckStark.prove_deep on `shape`; matrices: processor, memory, instruction, input, output"""
     processor_matrix, memory_matrix, instruction_matrix, input_matrix, output_matrix = matrices
     assert len(processor_matrix) + len(program) == len(instruction_matrix)
+    if secret_input:
+        check_secret_input(stark, shape)
+        # the claim's input table has no rows; the caller's input matrix is dropped here, before any stage sees it
+        input_matrix = LazyTraceMatrix(np.zeros((0, stark.input_table.base_width), dtype=np.uint64), VirtualMachine.field)
     gc.freeze()          # (as prove(): the trace matrices' objects are not walked by collections during the proof)
     try:
         # domain, n: where the trace is extended to and H is computed from (the working domain); the commitments are pc's, on the shape's fri
         p = SimpleNamespace(matrices=(processor_matrix, instruction_matrix, memory_matrix, input_matrix, output_matrix), proof_stream=proof_stream,
                             domain=shape.working_domain, n=shape.w, stream=current_stream(), pc=PolynomialCommitment(shape.fri, hiding=shape.hiding),
-                            commitments=[], shape=shape)
+                            commitments=[], shape=shape, secret_input=bool(secret_input))
         own = lambda stage: lambda p: stage(stark, p)
         return stark._run_stages(p, (("pad", own(_stage_pad)), ("base_lde", own(_stage_base_lde)), ("base_commit", own(_stage_base_commit)),
-                                     ("extend", stark._stage_extend), ("ext_lde", own(_stage_ext_lde)), ("ext_commit", own(_stage_ext_commit)),
+                                     ("extend", own(_stage_extend)), ("ext_lde", own(_stage_ext_lde)), ("ext_commit", own(_stage_ext_commit)),
                                      ("composition", own(_stage_composition)), ("composition_commit", own(_stage_composition_commit)),
                                      ("opening", own(_stage_opening)), ("serialize", stark._stage_serialize)))
     finally:
@@ -205,6 +267,15 @@ def _stage_base_commit(stark, p):          # C0: the codewords as lde_tables wro
     p.commitments.append(p.pc.commit_evaluated(p.base_polys, p.base_committed, p.proof_stream))
 
 
+def _stage_extend(stark, p):
+    """prove()'s stage -- challenges, initials, extension, the five terminals, the trace against the AIR where check_air is set (the
+    processor's running input evaluation against its own last value).  Behind it a secret-input proof forgets the input evaluation
+    terminal: the slot holds zero from here on, in the kernels' terminal vector as in the verifier's"""
+    stark._stage_extend(p)
+    if p.secret_input:
+        p.terminals[stark.input_table.terminal_index] = air.X0
+
+
 def _stage_ext_lde(stark, p):
     p.ext_codewords, p.ext_coefficients, p.ext_stride, p.ext_blinding = _lde(stark, p, True)
     p.ext_polys = _polys(stark, p.ext_coefficients, p.ext_stride, True, p.shape.k)
@@ -219,9 +290,12 @@ def _stage_composition(stark, p):
     """terminals, weights, H on the S points offset * omega^(k w / S) of the working domain, and its S coefficients: a coset inverse
     transform of length S with root omega^(w / S) and the domain's offset"""
     from . import debug_checks
-    for t in stark._terminal_objects(p.terminals):
-        p.proof_stream.push(t)
+    terminal_objects = stark._terminal_objects(p.terminals)
+    for i in sent_terminals(stark, p.secret_input):
+        p.proof_stream.push(terminal_objects[i])
     p.weights = type(stark)._sample_weights(stark.deep_weight_count(), p.proof_stream.prover_fiat_shamir(), as_array=True)
+    if p.secret_input:
+        p.weights = secret_input_weights(stark, p.weights)
     S, step = p.shape.S, p.n // p.shape.S
     offset, omega = p.domain.offset.value, p.domain.omega.value
     p.h_values = XArray.empty(S, stark.xfield)
@@ -313,34 +387,47 @@ def _stage_opening(stark, p):
 
 
 # ---- the verifier
-def verify(stark, proof, shape):
-    """BrainfuckStark.verify_deep on `shape`: False with one printed line for every refusal, a malformed stream included; raises nothing"""
+def verify(stark, proof, shape, secret_input=False):
+    """BrainfuckStark.verify_deep on `shape`: False with one printed line for every refusal, a malformed stream included; raises nothing
+    (but the ValueErrors of check_secret_input, which are about the call and not about the proof)"""
+    if secret_input:
+        check_secret_input(stark, shape)
     try:
-        return _verify_stream(stark, ProofStream().deserialize(proof), shape)
+        return _verify_stream(stark, ProofStream().deserialize(proof), shape, secret_input)
     except Exception as e:          # whatever a stream that is not prove_deep's makes the readers raise
         print("malformed proof: %s" % type(e).__name__)
         return False
 
 
-def _verify_stream(stark, proof_stream, shape):
+def _verify_stream(stark, proof_stream, shape, secret_input=False):
     X0, X1, xadd, xsub, xmul, xinv, xpow = air.X0, air.X1, air.xadd, air.xsub, air.xmul, air.xinv, air.xpow
     canonical_limbs, sample_weights = type(stark)._canonical_limbs, type(stark)._sample_weights
     root0 = proof_stream.pull()
     challenges = tuple(sample_weights(11, proof_stream.verifier_fiat_shamir()))
     root1 = proof_stream.pull()
-    terminal_objects = [proof_stream.pull() for _ in range(5)]
-    terminals = [canonical_limbs(t) for t in terminal_objects]
-    stored = [tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0) for t in terminal_objects]
-    for io, ea in zip((stark.input_table, stark.output_table), stark.evaluation_arguments):          # the rule of _verify_head, as a refusal
-        if io.height != 0 and not any(stored[io.terminal_index]) and any(ea.compute_terminal(challenges)):
+    # the terminals the stream carries; the slot of one it does not carry (the secret input's evaluation) holds zero and is compared with nothing
+    sent = sent_terminals(stark, secret_input)
+    terminals, stored = [X0] * 5, [X0] * 5
+    for i in sent:
+        t = proof_stream.pull()
+        terminals[i] = canonical_limbs(t)
+        stored[i] = tuple(t.limbs()) if hasattr(t, "limbs") else (t.value, 0, 0)
+    checked = [(io, ea) for io, ea in zip((stark.input_table, stark.output_table, None), stark.evaluation_arguments) if ea.terminal_index in sent]
+    for io, ea in checked:          # the rule of _verify_head, as a refusal
+        if io is not None and io.height != 0 and not any(stored[io.terminal_index]) and any(ea.compute_terminal(challenges)):
             print("evaluation terminal of a non-empty input or output table is zero")
             return False
-    for ea in stark.evaluation_arguments:
+    for _, ea in checked:
         if tuple(ea.select_terminal(stored)) != tuple(ea.compute_terminal(challenges)):
             print("a terminal does not match the public input, output or program")
             return False
     weights = sample_weights(stark.deep_weight_count(), proof_stream.verifier_fiat_shamir())
+    if secret_input:
+        weights = secret_input_weights(stark, weights)
     root2 = proof_stream.pull()
+    if not isinstance(root2, (bytes, bytearray)):          # (a proof with another number of terminals: a terminal lies where this mode's root does)
+        print("the composition's root is not a digest")
+        return False
     z = tuple(stark.xfield.sample(proof_stream.verifier_fiat_shamir()).limbs())
     if z[1] == 0 and z[2] == 0:
         print("the drawn point lies in the base field")

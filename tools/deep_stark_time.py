@@ -7,6 +7,13 @@
     python tools/deep_stark_time.py --write-golden-segmented DIR
     python tools/deep_stark_time.py --zero-knowledge [--program ...] [--reps 5] [--json FILE]
     python tools/deep_stark_time.py --write-golden-zk DIR
+    python tools/deep_stark_time.py --secret-input [--program sum2|big|...] [--reps 5] [--json FILE]
+    python tools/deep_stark_time.py --write-golden-secret DIR
+
+--secret-input: prove_deep(zero_knowledge=True) on the claim with its input public beside prove_deep(zero_knowledge=True,
+secret_input=True) on the claim without it, unsegmented and segmented, alternating in one process by stage, proof bytes and verify_deep of
+each (profiles/deep_stark_secret_input.md).  --write-golden-secret DIR writes the secret-input proofs of SECRET_FIXTURES on the seeds
+b"deep-zk-secret-" + name, and DIR/deep_zk_secret.json.
 
 --zero-knowledge: prove_deep in its four modes (segmented or not, zero_knowledge or not) alternating in one process by stage, per stage
 the cost of zero-knowledge over its twin, proof bytes of all four for the program and the four fixture programs
@@ -176,6 +183,99 @@ def write_golden_zk(directory):
         f.write("\n")
 
 
+# the secret-input mode (prove_deep(zero_knowledge=True, secret_input=True)): claims WITHOUT their input -- the object is made with
+# input_symbols "" and the matrices are those of a run on the secret --, seeds, a list and a file name of their own
+SECRET_FIXTURE_LIST = "deep_zk_secret.json"
+# name -> (source, the secret the fixtures and timings run on): FRI domains 2^9 .. 2^11 (the loop of sum2 runs once per unit of its first symbol)
+SECRET_PROGRAMS = {"read2": (",>,<.", "ab"), "sum2": (",>,<[->+<]>.", "\x02\x03"), "plus1": ("+", ""), "two_io": (",.,.", "ab")}
+SECRET_FIXTURES = [("two_io", mode(), False)]
+
+_secret_claims = {}
+
+
+def secret_claim(name, secret=None):
+    """(program, running_time, output symbols, trace matrices) of SECRET_PROGRAMS[name] (else PROGRAMS[name], else the source `name`
+    itself) run on `secret` (default: the input listed with the program)"""
+    from stark_brainfuck_amd.vm import VirtualMachine
+    source, given = SECRET_PROGRAMS.get(name) or PROGRAMS.get(name) or (name, "")
+    given = given if secret is None else secret
+    if (name, given) not in _secret_claims:
+        program = VirtualMachine.compile(source)
+        running_time, inputs, outputs = VirtualMachine.run(program, input_data=list(given))
+        _secret_claims[name, given] = (program, running_time, outputs, VirtualMachine.simulate(program, input_data=list(inputs)))
+    return _secret_claims[name, given]
+
+
+def make_secret_stark(name, m=None, secret=None, program=None, running_time=None, output_symbols=None):
+    """the object of the claim "some input makes the program write this output": input_symbols "" -- it never sees the secret.
+    program, running_time, output_symbols: another claim's, for the verifiers that must refuse"""
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    m = mode() if m is None else m
+    own_program, own_time, outputs, matrices = secret_claim(name, secret)
+    return BrainfuckStark(own_time if running_time is None else running_time, len(matrices[1]), own_program if program is None else program, "",
+                          outputs if output_symbols is None else output_symbols, m["log_expansion_factor"], m["security_level"],
+                          m["folding_factor"], m["coset_leaves"], m["grinding_bits"])
+
+
+def secret_seed_tag(name):
+    return b"deep-zk-secret-" + name.encode()
+
+
+def secret_fixture_file(name, m, segmented):
+    return ("deep_zk_secret_segmented_" if segmented else "deep_zk_secret_") + fixture_file(name, m)[len("deep_"):]
+
+
+def secret_refusal(name, m, segmented):
+    """the ValueError's text if deep_shape refuses the zero-knowledge shape of this claim, else None"""
+    try:
+        make_secret_stark(name, m).deep_shape(segmented, True)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+def prove_secret_seeded(name, m=None, prepare=None, segmented=False, secret=None, secret_input=True, matrices=None):
+    """-> (stark, proof) of the secret-input claim `name` on the seeded randomness; secret_input=False: the same object and matrices
+    through the zero-knowledge mode alone (which claims the EMPTY input: its verifier refuses the proof when the program read anything)"""
+    from stark_brainfuck_amd import randomness
+    stark = make_secret_stark(name, m, secret)
+    if prepare is not None:
+        prepare(stark)
+    kwargs = {"segmented": segmented, "zero_knowledge": True}
+    if secret_input:
+        kwargs["secret_input"] = True
+    program, _, _, own = secret_claim(name, secret)
+    with randomness.override(modes.Stream(secret_seed_tag(name))):
+        proof = stark.prove_deep(program, *(own if matrices is None else matrices), **kwargs)
+    return stark, proof
+
+
+def write_golden_secret(directory):
+    os.makedirs(directory, exist_ok=True)
+    entries = []
+    for name, m, segmented in SECRET_FIXTURES:
+        stark, proof = prove_secret_seeded(name, m, segmented=segmented)
+        shape = stark.deep_shape(segmented, True)
+        kwargs = {"segmented": segmented, "zero_knowledge": True, "secret_input": True}
+        assert make_secret_stark(name, m).verify_deep(proof, **kwargs) is True, "%s %s does not verify" % (name, modes.mode_id(m))
+        assert prove_secret_seeded(name, m, segmented=segmented)[1] == proof, "two proofs on the same seed differ"
+        source, given = SECRET_PROGRAMS[name]
+        entry = {"file": secret_fixture_file(name, m, segmented), "name": name, "program": source, "secret": given,
+                 "output": "".join(secret_claim(name)[2]), "args": m, "segmented": segmented,
+                 "seed": "shake_256(b'bfs-golden-urandom' + %r)" % secret_seed_tag(name), "fri_domain_length": shape.n,
+                 "working_domain_length": shape.w, "segments": shape.s, "segment_length": shape.L, "composition_coefficients": shape.S,
+                 "trace_blinding_coefficients": shape.k, "segment_blinding_coefficients": shape.m, "proof_len": len(proof),
+                 "proof_sha256": hashlib.sha256(proof).hexdigest()}
+        with open(os.path.join(directory, entry["file"]), "wb") as f:
+            f.write(proof)
+        entries.append(entry)
+        print("wrote %s  %d bytes  sha256 %s" % (entry["file"], len(proof), entry["proof_sha256"][:16]), flush=True)
+    with open(os.path.join(directory, SECRET_FIXTURE_LIST), "w") as f:
+        json.dump({"made_by": "tools/deep_stark_time.py --write-golden-secret", "proofs": entries,
+                   "randomness": "randomness.override(tools.stark_fri_modes.Stream(b'deep-zk-secret-' + name))"}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def fixtures(directory=GOLDEN, listing=FIXTURE_LIST):
     path = os.path.join(directory, listing)
     if not os.path.exists(path):
@@ -219,6 +319,37 @@ def tamperings(proof):
             "a limb of a terminal": bytes_of(objects[:2] + [_bumped(objects[2])] + objects[3:]),
             "a digest of the composition's root": bytes_of(objects[:ROOT2_AT] + [bytes(root2)] + objects[ROOT2_AT + 1:]),
             "a truncated proof": proof[:len(proof) // 2]}
+
+
+def _altered(obj):
+    """`obj` with its smallest change -- one bit of a digest or salt, one limb or value of an element plus one, an integer plus one, in a
+    list or tuple its first item that can be changed -- or None where there is nothing to change (an empty list)"""
+    if isinstance(obj, (bytes, bytearray)):
+        return bytes(obj[:len(obj) // 2]) + bytes([obj[len(obj) // 2] ^ 1]) + bytes(obj[len(obj) // 2 + 1:]) if len(obj) else None
+    if hasattr(obj, "limbs"):
+        return _bumped(obj)
+    if hasattr(obj, "value"):
+        from stark_brainfuck_amd.air import P
+        return type(obj)((obj.value + 1) % P, obj.field)
+    if isinstance(obj, int) and not isinstance(obj, bool):
+        return obj + 1
+    if isinstance(obj, (list, tuple)):
+        for i, item in enumerate(obj):
+            changed = _altered(item)
+            if changed is not None:
+                return type(obj)(list(obj[:i]) + [changed] + list(obj[i + 1:]))
+    return None
+
+
+def object_tamperings(proof):
+    """name -> bytes: per pushed object of the proof the stream with that one object changed (_altered), whatever the stream's layout"""
+    objects = objects_of(proof)
+    out = {}
+    for i, obj in enumerate(objects):
+        changed = _altered(obj)
+        if changed is not None:
+            out["object %d of %d (%s)" % (i, len(objects), type(obj).__name__)] = bytes_of(objects[:i] + [changed] + objects[i + 1:])
+    return out
 
 
 def segment_tamperings(proof):
@@ -469,6 +600,50 @@ def zero_knowledge_sizes():
     return rows
 
 
+def time_secret_input(name, reps):
+    """the zero-knowledge mode with the claim's input public beside secret_input=True (the object made without the input), unsegmented
+    and segmented where the shape exists, by stage, ms, ALTERNATING in one process (a warm-up proof of each first, dropped); proof bytes;
+    verify_deep.  name: a key of SECRET_PROGRAMS, or "big" (which reads nothing: the two claims differ in the terminal alone)"""
+    from stark_brainfuck_amd.brainfuck_stark import BrainfuckStark
+    program, running_time, outputs, matrices = secret_claim(name)
+    given = (SECRET_PROGRAMS.get(name) or PROGRAMS.get(name) or (name, ""))[1]
+    make = {False: lambda: BrainfuckStark(running_time, len(matrices[1]), program, list(given), outputs), True: lambda: make_secret_stark(name)}
+    legs = {}
+    for segmented in (False, True):
+        if secret_refusal(name, mode(), segmented) is None:
+            for secret in (False, True):
+                label = "prove_deep%s_zk%s" % ("_segmented" if segmented else "", "_secret" if secret else "")
+                legs[label] = (secret, dict({"segmented": segmented, "zero_knowledge": True}, **({"secret_input": True} if secret else {})))
+    series = {label: {"totals": [], "stages": {}} for label in legs}
+    proofs = {}
+    for rep in range(reps + 1):
+        for label, (secret, kwargs) in legs.items():
+            stark = make[secret]()
+            stark.stage_timing = True
+            t0 = time.perf_counter()
+            proofs[label] = stark.prove_deep(program, *matrices, **kwargs)
+            _sync()
+            if rep:
+                series[label]["totals"].append((time.perf_counter() - t0) * 1e3)
+                for stage, seconds in stark.timing.items():
+                    series[label]["stages"].setdefault(stage, []).append(seconds * 1e3)
+    out = {}
+    for label, (secret, kwargs) in legs.items():
+        verify_ms = []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            assert make[secret]().verify_deep(proofs[label], **kwargs) is True
+            verify_ms.append((time.perf_counter() - t0) * 1e3)
+        out[label] = {"total_ms": _mmm(series[label]["totals"]), "stages_ms": {s: _mmm(v) for s, v in series[label]["stages"].items()},
+                      "proof_bytes": len(proofs[label]), "verify_ms": _mmm(verify_ms[1:])}
+    for label in [l for l in legs if l.endswith("_secret")]:
+        a, b = out[label[:-len("_secret")]], out[label]
+        b["cost_over_twin_ms"] = dict({s: round(b["stages_ms"][s]["median"] - a["stages_ms"][s]["median"], 4) for s in a["stages_ms"]},
+                                      total=round(b["total_ms"]["median"] - a["total_ms"]["median"], 4))
+        b["bytes_over_twin"] = b["proof_bytes"] - a["proof_bytes"]
+    return out
+
+
 def time_decimation(reps, log_in=20, log_out=19, coefficients=(1 << 16) + 1):
     """bfsg_decimate_rows from 2^log_in to 2^log_out words per row over 16 and 27 rows, beside the alternative it was chosen against -- a
     second transform of the kept `coefficients` coefficients per row onto the 2^log_out points -- and a device copy of the same output
@@ -525,6 +700,8 @@ def main():
     ap.add_argument("--write-golden-segmented", default=None)
     ap.add_argument("--zero-knowledge", action="store_true", help="the four modes of prove_deep alternating, their proof sizes")
     ap.add_argument("--write-golden-zk", default=None)
+    ap.add_argument("--secret-input", action="store_true", help="the zero-knowledge mode with and without secret_input alternating, their proof sizes")
+    ap.add_argument("--write-golden-secret", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     import torch
@@ -536,8 +713,18 @@ def main():
         return write_golden(args.write_golden_segmented, segmented=True)
     if args.write_golden_zk:
         return write_golden_zk(args.write_golden_zk)
+    if args.write_golden_secret:
+        return write_golden_secret(args.write_golden_secret)
     result = {}
-    if args.zero_knowledge:
+    if args.secret_input:
+        name = args.program
+        if name == "big":
+            SECRET_PROGRAMS["big"] = (modes.BIG, "")
+        result["program"] = name
+        result["proofs"] = time_secret_input(name, args.reps)
+        print("SECRET_INPUT " + json.dumps(result["proofs"], sort_keys=True), flush=True)
+        SECRET_PROGRAMS.pop("big", None)
+    elif args.zero_knowledge:
         name = args.program
         if name == "big":
             PROGRAMS["big"] = (modes.BIG, "")
